@@ -18,6 +18,11 @@ same 100 M reads), config 5 (64-profile distance matrix at k = 12, multiset prod
 ms_per_step / roofline / parity flag, and `end_to_end` (host-resident input: H2D, kernels, D2H of the table) for
 config 2.  --no-extra skips them; --workload matrix runs config 5 alone as the headline.
 
+--dump-outputs DIR (one GPU) writes what the last timed step computed -- `counts` (the balanced 4^k table) or, for --workload
+matrix, `distances` (the lower triangle, pair (i, j < i) at i * (i - 1) / 2 + j) -- as DIR/<name>.npy in float64, so that two
+builds can be compared output for output (the inputs are seeded: the same arguments give the same reads).  Beyond 2^21 entries
+(the k = 12 table has 2^24) a fixed sample stands in for the array: dump_outputs() says which.
+
 Rank 0 prints ONE JSON line (DESIGN.md section 5 defines the fields).
 """
 import argparse
@@ -39,6 +44,10 @@ FP64_MFMA_PEAK_T = 78.6    # fp64 matrix TFLOP/s (v_mfma_f64_16x16x4_f64: 2048 f
 PROFILE_ROUND = 'r6'
 VALU_CYCLES_PER_INSTRUCTION = 3.44   # measured: the k = 12 scatter's opcode mix priced by tools/price_stream.py (profiles/r6/valu_prices.md)
 PROFILE_DIR = os.path.join(ROOT, 'profiles', PROFILE_ROUND)
+DUMP_SAMPLE = 1 << 21      # --dump-outputs: entries of a larger array sampled (16 MiB as float64, as much again for their positions)
+DUMP_BLOCKS = 1 << 16      # --dump-outputs: block sums covering the whole of a sampled array (512 KiB)
+DUMP_SEED = 12345
+DUMP_MAX_BYTES = 64 << 20
 
 
 def source_sha():
@@ -313,7 +322,7 @@ def matrix_measure(ctx, k, P, dprof, host, metric_name, balance, steps, warmup, 
     out = {
         'metric': 'Gterms/s distance matrix (%d profiles k=%d, %s%s)' % (P, k, metric_name, ' balanced' if balance else ''),
         'value': terms / (elapsed / steps) / 1e9, 'unit': 'Gterms/s', 'ms_per_step': ms, 'steps': steps, 'pairs': pairs,
-        'dtype': 'f64' if metric != 2 else 'int64/f64-mfma', 'roofline': roofline,
+        'dtype': 'f64' if metric != 2 else 'int64/f64-mfma', 'roofline': roofline, 'values': vals,
     }
     if check and host:
         import oracle
@@ -337,6 +346,8 @@ def matrix_workload(args):
     ctx = _native.Context(0)
     dprof, host = matrix_profiles(ctx, args.k, args.profiles, args.profile_reads, keep_host=0 if args.no_cpu else 8)
     r = matrix_measure(ctx, args.k, args.profiles, dprof, host, args.metric, args.balance, args.steps, args.warmup, check=not args.no_cpu)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, {'distances': r['values']})
     line = {
         'metric': r['metric'], 'value': r['value'], 'unit': r['unit'], 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
         'ms_per_step': r['ms_per_step'], 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': r['dtype'], 'data': 'synthetic',
@@ -537,9 +548,10 @@ def run_extras(ctx, args, dev_buf, nbytes, headline_ms):
     def matrices():
         dprof, host = matrix_profiles(ctx, 12, args.profiles, args.profile_reads, keep_host=0 if args.no_cpu else 8)
         try:
-            extra['matrix_prod'] = matrix_measure(ctx, 12, args.profiles, dprof, host, 'prod', False, 3, 1, check=not args.no_cpu)
-            extra['matrix_sum'] = matrix_measure(ctx, 12, args.profiles, dprof, host, 'sum', False, 3, 1, check=not args.no_cpu)
-            extra['matrix_euclidean'] = matrix_measure(ctx, 12, args.profiles, dprof, host, 'euclidean', False, 3, 1, check=not args.no_cpu)
+            for metric in ('prod', 'sum', 'euclidean'):
+                r = matrix_measure(ctx, 12, args.profiles, dprof, host, metric, False, 3, 1, check=not args.no_cpu)
+                r.pop('values')                 # (an array: the line must stay JSON whichever later metric fails)
+                extra['matrix_' + metric] = r
         finally:
             ctx.free(dprof)
         return {'config': 'BASELINE config 5: %d profiles k=12 (%d reads each, seed 100+p) resident in HBM; see matrix_prod / matrix_sum / matrix_euclidean' % (args.profiles, args.profile_reads)}
@@ -690,6 +702,15 @@ def set_flag(attempt, what, rank=None, text=''):
     os.replace(tmp, path)      # (atomic: a reader sees the whole text or no file)
 
 
+def read_flag(attempt, what, rank=None):
+    """The text of a flag ('' when there is no such flag)."""
+    try:
+        with open(flag_path(attempt, what, rank)) as fh:
+            return fh.read().strip()
+    except OSError:
+        return ''
+
+
 def supervise_rank(args):
     """One rank of an N > 1 job, under torch.distributed.run: starts the worker process and watches it (see the head of this
     section).  Never imports torch, never touches the GPU.  Exit status: 0 iff a verified line was printed."""
@@ -708,19 +729,17 @@ def supervise_rank(args):
         while True:
             rc = child.poll()
             if rc is not None:
-                why = None if rc == 0 else 'the worker of rank %d exited with status %d' % (rank, rc)
+                # a worker that gives up says why in its own flag before it exits: that is the reason, whether its exit or a
+                # peer's flag is seen first
+                told = read_flag(attempt, 'failed', rank)
+                why = None if rc == 0 else 'the worker of rank %d exited with status %d%s' % (rank, rc, ' (%s)' % told if told else '')
                 break
             now = time.time()
             if started_at is None and os.path.exists(flag_path(attempt, 'started', rank)):
                 started_at = now
             peers = [r for r in range(world) if r != rank and os.path.exists(flag_path(attempt, 'failed', r))]
             if peers:
-                try:
-                    with open(flag_path(attempt, 'failed', peers[0])) as fh:
-                        told = fh.read().strip()
-                except OSError:
-                    told = ''
-                why = 'rank %d gave up on attempt %d (%s)' % (peers[0], attempt, told or 'no reason given')
+                why = 'rank %d gave up on attempt %d (%s)' % (peers[0], attempt, read_flag(attempt, 'failed', peers[0]) or 'no reason given')
             elif started_at is None and now - t0 > startup_limit:
                 why = 'the worker of rank %d did not start within %.0f s' % (rank, startup_limit)
             elif started_at is not None and now - started_at > run_limit:
@@ -772,7 +791,8 @@ def stub_rank(args):
     arithmetic, one reduce(SUM) of int64 tables to rank 0 per step, max-over-ranks timing, the per-bin comparison of the merged
     table with the single-stream one, rank 0's JSON line.  Exists so that the launcher / supervisor path of `python bench.py
     --gpus N` can be tested where there is no GPU; `value` is null.  --stub-hang-attempt A: every worker of attempt A stops
-    responding after it has started; --stub-fail-rank R: rank R's worker of attempt 1 dies before the rendezvous;
+    responding after it has started; --stub-fail-rank R: rank R's worker of attempt 1 gives up before the rendezvous (its reason
+    in its flag, exit status 3);
     --stub-hang-after-headline: rank 0 publishes its line (as after the headline reduce mode), then every worker hangs."""
     import torch
     import torch.distributed as td
@@ -789,7 +809,9 @@ def stub_rank(args):
     if args.worker:
         set_flag(args.attempt, 'started', rank)
     if args.attempt == 1 and args.stub_fail_rank == rank:
-        sys.exit(3)
+        if args.worker:                 # as a GPU worker that gives up: the reason in its flag, then exit status 3
+            set_flag(args.attempt, 'failed', rank, 'stub: rank %d failed before the rendezvous' % rank)
+        os._exit(3)
     if args.stub_hang_attempt == args.attempt:
         time.sleep(3600)
     join_process_group('gloo', rank, world, args.attempt)
@@ -1130,6 +1152,32 @@ def multi_gpu_worker(args):
         sys.exit('the merged table differs from the single-stream count')
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (name -> what the last timed step computed) as <path>/<name>.npy in float64.  One of
+    more than DUMP_SAMPLE entries is written as <name>_sample (one entry from each of DUMP_SAMPLE equal strata, drawn with
+    DUMP_SEED), <name>_sample_index (their positions) and <name>_block_sums (sums of DUMP_BLOCKS consecutive blocks that cover
+    every entry, the last one shorter)."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size <= DUMP_SAMPLE:
+            out[name] = a
+            continue
+        width = a.size // DUMP_SAMPLE
+        index = np.arange(DUMP_SAMPLE, dtype=np.int64) * width + np.random.default_rng(DUMP_SEED).integers(0, width, DUMP_SAMPLE)
+        out[name + '_sample'] = a[index]
+        out[name + '_sample_index'] = index
+        out[name + '_block_sums'] = np.add.reduceat(a, np.arange(0, a.size, -(-a.size // DUMP_BLOCKS)))   # (int64 counts: exact)
+    out = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in out.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError('--dump-outputs: %d bytes of outputs, more than %d' % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -1169,15 +1217,21 @@ def main():
     ap.add_argument('--profile-reads', type=int, default=2_000_000, help='matrix workload: reads per profile')
     ap.add_argument('--metric', default='prod', choices=['prod', 'sum', 'euclidean'])
     ap.add_argument('--balance', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='one GPU: write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MiB; see dump_outputs)')
     args = ap.parse_args()
 
-    # ---- launcher and supervisors: nothing above or in here imports torch.cuda, the native library or anything else that opens the GPU
-    if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
-        return launch_ranks(args)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     # KPAL_BENCH_FORCE_MULTI=1 (tests on a one-GPU box): a world of ONE rank takes the multi-GPU code path -- supervisor, worker,
     # communicators of size one, every reduce mode, the per-bin comparison with the single-stream count
     multi = world > 1 or (os.environ.get('KPAL_BENCH_FORCE_MULTI', '') == '1' and 'RANK' in os.environ)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1: ms_per_step is the time of one timed step')
+    if args.dump_outputs is not None and (args.gpus > 1 or multi or args.stub):
+        ap.error('--dump-outputs needs the one-GPU path (--gpus 1, no --stub)')
+    # ---- launcher and supervisors: nothing above or in here imports torch.cuda, the native library or anything else that opens the GPU
+    if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
+        return launch_ranks(args)
     if multi and not args.worker and os.environ.get('KPAL_BENCH_NO_SUPERVISOR', '') != '1':
         sys.exit(supervise_rank(args))
     if args.stub:
@@ -1201,6 +1255,8 @@ def main():
     ctx.synth_reads_device(2, 0, n_reads, L, dev_buf)     # seed 2
     ctx.sync()
     r = count_measure(ctx, k, dev_buf, nbytes, n_reads, L, args.strategy, args.steps, args.warmup)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, {'counts': r['table']})
     line = {
         'metric': 'Gbases/s k-mer counted (k=%d, %dbp synthetic)' % (k, L), 'value': r['value'], 'unit': 'Gbases/s',
         'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': r['ms_per_step'],

@@ -434,18 +434,20 @@ def test_bench_supervisor_keeps_a_measured_headline():
     assert 'attempt 2' not in p.stderr.decode()
 
 
-@pytest.mark.parametrize('fault', ['hang', 'rank_dies'])
+@pytest.mark.parametrize('fault', ['hang', 'rank_dies', 'rank0_dies'])
 def test_bench_supervisor_falls_back_to_a_fresh_worker(fault):
     """A first multi-GPU attempt that never returns must still end in a line: every rank under torch.distributed.run is a
     supervisor that starts the GPU worker as a child, and on a worker that does not finish in time (hang: every worker of
     attempt 1 stops responding after start-up) or dies (rank_dies: rank 1's worker exits before the rendezvous while rank 0's
     waits for it) ends the attempt on ALL ranks -- failure flags in the job's shared directory -- kills the workers' process
     groups and starts FRESH workers in the conservative mode (--reduce-via torch --serial-reduce, a new rendezvous).  Driven
-    with the CPU/gloo stub."""
+    with the CPU/gloo stub.  rank0_dies: rank 0's own worker gives up, and the line carries the reason the worker wrote in its
+    flag whether rank 0's supervisor sees that worker's exit or rank 1's flag first (test_bench_comm_init_that_never_returns
+    needs the same on the GPU)."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(KPAL_BENCH_RUN_TIMEOUT='4', KPAL_BENCH_STARTUP_TIMEOUT='120')
-    extra = ['--stub-hang-attempt', '1'] if fault == 'hang' else ['--stub-fail-rank', '1']
+    extra = {'hang': ['--stub-hang-attempt', '1'], 'rank_dies': ['--stub-fail-rank', '1'], 'rank0_dies': ['--stub-fail-rank', '0']}[fault]
     t0 = time.time()
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '0', '--stub'] + extra,
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
@@ -457,6 +459,8 @@ def test_bench_supervisor_falls_back_to_a_fresh_worker(fault):
     assert line['attempt'] == 2 and line['n_gpus'] == 2 and line['merged_equals_single_stream'] is True
     if fault == 'hang':
         assert 'did not finish within' in line['fallback_reason'], line
+    elif fault == 'rank0_dies':          # (its own exit first, or rank 1's flag that quotes it: the worker's reason either way)
+        assert '(stub: rank 0 failed before the rendezvous)' in line['fallback_reason'], line
     else:
         assert 'exited with status 3' in line['fallback_reason'] or 'gave up on attempt 1' in line['fallback_reason'], line
         assert time.time() - t0 < 120          # the peer's flag ends rank 0's wait at once, not its time limit
@@ -643,6 +647,66 @@ def test_bench_traffic_comes_from_the_committed_profiles():
             assert per['quad_hist'] < 1.1 * nbytes                               # the records read once, 64 MiB of staged forms written
         assert info['traffic_step'] == pytest.approx(sum(per.values()))
         assert 2.5 * nbytes < info['traffic_step'] < 7 * nbytes
+
+
+def test_bench_dump_outputs_without_gpu(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float64 .npy files; an array up to DUMP_SAMPLE entries whole, a larger one (the k = 12 table)
+    as a sample that is the same on every call, its positions and block sums that cover every entry -- at most 64 MiB in all.
+    Paths other than the one-GPU timed step are refused before anything starts."""
+    import bench
+    table = np.random.default_rng(3).integers(0, 5000, 4 ** 12)
+    bench.dump_outputs(str(tmp_path / 'a'), {'counts': table, 'distances': np.linspace(0, 1, 2016)})
+    bench.dump_outputs(str(tmp_path / 'b'), {'counts': table})
+    got = {f[:-4]: np.load(str(tmp_path / 'a' / f)) for f in os.listdir(str(tmp_path / 'a'))}
+    assert sorted(got) == ['counts_block_sums', 'counts_sample', 'counts_sample_index', 'distances']
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    index = got['counts_sample_index'].astype(np.int64)
+    assert index.size == bench.DUMP_SAMPLE and np.all(np.diff(index) > 0) and index[-1] < table.size
+    np.testing.assert_array_equal(got['counts_sample'], table[index])
+    np.testing.assert_array_equal(got['counts_sample'], np.load(str(tmp_path / 'b' / 'counts_sample.npy')))
+    assert got['counts_block_sums'].size == bench.DUMP_BLOCKS and got['counts_block_sums'].sum() == table.sum()
+    np.testing.assert_array_equal(got['distances'], np.linspace(0, 1, 2016))
+    for extra in (['--gpus', '2'], ['--stub']):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dump-outputs', str(tmp_path / 'c')] + extra,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+        assert p.returncode == 2 and b'--dump-outputs' in p.stderr and not os.path.exists(str(tmp_path / 'c')), extra
+
+
+def test_bench_refuses_zero_timed_steps():
+    """--steps sets the number of timed steps and ms_per_step is the time of one: no path of bench.py runs with none."""
+    for extra in ([], ['--gpus', '2'], ['--gpus', '2', '--stub'], ['--workload', 'matrix']):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'] + extra,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+        assert p.returncode == 2 and b'--steps must be at least 1' in p.stderr and not p.stdout.strip(), extra
+
+
+def test_bench_extras_stay_json_when_a_matrix_metric_fails(monkeypatch):
+    """run_extras: one extra failing never takes the line down (guarded) -- also when the matrix extra fails after one metric has
+    been measured: what matrix_measure hands back for --dump-outputs (the distances, an array) must not be left in the line."""
+    import argparse
+    import json
+    import bench
+
+    class NoGpu(object):                 # every call fails as on a box without a GPU, except freeing
+        def free(self, ptr):
+            pass
+
+        def __getattr__(self, name):
+            def fail(*a, **kw):
+                raise RuntimeError('no GPU: %s' % name)
+            return fail
+
+    def measure(ctx, k, P, dprof, host, metric_name, *rest, **kw):
+        if metric_name != 'prod':
+            raise RuntimeError('%s failed' % metric_name)
+        return {'ms_per_step': 1.0, 'values': np.zeros(P * (P - 1) // 2)}
+    monkeypatch.setattr(bench, 'matrix_profiles', lambda ctx, k, P, reads, keep_host=8: (0, []))
+    monkeypatch.setattr(bench, 'matrix_measure', measure)
+    args = argparse.Namespace(read_len=150, k=12, reads=1000, profiles=4, profile_reads=100, no_cpu=True)
+    extra = bench.run_extras(NoGpu(), args, 0, 1000 * 151, 1.0)
+    json.dumps(extra)
+    assert extra['matrix_prod'] == {'ms_per_step': 1.0} and 'sum failed' in extra['matrix']['error']
+    assert all('error' in extra[name] for name in ('end_to_end', 'skew', 'k15'))
 
 
 def test_fake_rccl_stand_in_covers_what_the_library_binds(tmp_path):

@@ -21,12 +21,11 @@ def sha(v):
     return hashlib.sha256(np.ascontiguousarray(v, dtype='<i8').tobytes()).hexdigest()
 
 
-# The pipelines AUTO no longer takes for any input -- the exact-offset 'partition' (round 1) and the level-2 variants
-# KPAL_LEVEL2=0/1 of the two-level path -- keep ONE cross-check each in the default run (test_small_partition_batches,
-# test_partition_pipelines_on_skewed_inputs, test_two_level_variants_of_level2); KPAL_TEST_RETIRED=1 puts them back into
-# every strategy loop.
+# The exact-offset 'partition' (round 1), which AUTO no longer takes for any input, keeps its own cross-checks in the default
+# run (test_small_partition_batches, test_partition_pipelines_on_skewed_inputs); KPAL_TEST_RETIRED=1 puts it back into every
+# strategy loop.  The level-2 variants KPAL_LEVEL2=0/1 of the two-level path are checked at k = 13, 14
+# (test_two_level_variants_of_level2) and k = 15 (test_two_level_k15_against_oracle).
 RETIRED = os.environ.get('KPAL_TEST_RETIRED', '0') not in ('', '0')
-retired = pytest.mark.skipif(not RETIRED, reason='retired pipeline: KPAL_TEST_RETIRED=1 runs its full matrix')
 
 
 def strategies(k):
@@ -543,7 +542,7 @@ def test_full_size_k15(ctx):
         ctx.free(d)
 
 
-@pytest.mark.parametrize('mode', [pytest.param('0', marks=retired), pytest.param('1', marks=retired), '2'])
+@pytest.mark.parametrize('mode', ['0', '1', '2'])
 def test_two_level_k15_against_oracle(mode):
     """k = 15 (64 coarse buckets) through every level-2 pipeline, on inputs large enough for AUTO to take
     the two-level path (feeds above 256 KiB), bin for bin against the oracle: noisy reads, one unbroken

@@ -20,12 +20,19 @@ def test_rccl_collectives_on_table_view():
     assert 'NCCL_VIEW_OK' in out
 
 
-def test_bench_single_gpu_small():
-    """bench.py contract on a small workload: one JSON line with roofline and a true checksum."""
+def test_bench_single_gpu_small(tmp_path):
+    """bench.py contract on a small workload: one JSON line with roofline and a true checksum; --dump-outputs writes the sampled
+    balanced table of the last timed step, whose block sums add up to the checksum."""
     import json
+    import numpy as np
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1',
-                        '--reads', '2000000', '--cpu-reads', '200000', '--cpu-big-reads', '1000000', '--profile-reads', '100000'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        '--reads', '2000000', '--cpu-reads', '200000', '--cpu-big-reads', '1000000', '--profile-reads', '100000',
+                        '--dump-outputs', str(tmp_path / 'out')], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
+    dumped = {f[:-4]: np.load(str(tmp_path / 'out' / f)) for f in os.listdir(str(tmp_path / 'out'))}
+    assert sorted(dumped) == ['counts_block_sums', 'counts_sample', 'counts_sample_index']
+    assert all(a.dtype == np.float64 for a in dumped.values()) and dumped['counts_sample'].size == 1 << 21
+    assert dumped['counts_block_sums'].sum() == 2 * 2000000 * (150 - 12 + 1)
     line = json.loads(p.stdout.decode().strip().splitlines()[-1])
     for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
                 'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline'):
@@ -140,21 +147,41 @@ def _finish_world(procs):
 
 _ASYNC = {'KPAL_FAKE_RCCL_ASYNC': '1', 'KPAL_FAKE_RCCL_DELAY_MS': '15'}
 
+# rank processes of the worlds below alive at one time: with the pytest process (it has the GPU open as well) no more than 6
+# processes have the GPU open at once
+_MAX_RANKS = 4
+
 
 @pytest.fixture(scope='module')
 def worlds(tmp_path_factory):
     """The five worlds of rccl_world_rank.py the tests below look at -- three with a fault switch of the stand-in, the healthy ones
-    of 2 and 4 ranks -- started TOGETHER (sixteen processes on the one GPU; each world has its own shared-memory file): run one
-    after the other they spent a minute of the GPU suite's time box mostly asleep in the stand-in's bounded waits."""
+    of 2 and 4 ranks -- started in groups of at most _MAX_RANKS processes on the one GPU (each world has its own shared-memory
+    file): the two-rank worlds two at a time, so the stand-in's bounded waits of the fault worlds overlap."""
     tmp = tmp_path_factory.mktemp('worlds')
     lib = _build_fake_rccl(tmp)
-    started = {}
+    plan = []                                   # (name, world, id file, extra environment)
     for fault in ('reduce', 'recv', 'early'):
         extra = dict(_ASYNC) if fault == 'early' else {}
-        started['fault-' + fault] = _start_world(lib, str(tmp / ('id_' + fault)), 2, KPAL_FAKE_RCCL_FAULT=fault, KPAL_FAKE_RCCL_TIMEOUT_S='20', **extra)
+        plan.append(('fault-' + fault, 2, str(tmp / ('id_' + fault)), dict(extra, KPAL_FAKE_RCCL_FAULT=fault, KPAL_FAKE_RCCL_TIMEOUT_S='20')))
     for world in (2, 4):
-        started['async-%d' % world] = _start_world(lib, str(tmp / ('id_w%d' % world)), world, **_ASYNC)
-    return {name: _finish_world(procs) for name, procs in started.items()}
+        plan.append(('async-%d' % world, world, str(tmp / ('id_w%d' % world)), dict(_ASYNC)))
+    done = {}
+    while plan:
+        group, ranks = [], 0
+        while plan and (not group or ranks + plan[0][1] <= _MAX_RANKS):
+            name, world, id_file, extra = plan.pop(0)
+            group.append((name, _start_world(lib, id_file, world, **extra)))
+            ranks += world
+        try:
+            for name, procs in group:
+                done[name] = _finish_world(procs)
+        finally:                                # (a world past its time limit: no process of the group outlives the fixture)
+            for _, procs in group:
+                for p in procs:
+                    if p.poll() is None:
+                        p.kill()
+                        p.wait()
+    return done
 
 
 @pytest.mark.parametrize('fault', ['reduce', 'recv', 'early'])

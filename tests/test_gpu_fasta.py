@@ -656,8 +656,9 @@ def test_sharded_fasta_count_through_rccl_world_1(tmp_path, tutorial_dir):
     script = tmp_path / 'dist_count.py'
     script.write_text(code)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
+    # (in tmp_path: memh5 leaves an empty out.k8 placeholder in the working directory, and a second run must not find it there)
     p = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
-                        '--master-port', '29611', str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+                        '--master-port', '29611', str(script)], env=env, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     out = p.stdout.decode()
     assert p.returncode == 0 and 'DIST_COUNT_OK' in out, out[-3000:]
 
