@@ -109,6 +109,78 @@ def test_metrics_numpy_helpers():
     np.testing.assert_allclose(metrics.pairwise['prod'](l, r), abs(l - r) / ((l + 1) * (r + 1)))
 
 
+def test_matrix_cases_sit_on_their_boundaries():
+    """Every profile set of the matrix dispatch rows (tests/test_gpu_matrix_paths.py) has the properties its label claims:
+    largest / smallest count, negative counts, the exact |x|^2 of the Gram-limit cases, the degenerate profiles."""
+    import matrix_cases
+    import test_gpu_matrix_paths as rows
+    cases = sorted({(r[4], r[0], r[1]) for r in rows.ROWS})
+    assert len(cases) >= 40
+    for kind, k, P in cases:
+        matrix_cases.check_label(matrix_cases.build(kind, k, P))
+    n53 = matrix_cases.build('norm_2p53m1', 6, 40)
+    norms = matrix_cases.properties(n53)['norms']
+    assert max(norms) == (1 << 53) - 1 and all(v < 1 << 53 for v in norms)
+    assert max(matrix_cases.properties(matrix_cases.build('norm_2p53', 6, 40))['norms']) == 1 << 53
+    assert matrix_cases.build('max_1023', 6, 40).profiles.max() == 1023 < 1024
+    assert matrix_cases.build('max_511', 6, 70).profiles.max() == 511
+    assert not (matrix_cases.build('neg_small', 6, 12).profiles == -1).any()
+
+
+def test_oracle_matrix_values_follow_numpy_on_wrapping_counts():
+    """oracle.distance_matrix_values with its pairs dealt to threads -- the call every matrix row is compared with -- restates
+    metrics.multiset / metrics.euclidean with NumPy's int64 wrap-around: on the negative and int64-extreme sets its entries
+    are NumPy's own values, bit for bit, and on the int64-extreme set 'prod' and 'sum' have finite entries that differ from
+    arithmetic without the wrap-around."""
+    import matrix_cases
+    import oracle
+    for kind in ('neg_small', 'neg_large', 'int64_extreme'):
+        case = matrix_cases.build(kind, 4, 12)
+        P, h = case.P, case.P // 2
+        mats = {m: oracle.distance_matrix_values(case.profiles, 4, False, m, threads=os.cpu_count() or 1)
+                for m in ('prod', 'sum', 'euclidean')}
+        for i, j in ((h, 0), (h + 1, 0), (h + 1, h), (P - 2, h), (P - 1, h), (1, 0)):
+            l, r = case.profiles[i], case.profiles[j]
+            with np.errstate(all='ignore'):
+                keep = np.where(np.logical_or(l, r))
+                x, y = l[keep], r[keep]
+                prod = (np.abs(x - y) / ((x + 1) * (y + 1))).sum() / (len(x) + 1)
+                sum_ = (np.abs(x - y) / (x + y + 1)).sum() / (len(x) + 1)
+                d = np.subtract(l, r)
+                euc = np.sqrt(np.dot(d, d))
+            at = i * (i - 1) // 2 + j
+            got = [mats['prod'][at], mats['sum'][at], mats['euclidean'][at]]
+            np.testing.assert_array_equal(got, [prod, sum_, euc], err_msg='%s %d %d' % (kind, i, j))
+            if kind == 'int64_extreme' and i != P - 1 and (j == 0 or (i, j) == (h + 1, h)):
+                for pw, value in (('prod', prod), ('sum', sum_)):
+                    assert np.isfinite(value)
+                    assert abs(matrix_cases.multiset_model(l, r, pw) - value) <= 1e-12 * abs(value)
+            if kind == 'int64_extreme' and i == P - 1:
+                assert mats['prod'][at] == np.inf                  # the -1 of profile P - 1
+
+
+def test_matrix_rows_agree_with_their_cases():
+    """The launch sets of the tiled matrix rows follow from the labels of their profile sets: the staged multiset kernels
+    give up exactly when a count is negative or reaches their limit (2^16 for 'prod', 1024 for 'sum'), the Gram path exactly
+    when some |x|^2 reaches 2^53.  A case edited off its boundary, or a row edited away from its case, fails here."""
+    import matrix_cases
+    import test_gpu_matrix_paths as rows
+    for k, P, metric, bal, kind, expected, _ in rows.ROWS:
+        if k < 6 or P <= 8:
+            assert expected == {'matrix_tile': 1}
+            continue
+        lab = matrix_cases.build(kind, k, P).label if not bal else None
+        if lab is None:
+            continue                                               # (balanced plain profiles: counts at most 2 x 200)
+        limit = {'prod': 1 << 16, 'sum': 1024}.get(metric)
+        if limit is not None:
+            gives_up = lab['min'] < 0 or lab['max'] >= limit
+            assert ('matrix_super' in expected) == gives_up, (k, P, metric, kind)
+        else:
+            assert ('matrix_super' in expected) == (max(lab['norms']) >= 1 << 53), (k, P, metric, kind)
+            assert expected.get('gram_mfma') == (2 if P > 64 else 1), (k, P, metric, kind)
+
+
 def test_shard_range():
     from kpal_amd import dist
     for n in (0, 1, 7, 100, 10 ** 8):

@@ -3,6 +3,7 @@ kpal-compatible Python API) with the oracle and the reference goldens.
 Integers bit-exact; fp64 multiset sums within 1e-9 relative (north_star tolerance; observed
 ~1e-15).  Run on the GPU box: pytest -m gpu."""
 import io
+import math
 import os
 
 import numpy as np
@@ -13,6 +14,8 @@ import oracle
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-9
+THREADS = os.cpu_count() or 1                      # the oracle's pairs dealt to the host's cores (each value still single-threaded)
+METRIC_NAMES = ('prod', 'sum', 'euclidean')
 
 
 @pytest.fixture(scope='module')
@@ -177,16 +180,17 @@ def test_matrix_vs_pairs_and_oracle(ctx):
         for metric in ('prod', 'sum', 'euclidean'):
             for bal in (False, True):
                 got = ctx.distance_matrix(profs, k, ('prod', 'sum', 'euclidean').index(metric), do_balance=bal)
-                if P <= 13:
-                    want = oracle.distance_matrix_values(profs, k, bal, metric)
-                else:
-                    want = np.array([ctx.pair_distance(profs[i], profs[j], ('prod', 'sum', 'euclidean').index(metric),
-                                                       do_balance=bal, k=k) for i in range(1, P) for j in range(i)])
-                assert got.shape == want.shape
-                if metric == 'euclidean':
-                    np.testing.assert_array_equal(got, want)
-                else:
-                    np.testing.assert_allclose(got, want, rtol=RTOL, atol=0)
+                # every entry against the oracle; past 13 profiles against the pair kernel as well
+                wants = [oracle.distance_matrix_values(profs, k, bal, metric, threads=THREADS)]
+                if P > 13:
+                    wants.append(np.array([ctx.pair_distance(profs[i], profs[j], ('prod', 'sum', 'euclidean').index(metric),
+                                                             do_balance=bal, k=k) for i in range(1, P) for j in range(i)]))
+                for want in wants:
+                    assert got.shape == want.shape
+                    if metric == 'euclidean':
+                        np.testing.assert_array_equal(got, want)
+                    else:
+                        np.testing.assert_allclose(got, want, rtol=RTOL, atol=0)
 
 
 def test_matrix_super_tiles(ctx):
@@ -195,7 +199,8 @@ def test_matrix_super_tiles(ctx):
     reports them and the pair-of-counts kernel reruns: int64 path next to the float path) and the same shapes with every
     count below 2^16 (the difference-of-reciprocals kernel's own result: table and computed reciprocals, zero masks);
     at k = 12 enough bins per thread for the packed byte counters of the term counts to be flushed; and (big = None) every
-    count below 1024: multiset 'sum' on its reciprocal-table kernel up to the last table entries."""
+    count below 1024: multiset 'sum' on its reciprocal-table kernel up to the last table entries.  Every entry against the
+    oracle; past 17 profiles, and at k = 12, against the pair kernel as well."""
     rs = np.random.RandomState(17)
     for k, P, big in ((6, 9, True), (6, 16, True), (7, 17, True), (6, 33, True), (8, 20, True),
                       (6, 9, False), (7, 17, False), (6, 33, False), (8, 20, False), (9, 64, False),
@@ -218,24 +223,26 @@ def test_matrix_super_tiles(ctx):
         for metric in ('prod', 'sum', 'euclidean'):
             code = ('prod', 'sum', 'euclidean').index(metric)
             got = ctx.distance_matrix(profs, k, code)
-            if P <= 17:
-                want = oracle.distance_matrix_values(profs, k, False, metric)
-            else:
-                want = np.array([ctx.pair_distance(profs[i], profs[j], code) for i in range(1, P) for j in range(i)])
-            if metric == 'euclidean':
-                np.testing.assert_array_equal(got, want)
-            else:
-                np.testing.assert_allclose(got, want, rtol=RTOL, atol=0)
+            # every entry against the oracle; past 17 profiles against the pair kernel as well
+            wants = [oracle.distance_matrix_values(profs, k, False, metric, threads=THREADS)]
+            if P > 17:
+                wants.append(np.array([ctx.pair_distance(profs[i], profs[j], code) for i in range(1, P) for j in range(i)]))
+            for want in wants:
+                if metric == 'euclidean':
+                    np.testing.assert_array_equal(got, want)
+                else:
+                    np.testing.assert_allclose(got, want, rtol=RTOL, atol=0)
     k, P = 12, 10
     profs = [ctx.count_bytes(k, oracle.synth_reads(300 + p, 0, 60000, 150)) for p in range(P)]
     profs[3][:1000] += 1 << 32
     for code in (0, 1, 2):
         got = ctx.distance_matrix(profs, k, code)
-        want = np.array([ctx.pair_distance(profs[i], profs[j], code) for i in range(1, P) for j in range(i)])
-        if code == 2:
-            np.testing.assert_array_equal(got, want)
-        else:
-            np.testing.assert_allclose(got, want, rtol=RTOL, atol=0)
+        for want in (oracle.distance_matrix_values(profs, k, False, METRIC_NAMES[code], threads=THREADS),
+                     np.array([ctx.pair_distance(profs[i], profs[j], code) for i in range(1, P) for j in range(i)])):
+            if code == 2:
+                np.testing.assert_array_equal(got, want)
+            else:
+                np.testing.assert_allclose(got, want, rtol=RTOL, atol=0)
     metric = 'prod'
     for i, j in ((1, 0), (3, 2), (9, 3)):
         assert close(ctx.distance_matrix(profs, k, 0)[i * (i - 1) // 2 + j], oracle.distance(profs[i], profs[j], k, metric=metric))
@@ -246,7 +253,7 @@ def test_matrix_all_staged_once(ctx):
     sum): every profile count around their geometry's edges -- 17 / 32 (the 256-thread form, a last block of one / four
     rows), 33 / 48 / 61 / 64 (the 1024-thread form; dead slots; a diagonal slot whose second block is past the end) -- with
     zero bins (term counts from the zero masks), counts beyond the reciprocal table of 'prod' and up to the last entries of
-    the table of 'sum'; every pair against kpal_pair_distance (IEEE divisions), a sample of pairs against the oracle."""
+    the table of 'sum'; every pair against the oracle and against kpal_pair_distance (IEEE divisions)."""
     rs = np.random.RandomState(23)
     for k, P in ((6, 17), (6, 32), (7, 33), (6, 48), (6, 61), (7, 64), (6, 18), (6, 29)):
         profs = [rs.poisson(rs.choice([0.3, 5.0, 90.0]), 4 ** k).astype(np.int64) for _ in range(P)]
@@ -258,6 +265,7 @@ def test_matrix_all_staged_once(ctx):
         profs[P - 2][:] = 0                                                           # an empty profile: every bin a both-zero candidate
         for code, metric in ((0, 'prod'), (1, 'sum')):
             got = ctx.distance_matrix(profs, k, code)
+            np.testing.assert_allclose(got, oracle.distance_matrix_values(profs, k, False, metric, threads=THREADS), rtol=RTOL, atol=0)
             want = np.array([ctx.pair_distance(profs[i], profs[j], code) for i in range(1, P) for j in range(i)])
             np.testing.assert_allclose(got, want, rtol=RTOL, atol=0)
             for i, j in ((1, 0), (P - 1, P - 2), (P - 1, 0), (P // 2, 3), (P - 2, 1)):
@@ -345,14 +353,14 @@ def test_config5_matrix_k12_subset(ctx):
 def test_config5_matrix_k12_64_profiles(ctx, n_reads):
     """BASELINE config 5 at its stated size: 64 profiles at k = 12, profile p = the
     count of n_reads synthetic reads with seed 100 + p (dense: 2 M reads, mean 16.6 per bin; sparse: 100 k
-    reads, ~43 % zero bins), kdistlib.distance_matrix values through kpal_distance_matrix_device (the
-    super-tile kernels; euclidean on the matrix cores) for prod / sum / euclidean with and without balancing
-    (kdistlib.py:164-186):
-      * ALL 2016 entries against the oracle (its pair function on every pair, dealt to the host's cores) for multiset prod,
-        multiset sum and (dense) euclidean -- matrix_rdiff, matrix_rsum and gram_mfma at full P; the 276 entries of the first
-        24 profiles for the other combinations (dense: prod balanced; sparse: euclidean): <= 1e-9 relative, euclidean
-        bit-identical,
-      * 60 entries against the pair kernel (IEEE divisions, another summation order),
+    reads, ~43 % zero bins), kdistlib.distance_matrix values through kpal_distance_matrix_device (64 profiles: multiset on the
+    kernels that stage every profile once, matrix_rdiff_all / matrix_rsum_all; euclidean on the matrix cores, gram_mfma) for
+    prod / sum / euclidean, prod also balanced on the dense variant (kdistlib.py:164-186):
+      * ALL 2016 entries against the oracle (its pair function on every pair, dealt to the host's cores) for multiset prod
+        (dense and sparse), multiset sum (dense and sparse) and euclidean (dense): <= 1e-9 relative, euclidean bit-identical;
+      * the 276 entries of the first 24 profiles against the oracle for the other two combinations (dense: prod balanced;
+        sparse: euclidean);
+      * 60 entries of every combination against the pair kernel (IEEE divisions, another summation order);
       * the text of a 12-profile sub-matrix through kdistlib.distance_matrix against the oracle's text."""
     from kpal_amd import klib, kdistlib
     k, P = 12, 64
@@ -374,12 +382,9 @@ def test_config5_matrix_k12_64_profiles(ctx, n_reads):
             assert 0.40 < np.mean(host[0] == 0) < 0.46          # the sparse variant really is sparse
         pairs = [(i, j) for i in range(1, P) for j in range(i)]
         pick = [pairs[t] for t in rs.choice(len(pairs), 60, replace=False)]
-        # the oracle on ALL 2016 pairs for the default metric (both variants), on the 276 pairs of the first 24 profiles for the
-        # other combinations (2016 pairs x 4^12 bins cost the host ~12 s each)
-        # (round 6: the GPU suite's time box -- all 2016 pairs against the oracle for 'prod' (both variants); 'sum' and euclidean against
-        # the oracle on the 276 pairs of the first 24 profiles and against the pair kernels (IEEE divisions; int64, bit for bit) on 60 pairs
-        # anywhere in the matrix)
-        full = {('prod', False)}
+        # the oracle on ALL 2016 pairs for prod, sum and (dense) euclidean; on the 276 pairs of the first 24 profiles for the other two
+        # combinations (2016 pairs x 4^12 bins cost the host ~12 s each)
+        full = {('prod', False), ('sum', False), ('euclidean', False)} if n_reads == 2_000_000 else {('prod', False), ('sum', False)}
         sub = 24
         combos = [('prod', False), ('prod', True), ('sum', False), ('euclidean', False)]   # (sum / euclidean with balancing: the smaller tests)
         if n_reads != 2_000_000:
@@ -414,3 +419,149 @@ def test_config5_matrix_k12_64_profiles(ctx, n_reads):
     finally:
         ctx.free(d)
         ctx.free(dprof)
+
+
+def _multiset_expression(left, right, pairwise):
+    """metrics.multiset (kpal/metrics.py:101-123) evaluated here: the reference's mask and NumPy terms, the terms summed
+    exactly (math.fsum) -- or, when a term is not finite, by NumPy, which is then exact as well (inf, -inf or NaN)."""
+    left, right = np.asanyarray(left), np.asanyarray(right)
+    with np.errstate(all='ignore'):
+        keep = np.logical_or(left, right)
+        x, y = left[keep], right[keep]
+        terms = np.abs(x - y) / ((x + 1) * (y + 1)) if pairwise == 'prod' else np.abs(x - y) / (x + y + 1)
+        terms = np.asarray(terms, dtype=np.float64)
+        total = math.fsum(terms) if np.isfinite(terms).all() else terms.sum()
+    return total / (len(terms) + 1), len(terms)
+
+
+def close_strict(a, b):
+    """close() without its absolute floor: subnormal results must agree to 1e-9 relative as well."""
+    if np.isnan(b) or np.isinf(b):
+        return close(a, b)
+    return abs(a - b) <= RTOL * abs(b)
+
+
+def _float_vectors():
+    """(name, left, right) float64 pairs for kpal_pair_distance_f64."""
+    rs = np.random.RandomState(31)
+    from kpal_amd import metrics
+    out = []
+    for n in [0, 1, 2, 3, 255, 257] + [4 ** k for k in range(1, 11)] + [4 ** 12]:
+        l = rs.poisson(rs.choice([0.5, 16.6]), n).astype(np.int64)
+        r = rs.poisson(rs.choice([0.5, 16.6, 200.0]), n).astype(np.int64)
+        if n and not r.any():
+            r[0] = 3
+        if n and not l.any():
+            l[-1] = 1
+        for down in (False, True):
+            with np.errstate(all='ignore'):
+                ls, rsc = metrics.get_scale(l, r)              # (one of the factors is 1.0, the other the totals' ratio)
+            if down:
+                ls, rsc = metrics.scale_down(ls, rsc)
+            out.append(('scaled_n%d%s' % (n, '_down' if down else ''), l * ls, r * rsc))
+    n = 4 ** 6
+    a = rs.uniform(-0.9, 40.0, n)
+    b = rs.uniform(-0.9, 40.0, n)
+    a[rs.rand(n) < 0.3] = 0.0
+    out.append(('non_integer', a, b))
+    c, d = a.copy(), b.copy()
+    c[rs.randint(0, n, 40)] = -rs.uniform(1.5, 30.0, 40)    # negative denominators: negative terms
+    d[rs.randint(0, n, 40)] = -rs.uniform(1.5, 30.0, 40)
+    out.append(('negative', c, d))
+    e = c.copy()
+    e[[5, 77]] = -1.0                                        # x + 1 == 0: the terms are +inf / NaN
+    out.append(('x_plus_1_zero', e, d))
+    f = b.copy()
+    f[9] = -1.0
+    g = f.copy()                                             # -1 against -1: 0 / 0
+    out.append(('both_minus_1', f, g))
+    for name, val in (('nan', np.nan), ('inf', np.inf), ('minus_inf', -np.inf)):
+        h = a.copy()
+        h[100] = val
+        out.append((name, h, b))
+    z, w = a.copy(), b.copy()
+    z[:50] = -0.0                                            # falsy in logical_or: no term where both are (-)0
+    w[:50] = 0.0
+    w[50:60] = -0.0
+    z[50:60] = 0.0
+    out.append(('minus_zero', z, w))
+    s = np.zeros(n)
+    s[::3] = np.finfo(np.float64).tiny * rs.rand((n + 2) // 3)   # subnormals (and a few zeros)
+    s[1] = 5e-324
+    t = np.zeros(n)
+    t[::5] = 5e-324 * rs.randint(1, 1000, (n + 4) // 5)
+    out.append(('subnormal', s, t))
+    out.append(('subnormal_vs_counts', s, b))
+    return out
+
+
+def test_pair_distance_f64_vs_oracle_and_expression(ctx):
+    """kpal_pair_distance_f64 (metrics.multiset on float vectors; ProfileDistance's NumPy path after do_scale) for prod and sum
+    against oracle.multiset on float64 and against the reference's expression evaluated here: the same number of terms, the
+    value within 1e-9 relative, the same NaN / infinity."""
+    for name, l, r in _float_vectors():
+        for code, pw in ((0, 'prod'), (1, 'sum')):
+            got, m = ctx.pair_distance_f64(l, r, code, return_aux=True)
+            want, m_want = _multiset_expression(l, r, pw)
+            assert m == m_want, (name, pw, m, m_want)
+            with np.errstate(all='ignore'):
+                o, m_o = oracle.multiset(l, r, pw, return_m=True)
+            assert m_o == m_want, (name, pw)
+            assert close_strict(got, want), (name, pw, got, want)
+            assert close_strict(got, o), (name, pw, got, o)
+            if want == 0:
+                assert got == 0, (name, pw, got)
+
+
+def test_float_multiset_through_the_api(ctx):
+    """metrics.multiset on float64 x float64 and int64 x float64 vectors (kpal_pair_distance_f64), and ProfileDistance with
+    a summary callable and do_scale -- the reference's NumPy pipeline ending in that kernel -- against the oracle's
+    ProfileDistance with the built-in summary the callable mimics."""
+    from kpal_amd import klib, kdistlib, metrics
+    rs = np.random.RandomState(37)
+    n = 4 ** 7
+    li = rs.poisson(3.0, n).astype(np.int64)
+    ri = rs.poisson(40.0, n).astype(np.int64)
+    ri[rs.rand(n) < 0.2] = 0
+    lf, rf = li * 13.25, ri * 0.375
+    for pw in ('prod', 'sum'):
+        f = metrics.pairwise[pw]
+        for a, b in ((lf, rf), (li, rf), (lf, ri)):
+            got = metrics.multiset(a, b, f)
+            assert close(got, oracle.multiset(a, b, pw)), (pw, a.dtype, b.dtype)
+            assert close(got, _multiset_expression(a, b, pw)[0]), (pw, a.dtype, b.dtype)
+    k = 5
+    mimic = {'min': lambda v: np.min(v), 'median': lambda v: np.median(v)}
+    for trial in range(3):
+        l = rs.poisson(rs.choice([0.5, 4.0, 30.0]), 4 ** k).astype(np.int64)
+        r = rs.poisson(rs.choice([0.5, 4.0, 30.0]), 4 ** k).astype(np.int64)
+        for summary, fn in mimic.items():
+            for down in (False, True):
+                for pw in ('prod', 'sum'):
+                    dist = kdistlib.ProfileDistance(do_smooth=True, summary=fn, do_scale=True, down=down,
+                                                    pairwise=metrics.pairwise[pw])
+                    got = dist.distance(klib.Profile(l.copy()), klib.Profile(r.copy()))
+                    want = oracle.profile_distance(l, r, k, do_smooth=True, summary=summary, do_scale=True, down=down,
+                                                   metric=pw)
+                    assert close(got, want), (trial, summary, down, pw, got, want)
+
+
+def test_vector_length_and_cosine_on_int64(ctx):
+    """metrics.vector_length (the pair kernel against a zero vector) and metrics.cosine_similarity on int64 vectors, wrapping
+    ones included, against the oracle's euclidean(v, 0) -- np.sqrt(np.dot(v, v)) with int64 wrap-around -- bit for bit."""
+    from kpal_amd import metrics
+    rs = np.random.RandomState(41)
+    vecs = [rs.poisson(20.0, 4 ** 6).astype(np.int64), rs.randint(-1000, 1000, 4 ** 8).astype(np.int64),
+            np.array([3, 4], dtype=np.int64), np.array([1 << 31, 1 << 31], dtype=np.int64),       # dot = 2^63: wraps negative
+            np.array([np.iinfo(np.int64).max, 5, -7], dtype=np.int64), np.array([1 << 32, 3], dtype=np.int64),  # wraps to 9
+            np.array([-(1 << 62), 1 << 62, 12345], dtype=np.int64), np.zeros(17, dtype=np.int64)]
+    for v in vecs:
+        want = oracle.euclidean(v, np.zeros_like(v))
+        got = metrics.vector_length(v)
+        assert got == want or (np.isnan(got) and np.isnan(want)), (v[:4], got, want)
+    for a, b in ((vecs[0], vecs[0][::-1].copy()), (vecs[1], vecs[1] * 3), (vecs[3], vecs[3]), (vecs[4], vecs[4][::-1].copy()),
+                 (vecs[6], vecs[6] + 1)):
+        with np.errstate(all='ignore'):
+            want = np.dot(a, b) / (oracle.euclidean(a, np.zeros_like(a)) * oracle.euclidean(b, np.zeros_like(b)))
+            got = metrics.cosine_similarity(a, b)
+        assert got == want or (np.isnan(got) and np.isnan(want)), (a[:4], b[:4], got, want)
