@@ -116,6 +116,35 @@ int kpal_count_feed_fasta(kpal_ctx *ctx, const uint8_t *host_buf, size_t nbytes)
 int kpal_count_feed_fasta_file(kpal_ctx *ctx, const char *path, uint64_t begin, uint64_t end, const uint8_t *prefix, size_t prefix_len);
 /* The flattening alone (tests): host_out needs nbytes bytes; records are each preceded by '\n'. */
 int kpal_fasta_flatten(kpal_ctx *ctx, const uint8_t *host_buf, size_t nbytes, uint8_t *host_out, uint64_t *n_out);
+/* FASTQ reads (Profile.from_fastq; beyond the reference, which reads FASTA only).  Four-line records: a title line beginning
+ * with '@', the sequence line, a separator line beginning with '+' (the rest of it is ignored), the quality line; lines end at
+ * '\n', a '\r' just before it is dropped; the role of a line follows from its index mod 4 alone (a quality line may begin with
+ * '@' or '+').  Every record contributes '\n' + its sequence bytes, verbatim, to the stream the counters see (k-mers never span
+ * two reads).  len(quality) must equal len(sequence).  Empty lines at the very end of the text are ignored; the last line may lack
+ * its '\n'; an empty read (empty sequence and quality lines) is legal.  Wrapped (multi-line) FASTQ is malformed.
+ * min_quality >= 0 masks bases: base i becomes 'N' (a byte outside the alphabet: it breaks windows) when
+ * qual[i] - quality_offset < min_quality, and a quality byte below quality_offset or above '~' is malformed; min_quality < 0
+ * (no mask) only length-checks the quality line.  quality_offset is 33 or 64; min_quality <= 93.
+ * The text of one count may be cut ANYWHERE between the feeds of kpal_count_begin .. kpal_count_finish: the library carries the
+ * unfinished record (in host memory) into the next FASTQ feed, and kpal_count_finish ends the text -- it tokenises what is left
+ * with the options of the last FASTQ feed, and returns KPAL_E_INVALID if that is a cut-off record.  A malformed record makes the
+ * feed (or the finish) return KPAL_E_INVALID with "malformed FASTQ record N: ..." (N 1-based over the count's text) in
+ * kpal_last_error(); the count is abandoned then (the next call that needs it is KPAL_E_STATE until kpal_count_begin).
+ * The text goes to the device in 64 MiB chunks (KPAL_FASTA_CHUNK) by the pinned staging of the FASTA path; every chunk is
+ * tokenised on the device (fastq_kernels.hpp) behind the carried rest of the chunk before, its status read back once, and counted
+ * while the next chunk is copied and tokenised. */
+typedef struct kpal_fastq_options {
+    int min_quality;     /* < 0: no mask */
+    int quality_offset;  /* 33 (Sanger / Illumina 1.8+) or 64 (Illumina 1.3-1.7) */
+} kpal_fastq_options;
+int kpal_count_feed_fastq(kpal_ctx *ctx, const uint8_t *host_buf, size_t nbytes, const kpal_fastq_options *opt /* NULL: no mask, 33 */);
+/* The same for the bytes [begin, end) of a FILE (end = 0: to its end), read by the library's parallel preads straight into the
+ * pinned staging buffers, as kpal_count_feed_fasta_file does; the range continues the text of the FASTQ feeds before it. */
+int kpal_count_feed_fastq_file(kpal_ctx *ctx, const char *path, uint64_t begin, uint64_t end, const kpal_fastq_options *opt);
+/* The tokenising alone (tests): the whole text in one call, ended; host_out needs nbytes bytes and receives the exact stream
+ * the counters would see.  Independent of the begin / feed / finish state. */
+int kpal_fastq_flatten(kpal_ctx *ctx, const uint8_t *host_buf, size_t nbytes, const kpal_fastq_options *opt, uint8_t *host_out,
+                       uint64_t *n_out);
 /* Profile.from_fasta_by_record, klib.py:114-133, batched: host_flat holds n_records records,
  * record r = bytes [starts[r], starts[r+1]) (starts ascending, starts[n_records] = nbytes; put a
  * separator byte such as '\n' between records so that no window spans two of them).  host_out

@@ -6,6 +6,7 @@ raises -- loudly -- instead of computing something on the host.
 """
 import ctypes
 import os
+import numbers
 import threading
 
 import numpy as np
@@ -36,6 +37,11 @@ class DistanceOptions(ctypes.Structure):
 
 
 _optp = ctypes.POINTER(DistanceOptions)
+
+
+class FastqOptions(ctypes.Structure):
+    """``kpal_fastq_options`` of include/kpal_hip.h: the base mask of a FASTQ count (min_quality < 0: none)."""
+    _fields_ = [('min_quality', ctypes.c_int), ('quality_offset', ctypes.c_int)]
 
 
 class ProfileStats(ctypes.Structure):
@@ -71,6 +77,9 @@ SIGNATURES = {
     'kpal_count_feed_fasta': (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
     'kpal_count_feed_fasta_file': (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, _vp, ctypes.c_size_t]),
     'kpal_fasta_flatten': (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.POINTER(ctypes.c_uint64)]),
+    'kpal_count_feed_fastq': (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.POINTER(FastqOptions)]),
+    'kpal_count_feed_fastq_file': (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(FastqOptions)]),
+    'kpal_fastq_flatten': (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.POINTER(FastqOptions), _vp, ctypes.POINTER(ctypes.c_uint64)]),
     'kpal_count_records': (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     'kpal_fasta_records_begin': (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     'kpal_fasta_records_index': (ctypes.c_int, [_vp, _vp, _vp]),
@@ -183,6 +192,20 @@ def load():
                 fn.argtypes = args
             _lib = L
     return _lib
+
+
+def fastq_options_check(min_quality, quality_offset):
+    """ValueError unless ``min_quality`` is None (no mask) or in 0..93 and ``quality_offset`` is 33 or 64."""
+    if quality_offset not in (33, 64) or isinstance(quality_offset, bool):
+        raise ValueError('quality_offset must be 33 or 64 (got %r)' % (quality_offset,))
+    if min_quality is not None and (isinstance(min_quality, bool) or not isinstance(min_quality, numbers.Integral)
+                                    or not 0 <= min_quality <= 93):
+        raise ValueError('min_quality must be None or an integer in 0..93 (got %r)' % (min_quality,))
+
+
+def _fastq_options(min_quality, quality_offset):
+    fastq_options_check(min_quality, quality_offset)
+    return FastqOptions(-1 if min_quality is None else int(min_quality), int(quality_offset))
 
 
 def _check(rc):
@@ -353,6 +376,31 @@ class Context(object):
         out = np.empty(max(a.size, 1), dtype=np.uint8)
         n = ctypes.c_uint64(0)
         _check(self._L.kpal_fasta_flatten(self._h, a.ctypes.data if a.size else None, a.size, out.ctypes.data, ctypes.byref(n)))
+        return out[:n.value].tobytes()
+
+    def count_feed_fastq(self, buf, min_quality=None, quality_offset=33):
+        """buf: FASTQ text (bytes-like) cut anywhere -- the library carries an unfinished record into the next FASTQ feed and
+        ``count_finish`` ends the text; tokenised (and masked: bases whose quality is below ``min_quality``) and counted on the GPU.
+        A malformed record raises ValueError naming it."""
+        a = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf, dtype=np.uint8)
+        opt = _fastq_options(min_quality, quality_offset)
+        if a.size:
+            _check(self._L.kpal_count_feed_fastq(self._h, a.ctypes.data, a.size, ctypes.byref(opt)))
+
+    def count_feed_fastq_file(self, path, begin=0, end=0, min_quality=None, quality_offset=33):
+        """The bytes [begin, end) of a FASTQ file (end = 0: to its end), read by the library itself (parallel preads into its
+        pinned staging buffers), tokenised and counted on the GPU, chunks pipelined."""
+        opt = _fastq_options(min_quality, quality_offset)
+        _check(self._L.kpal_count_feed_fastq_file(self._h, os.fsencode(path), int(begin), int(end), ctypes.byref(opt)))
+
+    def fastq_flatten(self, buf, min_quality=None, quality_offset=33):
+        """-> the flat byte stream the counting kernels see for this (whole) FASTQ text (tests)."""
+        a = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf, dtype=np.uint8)
+        out = np.empty(max(a.size, 1), dtype=np.uint8)
+        n = ctypes.c_uint64(0)
+        opt = _fastq_options(min_quality, quality_offset)
+        _check(self._L.kpal_fastq_flatten(self._h, a.ctypes.data if a.size else None, a.size, ctypes.byref(opt), out.ctypes.data,
+                                          ctypes.byref(n)))
         return out[:n.value].tobytes()
 
     def count_feed_device(self, dev_ptr, nbytes):

@@ -1,4 +1,4 @@
-// kpal_count.hip -- the counting front end of the C-ABI (begin / feed / feed_device / feed_fasta / records / finish),
+// kpal_count.hip -- the counting front end of the C-ABI (begin / feed / feed_device / feed_fasta / feed_fastq / records / finish),
 // strategy choice, piece sizes, H2D staging, and the launchers of the LDS-direct, global-atomic and round-1
 // partition pipelines.  The quad record pipelines live in kpal_quads.hip / kpal_quads2.hip.
 #include "kpal_host.hpp"
@@ -8,6 +8,7 @@
 #include "chunk_kernels.hpp"
 #include "fasta_kernels.hpp"
 #include "fasta_host.hpp"
+#include "fastq_kernels.hpp"
 
 #include <cerrno>
 #include <fcntl.h>
@@ -20,6 +21,8 @@ static_assert(sizeof(ChunkPool) <= sizeof(kpal_ctx::chunk_pool_sent), "kpal_ctx:
 // ----------------------------------------------------------------------------------------------
 // counting
 // ----------------------------------------------------------------------------------------------
+static void fq_reset(kpal_ctx *ctx);
+
 KPAL_API int kpal_count_begin(kpal_ctx *ctx, int k)
 {
     CTX_ENTER(ctx);
@@ -45,6 +48,7 @@ KPAL_API int kpal_count_begin(kpal_ctx *ctx, int k)
     ctx->cached_steps1 = ctx->cached_steps2 = 0;
     ctx->sample_hot_rows = false;           // (the verdict of a sample of THIS count only: kpal_quads2.hip reads it for cached tile sizes)
     ctx->plan_strategy = ctx->plan_steps1 = ctx->plan_steps2 = 0;
+    fq_reset(ctx);                          // (the unfinished FASTQ record of an abandoned count)
     ctx->counting = true;
     return KPAL_OK;
 }
@@ -808,6 +812,282 @@ KPAL_API int kpal_fasta_flatten(kpal_ctx *ctx, const uint8_t *host_buf, size_t n
     return fasta_pipeline(ctx, src, false, host_out, n_out);
 }
 
+// ----------------------------------------------------------------------------------------------
+// FASTQ ingest: text (a byte range of a file, or host memory) -> pinned staging -> device, behind the rest of the chunk before
+// that no record finished -> tokenised on the device (fastq_kernels.hpp) -> counted.  Unlike a FASTA chunk, a FASTQ chunk cannot
+// tell from its own bytes where its records begin (a quality line may begin with '@'), so every chunk begins at a record: the
+// status of a chunk (where its unfinished rest begins, its flattened size, its first bad record) is read back once, and the next
+// chunk is tokenised behind that rest.  The count of chunk i is queued behind the tokenising of chunk i + 1, and the pool reads
+// chunk i + 1 while chunk i is copied and tokenised.
+// ----------------------------------------------------------------------------------------------
+static const char *fq_error_text(unsigned kind)
+{
+    switch (kind) {
+    case kFqNoAt: return "the title line does not begin with '@'";
+    case kFqNoPlus: return "the separator line does not begin with '+'";
+    case kFqLength: return "the quality line is not as long as the sequence line";
+    case kFqCutOff: return "the record is cut off at the end of the text";
+    default: return "a quality byte outside the range of the quality offset";
+    }
+}
+
+static int fq_options(const kpal_fastq_options *opt, FqMask &m)
+{
+    m.min_quality = opt ? opt->min_quality : -1;
+    m.offset = opt ? opt->quality_offset : 33;
+    if (m.offset != 33 && m.offset != 64) return set_err(KPAL_E_INVALID, "quality_offset must be 33 or 64 (got %d)", m.offset);
+    if (m.min_quality > 93) return set_err(KPAL_E_INVALID, "min_quality must be at most 93 (got %d)", m.min_quality);
+    if (m.min_quality < 0) m.min_quality = -1;
+    return KPAL_OK;
+}
+
+// The text = carry_in, then the source.  final_text: the text ends with the source (a record still open there is cut off); else
+// the unfinished rest goes to *carry_out (which may be carry_in).  records: records finished before, advanced.  count: the stream
+// is counted into the running count; else it is copied to host_out (*n_out bytes).
+static int fastq_pipeline(kpal_ctx *ctx, FaSource &src, const std::vector<uint8_t> &carry_in, bool final_text, FqMask m,
+                          uint64_t &records, bool count, uint8_t *host_out, uint64_t *n_out, std::vector<uint8_t> *carry_out)
+{
+    const size_t stage = ctx->fa_chunk, pad = kpal_ctx::kStagePad;
+    CHK(ensure_pinned(ctx));
+    if (!ctx->fq_status_host) {
+        hipError_t e = hipHostMalloc((void **)&ctx->fq_status_host, kFqStatusWords * sizeof(unsigned long long), hipHostMallocDefault);
+        if (e != hipSuccess) {
+            ctx->fq_status_host = nullptr;
+            return set_err(KPAL_E_NOMEM, "hipHostMalloc failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (!ctx->fq_ev) HIPCHK(hipEventCreateWithFlags(&ctx->fq_ev, hipEventDisableTiming));
+    CHK(ensure(ctx, ctx->fq_status, kFqStatusWords * sizeof(unsigned long long)));
+    HIPCHK(hipStreamSynchronize(ctx->copy_stream));   // (another path's copy out of a pinned buffer may still be running)
+
+    // the carried text: fq_raw[cslot][cstart, cstart + clen)
+    int cslot = 1;
+    uint64_t cstart = 0, clen = carry_in.size();
+    if (clen) {
+        CHK(ensure(ctx, ctx->fq_raw[1], clen + 64));
+        HIPCHK(hipMemcpyAsync(ctx->fq_raw[1].p, carry_in.data(), clen, hipMemcpyHostToDevice, ctx->stream));
+    }
+    uint8_t *pin[2] = {(uint8_t *)ctx->pinned[0], (uint8_t *)ctx->pinned[1]};
+    bool ra = false;               // the pool is reading the next chunk into pin[slot]
+    size_t ra_n = 0;
+    std::vector<int> ra_ok;
+    struct PoolGuard {
+        bool &active;
+        ~PoolGuard()
+        {
+            if (active) HostPool::instance().wait();   // (an error return must not leave the pool writing into a staging buffer)
+        }
+    } guard{ra};
+    int pend_slot = -1;            // tokenised, not consumed yet: fq_flat[pend_slot], pend_n bytes
+    uint64_t pend_n = 0, out_total = 0;
+    auto consume = [&]() -> int {
+        if (pend_slot < 0) return KPAL_OK;
+        uint8_t *flat = (uint8_t *)ctx->fq_flat[pend_slot].p + pad;
+        if (pend_n) {
+            if (count) CHK(count_device_range(ctx, flat, (size_t)pend_n, 0));   // (whole records: no window crosses the seam)
+            else HIPCHK(hipMemcpyAsync(host_out + out_total, flat, pend_n, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        out_total += pend_n;
+        pend_slot = -1;
+        return KPAL_OK;
+    };
+    auto read_failed = [&](const std::vector<int> &ok) -> int {
+        for (int e : ok)
+            if (e) return set_err(KPAL_E_IO, "reading the FASTQ input failed: %s", strerror(e));
+        return KPAL_OK;
+    };
+
+    int slot = 0;
+    for (bool first = true;; first = false) {
+        size_t m_bytes = 0;
+        if (ra) {
+            HostPool::instance().wait();
+            ra = false;
+            CHK(read_failed(ra_ok));
+            m_bytes = ra_n;
+            src.pos += ra_n;
+        } else if (src.pos < src.end) {
+            m_bytes = (size_t)std::min<uint64_t>(stage, src.end - src.pos);
+            std::vector<int> ok;
+            fa_copy_start(src, pin[slot], src.pos, m_bytes, ok);
+            HostPool::instance().wait();
+            CHK(read_failed(ok));
+            src.pos += m_bytes;
+        } else if (!(first && clen)) {
+            break;
+        }
+        const bool last = src.pos >= src.end;
+        const bool fin = final_text && last;
+        if (!last) {   // the next chunk into the other pinned buffer (its copy to the device ended before the status below)
+            ra_n = (size_t)std::min<uint64_t>(stage, src.end - src.pos);
+            fa_copy_start(src, pin[slot ^ 1], src.pos, ra_n, ra_ok);
+            ra = true;
+        }
+        const uint64_t n = clen + m_bytes;
+        if (n >= ((uint64_t)1 << 32) - 64)
+            return set_err(KPAL_E_INVALID, "FASTQ record %llu: a record (or a run of empty lines) longer than 4 GiB",
+                           (unsigned long long)records + 1);
+        const uint32_t nb = (uint32_t)((n + kFaBlockBytes - 1) / kFaBlockBytes);
+        CHK(ensure(ctx, ctx->fq_raw[slot], n + 64));   // (never the carry's buffer: cslot != slot)
+        CHK(ensure(ctx, ctx->fq_flat[slot], n + pad + 64));
+        CHK(ensure(ctx, ctx->fq_pos, n * sizeof(uint32_t) + 64));
+        CHK(ensure(ctx, ctx->fq_meta, (size_t)(nb + 1) * 16 + (size_t)nb * 8 + 64));
+        uint8_t *raw = (uint8_t *)ctx->fq_raw[slot].p;
+        uint8_t *flat = (uint8_t *)ctx->fq_flat[slot].p + pad;
+        uint64_t *line_offs = (uint64_t *)ctx->fq_meta.p;
+        uint64_t *kept_offs = line_offs + nb + 1;
+        uint32_t *nl_cnt = (uint32_t *)(kept_offs + nb + 1);
+        uint32_t *kept = nl_cnt + nb;
+        uint32_t *pos = (uint32_t *)ctx->fq_pos.p;
+        unsigned long long *st = (unsigned long long *)ctx->fq_status.p;
+        if (clen) HIPCHK(hipMemcpyAsync(raw, (const uint8_t *)ctx->fq_raw[cslot].p + cstart, clen, hipMemcpyDeviceToDevice, ctx->stream));
+        if (m_bytes) {
+            HIPCHK(hipMemcpyAsync(raw + clen, pin[slot], m_bytes, hipMemcpyHostToDevice, ctx->copy_stream));
+            HIPCHK(hipEventRecord(ctx->ev_copied[slot], ctx->copy_stream));
+            HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied[slot], 0));
+        }
+        HIPCHK(hipMemsetAsync(st, 0xFF, 2 * sizeof(unsigned long long), ctx->stream));
+        HIPCHK(hipMemsetAsync(st + 2, 0, (kFqStatusWords - 2) * sizeof(unsigned long long), ctx->stream));
+        const unsigned rec_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n / 4 / 256 + 1, (uint64_t)ctx->num_cu * 4));
+        LAUNCH(ctx, "fq_newlines", (fa_mark_count_kernel<0>), dim3(nb), dim3(kFaThreads), (const uint8_t *)raw, n, nl_cnt);
+        LAUNCH(ctx, "fq_line_scan", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)nl_cnt, nb, line_offs);
+        LAUNCH(ctx, "fq_newline_pos", fq_newline_pos_kernel, dim3(nb), dim3(kFaThreads), (const uint8_t *)raw, n, (const uint64_t *)line_offs, pos);
+        LAUNCH(ctx, "fq_records", fq_record_kernel, dim3(rec_grid), dim3(256), (const uint8_t *)raw, n, (const uint32_t *)pos,
+               (const uint64_t *)(line_offs + nb), fin ? 1 : 0, st);
+        LAUNCH(ctx, "fq_carry", fq_carry_kernel, dim3(1), dim3(1), (const uint32_t *)pos, (const uint64_t *)(line_offs + nb), n, st);
+        LAUNCH(ctx, "fq_count", fq_count_kernel, dim3(nb), dim3(kFaThreads), (const uint8_t *)raw, n, (const uint64_t *)line_offs, nb,
+               (const uint32_t *)pos, m, st, kept);
+        LAUNCH(ctx, "fq_offset", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)kept, nb, kept_offs);
+        LAUNCH(ctx, "fq_scatter", fq_scatter_kernel, dim3(nb), dim3(kFaThreads), (const uint8_t *)raw, n, (const uint64_t *)line_offs, nb,
+               (const uint32_t *)pos, m, st, (const uint64_t *)kept_offs, flat);
+        HIPCHK(hipMemcpyAsync(ctx->fq_status_host, st, kFqStatusWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipEventRecord(ctx->fq_ev, ctx->stream));
+        CHK(consume());                          // the chunk before: its count runs behind this chunk's tokenising
+        HIPCHK(hipEventSynchronize(ctx->fq_ev));
+        const unsigned long long *hs = ctx->fq_status_host;
+        if (hs[0] != ~0ull)
+            return set_err(KPAL_E_INVALID, "malformed FASTQ record %llu: %s", (unsigned long long)(records + (hs[0] >> 3) + 1),
+                           fq_error_text((unsigned)(hs[0] & 7)));
+        records += hs[2];
+        cslot = slot;
+        cstart = fin ? n : hs[3];
+        clen = n - cstart;
+        pend_slot = slot;
+        pend_n = hs[4];
+        slot ^= 1;
+    }
+    if (carry_out) {
+        carry_out->resize((size_t)clen);
+        if (clen) {
+            HIPCHK(hipMemcpyAsync(carry_out->data(), (const uint8_t *)ctx->fq_raw[cslot].p + cstart, clen, hipMemcpyDeviceToHost, ctx->copy_stream));
+            HIPCHK(hipStreamSynchronize(ctx->copy_stream));
+        }
+    }
+    CHK(consume());
+    if (!count) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        *n_out = out_total;
+    }
+    return KPAL_OK;
+}
+
+static void fq_reset(kpal_ctx *ctx)
+{
+    ctx->fq_carry.clear();
+    ctx->fq_records = 0;
+    ctx->fq_open = false;
+}
+
+// One FASTQ feed of a count; a malformed record abandons the count.
+static int fastq_feed(kpal_ctx *ctx, FaSource &src, const FqMask &m)
+{
+    ctx->fq_open = true;
+    ctx->fq_min_quality = m.min_quality;
+    ctx->fq_offset = m.offset;
+    const int rc = fastq_pipeline(ctx, src, ctx->fq_carry, false, m, ctx->fq_records, true, nullptr, nullptr, &ctx->fq_carry);
+    if (rc != KPAL_OK) {
+        fq_reset(ctx);
+        ctx->counting = false;
+    }
+    return rc;
+}
+
+// kpal_count_finish: the end of the FASTQ text -- the record the last feed left unfinished is tokenised and counted, or is an error.
+static int fastq_end(kpal_ctx *ctx)
+{
+    int rc = KPAL_OK;
+    if (!ctx->fq_carry.empty()) {
+        FaSource src;
+        const FqMask m = {ctx->fq_min_quality, ctx->fq_offset};
+        rc = fastq_pipeline(ctx, src, ctx->fq_carry, true, m, ctx->fq_records, true, nullptr, nullptr, nullptr);
+    }
+    fq_reset(ctx);
+    if (rc != KPAL_OK) ctx->counting = false;
+    return rc;
+}
+
+KPAL_API int kpal_count_feed_fastq(kpal_ctx *ctx, const uint8_t *host_buf, size_t nbytes, const kpal_fastq_options *opt)
+{
+    CTX_ENTER(ctx);
+    if (!ctx->counting) return set_err(KPAL_E_STATE, "kpal_count_feed_fastq before kpal_count_begin");
+    FqMask m;
+    CHK(fq_options(opt, m));
+    if (nbytes == 0) return KPAL_OK;
+    if (!host_buf) return set_err(KPAL_E_INVALID, "host_buf is NULL");
+    FaSource src;
+    src.mem = host_buf;
+    src.end = nbytes;
+    return fastq_feed(ctx, src, m);
+}
+
+KPAL_API int kpal_count_feed_fastq_file(kpal_ctx *ctx, const char *path, uint64_t begin, uint64_t end, const kpal_fastq_options *opt)
+{
+    CTX_ENTER(ctx);
+    if (!ctx->counting) return set_err(KPAL_E_STATE, "kpal_count_feed_fastq_file before kpal_count_begin");
+    if (!path) return set_err(KPAL_E_INVALID, "path is NULL");
+    FqMask m;
+    CHK(fq_options(opt, m));
+    const int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return set_err(KPAL_E_IO, "cannot open %s: %s", path, strerror(errno));
+    struct stat st;
+    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) {
+        close(fd);
+        return set_err(KPAL_E_IO, "%s is not a regular file", path);
+    }
+    const uint64_t size = (uint64_t)st.st_size;
+    if (end == 0) end = size;
+    if (begin > end || end > size) {
+        close(fd);
+        return set_err(KPAL_E_INVALID, "byte range %llu..%llu outside %s (%llu bytes)", (unsigned long long)begin, (unsigned long long)end, path,
+                       (unsigned long long)size);
+    }
+    (void)posix_fadvise(fd, (off_t)begin, (off_t)(end - begin), POSIX_FADV_SEQUENTIAL);
+    FaSource src;
+    src.fd = fd;
+    src.pos = begin;
+    src.end = end;
+    const int rc = begin < end ? fastq_feed(ctx, src, m) : KPAL_OK;
+    close(fd);
+    return rc;
+}
+
+KPAL_API int kpal_fastq_flatten(kpal_ctx *ctx, const uint8_t *host_buf, size_t nbytes, const kpal_fastq_options *opt, uint8_t *host_out,
+                                uint64_t *n_out)
+{
+    CTX_ENTER(ctx);
+    if (!n_out || (nbytes && (!host_buf || !host_out))) return set_err(KPAL_E_INVALID, "NULL pointer");
+    *n_out = 0;
+    FqMask m;
+    CHK(fq_options(opt, m));
+    if (nbytes == 0) return KPAL_OK;
+    FaSource src;
+    src.mem = host_buf;
+    src.end = nbytes;
+    const std::vector<uint8_t> none;
+    uint64_t records = 0;
+    return fastq_pipeline(ctx, src, none, true, m, records, false, host_out, n_out, nullptr);
+}
+
 KPAL_API int kpal_count_records(kpal_ctx *ctx, int k, const uint8_t *host_flat, size_t nbytes, const uint64_t *host_starts,
                                 size_t n_records, int64_t *host_out)
 {
@@ -1156,6 +1436,7 @@ KPAL_API int kpal_count_finish(kpal_ctx *ctx, int64_t *host_out)
 {
     CTX_ENTER(ctx);
     if (!ctx->counting) return set_err(KPAL_E_STATE, "kpal_count_finish before kpal_count_begin");
+    if (ctx->fq_open) CHK(fastq_end(ctx));   // the end of a FASTQ text: its last record
     CHK(table_ready(ctx));
     uint32_t pool_error = 0, quad_error = 0;
     if (ctx->chunk_error_armed)

@@ -133,6 +133,16 @@ struct kpal_ctx {
     uint64_t rec_pos = 0, rec_end = 0, rec_piece_at = 0;
     std::vector<uint8_t> rec_carry;
     uint64_t *fa_nflat_host = nullptr;
+    // FASTQ ingest (kpal_count.hip): raw text (carried rest of the chunk before + the chunk) and flattened stream of two chunks,
+    // scan metadata and newline positions of the chunk being tokenised, its status words on the device and in pinned host memory
+    DevBuf fq_raw[2], fq_flat[2], fq_meta, fq_pos, fq_status;
+    unsigned long long *fq_status_host = nullptr;
+    hipEvent_t fq_ev = nullptr;
+    // ... and the record a count's last FASTQ feed left unfinished (kpal_count_finish ends it), with that feed's mask options
+    std::vector<uint8_t> fq_carry;
+    uint64_t fq_records = 0;                 // records of this count finished so far (error messages name record fq_records + r + 1)
+    int fq_min_quality = -1, fq_offset = 33;
+    bool fq_open = false;                    // a FASTQ feed happened since kpal_count_begin: kpal_count_finish ends the text
     std::vector<void *> host_allocs;         // kpal_host_alloc buffers still owned by callers (released with the context at the latest)
     size_t fa_chunk = kStage;                // text bytes per chunk (KPAL_FASTA_CHUNK: tests put the seams everywhere)
     // host-feed staging

@@ -407,6 +407,43 @@ class Profile(object):
         return cls._finish_count(ctx, length, name)
 
     @classmethod
+    def from_fastq(cls, handle, length, name=None, min_quality=None, quality_offset=33):
+        """One profile over all reads of a four-line FASTQ handle (beyond the reference, which reads FASTA only).
+
+        Every read is its own record (k-mers never span two reads); its sequence line is counted verbatim, as one sequence of
+        ``from_sequences``.  With ``min_quality`` (0..93) a base whose Phred quality (quality byte - ``quality_offset``, 33 or
+        64) is below it is masked: it breaks k-mer windows like any byte outside ``ACGT``.  Tokenising, validation and masking
+        run on the device (``kpal_count_feed_fastq``); Python does not look for record boundaries.  A malformed record raises
+        ``ValueError`` naming its 1-based number, and no profile is returned."""
+        length = int(length)
+        if length < 1 or length > _native.KPAL_MAX_K:
+            raise ValueError('k-mer length must be in 1..%d (got %d)' % (_native.KPAL_MAX_K, length))
+        _native.fastq_options_check(min_quality, quality_offset)
+        ctx = _native.context()
+        ctx.count_begin(length)
+        plain = _plain_file(handle)
+        if plain is not None:
+            # an ordinary file: the library reads it itself (parallel preads into pinned memory, as from_fasta)
+            ctx.count_feed_fastq_file(plain[0], plain[1], 0, min_quality, quality_offset)
+            handle.seek(0, os.SEEK_END)
+            return cls._finish_count(ctx, length, name)
+        reader = handle
+        if isinstance(handle, io.TextIOWrapper):
+            try:                              # a pipe or a decompressing wrapper in an ASCII-compatible text encoding: its bytes, undecoded
+                if codecs.lookup(handle.encoding or '').name in ('utf-8', 'ascii', 'iso8859-1') and handle.tell() == 0:
+                    reader = handle.buffer
+            except (LookupError, OSError, ValueError):
+                reader = handle
+        while True:
+            text = reader.read(_FASTA_CHUNK)   # raw pieces cut anywhere: the library carries the unfinished record
+            if not text:
+                break
+            if not isinstance(text, bytes):
+                text = text.encode('latin-1', 'replace')
+            ctx.count_feed_fastq(text, min_quality, quality_offset)
+        return cls._finish_count(ctx, length, name)
+
+    @classmethod
     def from_fasta_by_record(cls, handle, length, prefix=None):
         """One profile per FASTA record, named by record (kpal/klib.py:114-133).
 

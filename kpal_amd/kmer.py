@@ -86,15 +86,24 @@ def cat(input_handles, output_handle, names=None, prefixes=None):
             profile.save(output_handle, name=prefix + name)
 
 
-def count(input_handles, output_handle, size, names=None, by_record=False):
+def count(input_handles, output_handle, size, names=None, by_record=False, fastq=False, min_quality=None, phred64=False):
     """k-mer profiles of FASTA files (kpal/kmer.py:112-146): one profile per file, or per record
-    with ``by_record`` (record names, prefixed by the file's name when several files are given)."""
+    with ``by_record`` (record names, prefixed by the file's name when several files are given).
+    With ``fastq`` the inputs are four-line FASTQ files, one profile per file (beyond the reference); ``min_quality`` masks
+    bases of a lower Phred quality, read with offset 64 instead of 33 under ``phred64``."""
+    if fastq and by_record:
+        raise ValueError('--by-record does not apply to FASTQ input (one profile per read is not supported)')
+    if not fastq and (min_quality is not None or phred64):
+        raise ValueError('--min-quality and --phred64 apply to FASTQ input only (add --fastq)')
     names = names or [_name_from_handle(handle) for handle in input_handles]
     if len(names) != len(input_handles):
         raise ValueError(NAMES_COUNT_ERROR)
     several = len(input_handles) > 1
     for handle, name in zip(input_handles, names):
-        if by_record:
+        if fastq:
+            profiles = [klib.Profile.from_fastq(handle, size, name=name, min_quality=min_quality,
+                                                quality_offset=64 if phred64 else 33)]
+        elif by_record:
             profiles = klib.Profile.from_fasta_by_record(handle, size, prefix=name if several else None)
         else:
             profiles = [klib.Profile.from_fasta(handle, size, name=name)]
@@ -431,6 +440,12 @@ def build_parser():
     sub.add_argument('--by-record', '-r', dest='by_record', action='store_true',
                      help='make a k-mer profile per FASTA record instead of a k-mer profile per FASTA file (profiles are '
                      'named by the record names and prefixed according to --profiles if more than one INPUT is given)')
+    sub.add_argument('--fastq', dest='fastq', action='store_true',
+                     help='the INPUTs are four-line FASTQ files of reads (one k-mer profile per file)')
+    sub.add_argument('--min-quality', dest='min_quality', metavar='Q', type=int, default=None,
+                     help='with --fastq: mask bases whose Phred quality is below Q (0..93; default: no mask)')
+    sub.add_argument('--phred64', dest='phred64', action='store_true',
+                     help='with --fastq: quality bytes are Phred + 64 (default: Phred + 33)')
     sub = command('merge', merge, ['paired_input_profile', 'output_profile'])
     sub.add_argument('-m', dest='merger', type=str, default='sum', choices=metrics.mergers,
                      help='merge function (default: %(default)s)')

@@ -13,7 +13,15 @@ device), then times, each from a page-cached file:
                stand-in of the tests -- h5py is not in this image)
   shards       the file cut for 8 ranks by kpal_amd.dist.fasta_shards, every shard through count_feed_fasta_file on this one GPU
                (cut cost + per-shard rate; the tables add up to the whole-file table: checked)
-Prints one JSON object (bases/s are sequence bases, the file holds 61/60 bytes per base + headers)."""
+Prints one JSON object (bases/s are sequence bases, the file holds 61/60 bytes per base + headers).
+
+    python tools/clibench.py --fastq [--gb 8] [--k 12]
+
+writes a FASTQ of --gb GB of 150-bp reads (SURVEY 8d bases, titles of 30 bytes, random qualities: ~2.23 bytes per base) and the
+same reads as FASTA, and times from page-cached files: pread (8 and 16 threads), feed_file (count_feed_fastq_file + count_finish),
+from_fastq without and with the mask (min_quality 20), cli_count (kmer.main count --fastq) and from_fasta on the FASTA copy;
+Gbases/s and text GB/s each, and fastq_vs_fasta_text = from_fastq text GB/s / from_fasta text GB/s.  Every table is checked
+against the FASTA count of the same reads (the masked one: no larger in total)."""
 import argparse
 import ctypes
 import json
@@ -135,6 +143,111 @@ def by_record_bench(ctx, args):
     return out
 
 
+def write_fastq(ctx, fq_path, fa_path, gb, read_len=150, seed=91):
+    """-> (fastq bytes, fasta bytes, bases, reads): the same reads in both files."""
+    rec = 1 + 29 + 1 + read_len + 3 + read_len + 1
+    n_total = int(gb * 1e9) // rec
+    piece = 1 << 20
+    rng = np.random.default_rng(seed)
+    titles = rng.integers(ord('A'), ord('Z') + 1, size=(piece, 29), dtype=np.uint8)
+    quals = rng.integers(33, 74, size=(piece, read_len), dtype=np.uint8)   # Phred 0..40
+    d = ctx.alloc(piece * (read_len + 1))
+    host = np.empty((piece, read_len + 1), dtype=np.uint8)
+    fq = np.empty((piece, rec), dtype=np.uint8)
+    fq[:, 0] = ord('@')
+    fq[:, 1:30] = titles
+    fq[:, 30] = ord('\n')
+    fq[:, 31 + read_len:34 + read_len] = np.frombuffer(b'\n+\n', dtype=np.uint8)
+    fq[:, -1] = ord('\n')
+    fa = np.empty((piece, 1 + 29 + 1 + read_len + 1), dtype=np.uint8)
+    fa[:, 0] = ord('>')
+    fa[:, 1:30] = titles
+    fa[:, 30] = ord('\n')
+    fa[:, -1] = ord('\n')
+    done = 0
+    with open(fq_path, 'wb') as hq, open(fa_path, 'wb') as ha:
+        while done < n_total:
+            n = min(piece, n_total - done)
+            ctx.synth_reads_device(seed, done, n, read_len, d)
+            ctx.d2h(host[:n].reshape(-1), d)
+            fq[:n, 31:31 + read_len] = host[:n, :read_len]
+            fq[:n, 34 + read_len:34 + 2 * read_len] = np.roll(quals, done % 7, axis=1)[:n]
+            fa[:n, 31:31 + read_len] = host[:n, :read_len]
+            hq.write(fq[:n].data)
+            ha.write(fa[:n].data)
+            done += n
+    ctx.free(d)
+    return os.path.getsize(fq_path), os.path.getsize(fa_path), n_total * read_len, n_total
+
+
+def fastq_bench(ctx, args):
+    from kpal_amd import files, klib, kmer
+    import memh5
+    import tempfile
+    fq_path = os.path.join(args.dir, 'kpal_clibench_%d.fq' % os.getpid())
+    fa_path = fq_path[:-3] + '.fa'
+    out = {'mode': 'fastq', 'k': args.k, 'dir': args.dir, 'read_len': 150, 'read_threads': int(os.environ.get('KPAL_READ_THREADS', '16'))}
+    try:
+        t0 = time.perf_counter()
+        fq_bytes, fa_bytes, bases, reads = write_fastq(ctx, fq_path, fa_path, args.gb)
+        out.update(fastq_bytes=fq_bytes, fasta_bytes=fa_bytes, bases=bases, reads=reads, write_s=time.perf_counter() - t0)
+        out['pread_GBs'] = {str(t): pread_rate(fq_path, t) for t in (8, 16)}
+
+        def best(fn):
+            times = []
+            for _ in range(args.repeat):
+                t = time.perf_counter()
+                r = fn()
+                times.append(time.perf_counter() - t)
+            return min(times), r
+
+        def rates(s, nbytes):
+            return {'s': s, 'Gbases_per_s': bases / s / 1e9, 'text_GBs': nbytes / s / 1e9}
+
+        def from_fasta():
+            with open(fa_path) as fh:
+                return klib.Profile.from_fasta(fh, args.k).counts
+        s, want = best(from_fasta)
+        out['from_fasta'] = rates(s, fa_bytes)
+
+        def feed_file():
+            ctx.count_begin(args.k)
+            ctx.count_feed_fastq_file(fq_path)
+            return ctx.count_finish()
+        s, table = best(feed_file)
+        assert np.array_equal(table, want)
+        out['feed_file'] = rates(s, fq_bytes)
+
+        def from_fastq(mq=None):
+            with open(fq_path) as fh:
+                return klib.Profile.from_fastq(fh, args.k, min_quality=mq).counts
+        s, table = best(from_fastq)
+        assert np.array_equal(table, want)
+        out['from_fastq'] = rates(s, fq_bytes)
+        s, table = best(lambda: from_fastq(20))
+        assert int(table.sum()) < int(want.sum())
+        out['from_fastq_q20'] = rates(s, fq_bytes)
+
+        if not args.no_cli:
+            store = memh5.Store()
+            files.open_profile_file = store.open
+            scratch = tempfile.mkdtemp(prefix='kpal_clibench_')
+
+            def cli():
+                name = os.path.join(scratch, 'out_%d.k%d' % (time.perf_counter_ns(), args.k))
+                kmer.main(['count', '--fastq', '-k', str(args.k), fq_path, name])
+                return name
+            s, name = best(cli)
+            assert np.array_equal(klib.Profile.from_file(store.open(name, 'r')).counts, want)
+            out['cli_count'] = rates(s, fq_bytes)
+        out['fastq_vs_fasta_text'] = out['from_fastq']['text_GBs'] / out['from_fasta']['text_GBs']
+    finally:
+        for p in (fq_path, fa_path):
+            if not args.keep and os.path.exists(p):
+                os.unlink(p)
+    return out
+
+
 def pread_rate(path, threads, limit=4 << 30):
     size = min(os.path.getsize(path), limit)
     buf = np.empty(64 << 20, dtype=np.uint8)
@@ -171,10 +284,15 @@ def main():
     ap.add_argument('--by-record', action='store_true', help='time Profile.from_fasta_by_record on files of many records instead')
     ap.add_argument('--records', type=int, default=0, help='--by-record: one shape only: this many records ...')
     ap.add_argument('--record-bases', type=int, default=10_020, help='... of this many bases each (at --k)')
+    ap.add_argument('--fastq', action='store_true', help='time the FASTQ paths against from_fasta on the same reads instead')
+    ap.add_argument('--no-cli', action='store_true', help='--fastq: leave out the kpal count run')
     args = ap.parse_args()
     from kpal_amd import _native, dist, files, klib, kmer
     import memh5
     ctx = _native.context()
+    if args.fastq:
+        print(json.dumps(fastq_bench(ctx, args)))
+        return
     if args.by_record:
         print(json.dumps({'by_record': by_record_bench(ctx, args), 'host_cores': os.cpu_count()}))
         return
