@@ -1,11 +1,13 @@
-// fasta_host.hpp -- the host side of the FASTA ingest, free of HIP: where the text comes from (a byte range of a file read by
-// the pool's threads, or host memory, optionally preceded by a short prefix) and how it is cut into the chunks the flattening
-// kernels of fasta_kernels.hpp take.  kpal_count.hip drives a FaChunker with its pinned staging buffers and queues the
-// copies and kernels per chunk; tests/native/fasta_host_check.cpp drives the same class with malloc'ed buffers under
-// AddressSanitizer / ThreadSanitizer and compares the chunks, flattened by a restatement of the kernels' rules, with the
-// text flattened in one piece.
+// fasta_host.hpp -- the host side of the text ingest (FASTA, FASTQ and the by-record index), free of HIP: where the text comes
+// from (a byte range of a file read by the pool's threads, or host memory, optionally preceded by a short prefix), how it is read
+// into two staging buffers -- StagedReader reads chunk i + 1 into one while the caller handles chunk i in the other; fa_read
+// reads one range synchronously -- and how FaChunker cuts FASTA text into the chunks the flattening kernels of fasta_kernels.hpp
+// take.  kpal_count.hip drives both with its pinned staging buffers and queues the copies and kernels per chunk;
+// tests/native/fasta_host_check.cpp drives the same classes with malloc'ed buffers under AddressSanitizer / ThreadSanitizer and
+// compares the chunks with the source, and the FASTA chunks, flattened by a restatement of the kernels' rules, with the text
+// flattened in one piece.
 //
-// A chunk may be cut ANYWHERE.  What the kernels cannot see from inside a chunk travels with it:
+// A FASTA chunk may be cut ANYWHERE.  What the kernels cannot see from inside a chunk travels with it:
 //   * state         what the chunk's first byte continues (0 line start, 1 inside a header line, 2 inside a sequence line);
 //   * tail_trailing the chunk ends in a run of blanks: whether those trail their line (str.rstrip() drops them) or stand
 //                   inside it (a tab stays and separates k-mer windows) is decided by the first byte that is not a blank
@@ -104,6 +106,122 @@ static inline void fa_copy_start(const FaSource &s, uint8_t *dst, uint64_t pos, 
     });
 }
 
+// fa_copy_start, now: returns 0 or the first errno of its parts.  A range of one part is copied on the calling thread (a small
+// read gains nothing from a pool round trip).
+static inline int fa_read(const FaSource &s, uint8_t *dst, uint64_t pos, size_t n, size_t split = (size_t)4 << 20)
+{
+    if (n / std::max<size_t>(split, 1) < 2 || HostPool::instance().size() == 1) {
+        if (!s.mem) return pread_all(s.fd, dst, n, pos);
+        memcpy(dst, s.mem + pos, n);
+        return 0;
+    }
+    std::vector<int> ok;
+    fa_copy_start(s, dst, pos, n, ok, split);
+    HostPool::instance().wait();
+    for (int e : ok)
+        if (e) return e;
+    return 0;
+}
+
+struct StagedChunk {
+    uint8_t *data = nullptr;           // buffer `slot`, from its first byte
+    size_t n = 0;
+    int slot = 0;
+};
+
+// The source, prefix first, in chunks of up to `stage` bytes that alternate between two staging buffers: while the caller handles
+// chunk i, the pool reads chunk i + 1 into the other buffer.
+class StagedReader {
+public:
+    // buf[0], buf[1]: staging buffers of `stage` bytes each (pinned memory in the library).  wait_slot(slot) is called before
+    // a buffer is written again: it returns (0) once whatever the caller queued on the buffer's previous contents -- the DMA
+    // out of it -- is done, or an error code that ends the reading.  split: see fa_copy_start (tests make it tiny).
+    StagedReader(FaSource &src, uint8_t *buf0, uint8_t *buf1, size_t stage, std::function<int(int)> wait_slot, size_t split = (size_t)4 << 20)
+        : src_(src), stage_(stage), wait_slot_(std::move(wait_slot)), split_(split)
+    {
+        buf_[0] = buf0;
+        buf_[1] = buf1;
+    }
+    ~StagedReader()
+    {
+        if (ra_active_) HostPool::instance().wait();   // (an error return must not leave the pool writing into a staging buffer)
+    }
+    StagedReader(const StagedReader &) = delete;
+    StagedReader &operator=(const StagedReader &) = delete;
+
+    int io_errno() const { return io_errno_; }       // after next() returned -1
+    int user_error() const { return user_error_; }   // after next() returned -2: what wait_slot returned
+
+    // 1: `out` is the next chunk (valid until the call after the next one: the other buffer is filled first); 0: the end of
+    // the source; -1: a read failed (io_errno()); -2: wait_slot failed (user_error()).  The source stands behind the chunk.
+    int next(StagedChunk &out)
+    {
+        uint8_t *hp = buf_[slot_];
+        size_t n = 0;
+        if (ra_active_) {
+            HostPool::instance().wait();
+            ra_active_ = false;
+            for (int e : ra_ok_)
+                if (e) {
+                    io_errno_ = e;
+                    return -1;
+                }
+            n = ra_n_;                               // (read into buf_[slot_] from src_.pos while the chunk before was handled)
+            src_.pos += ra_n_;
+        } else {
+            if (!src_.more()) return 0;
+            if (int rc = wait_slot_(slot_)) {
+                user_error_ = rc;
+                return -2;
+            }
+            if (src_.prefix_left) {
+                n = std::min(stage_, src_.prefix_left);
+                memcpy(hp, src_.prefix, n);
+                src_.prefix += n;
+                src_.prefix_left -= n;
+            }
+            const size_t more = (size_t)std::min<uint64_t>(stage_ - n, src_.end - src_.pos);
+            if (more) {
+                if (int e = fa_read(src_, hp + n, src_.pos, more, split_)) {
+                    io_errno_ = e;
+                    return -1;
+                }
+                src_.pos += more;
+                n += more;
+            }
+            if (n == 0) return 0;
+        }
+        // the next chunk: the pool reads it while this one is handled
+        if (src_.prefix_left == 0 && src_.pos < src_.end) {
+            const int other = slot_ ^ 1;
+            if (int rc = wait_slot_(other)) {
+                user_error_ = rc;
+                return -2;
+            }
+            ra_n_ = (size_t)std::min<uint64_t>(stage_, src_.end - src_.pos);
+            fa_copy_start(src_, buf_[other], src_.pos, ra_n_, ra_ok_, split_);
+            ra_active_ = true;
+        }
+        out.data = hp;
+        out.n = n;
+        out.slot = slot_;
+        slot_ ^= 1;
+        return 1;
+    }
+
+private:
+    FaSource &src_;
+    uint8_t *buf_[2];
+    size_t stage_;
+    std::function<int(int)> wait_slot_;
+    size_t split_;
+    int slot_ = 0;
+    bool ra_active_ = false;
+    size_t ra_n_ = 0;
+    std::vector<int> ra_ok_;
+    int io_errno_ = 0, user_error_ = 0;
+};
+
 struct FaChunk {
     const uint8_t *data = nullptr;     // inside the staging buffer of `slot`
     size_t n = 0;
@@ -112,68 +230,27 @@ struct FaChunk {
     int slot = 0;
 };
 
+// FASTA chunks on a StagedReader (its buffers, wait_slot and split): text before the first header skipped, every chunk with its
+// line state and tail_trailing.
 class FaChunker {
 public:
-    // buf[0], buf[1]: staging buffers of `stage` bytes each (pinned memory in the library).  wait_slot(slot) is called before
-    // a buffer is written again: it returns (0) once whatever the caller queued on the buffer's previous contents -- the DMA
-    // out of it -- is done, or an error code that ends the chunking.  split: see fa_copy_start (tests make it tiny).
     FaChunker(FaSource &src, uint8_t *buf0, uint8_t *buf1, size_t stage, std::function<int(int)> wait_slot, size_t split = (size_t)4 << 20)
-        : src_(src), stage_(stage), wait_slot_(std::move(wait_slot)), split_(split)
+        : src_(src), reader_(src, buf0, buf1, stage, std::move(wait_slot), split)
     {
-        buf_[0] = buf0;
-        buf_[1] = buf1;
     }
-    ~FaChunker()
-    {
-        if (ra_active_) HostPool::instance().wait();   // (an error return must not leave the pool writing into a staging buffer)
-    }
-    FaChunker(const FaChunker &) = delete;
-    FaChunker &operator=(const FaChunker &) = delete;
 
-    int io_errno() const { return io_errno_; }   // after next() returned -1
-    int user_error() const { return user_error_; }   // after next() returned -2: what wait_slot returned
+    int io_errno() const { return peek_errno_ ? peek_errno_ : reader_.io_errno(); }   // after next() returned -1
+    int user_error() const { return reader_.user_error(); }                          // after next() returned -2
 
-    // 1: `out` is the next chunk (valid until the call after the next one: the other buffer is filled first); 0: the end of
-    // the text; -1: a read failed (io_errno()); -2: wait_slot failed (user_error()).
+    // 1: `out` is the next chunk (valid until the call after the next one); 0: the end of the text; -1: a read failed
+    // (io_errno()); -2: wait_slot failed (user_error()).
     int next(FaChunk &out)
     {
         for (;;) {
-            uint8_t *hp = buf_[slot_];
-            size_t n = 0;
-            if (ra_active_) {
-                HostPool::instance().wait();
-                ra_active_ = false;
-                for (int e : ra_ok_)
-                    if (e) {
-                        io_errno_ = e;
-                        return -1;
-                    }
-                n = ra_n_;                               // (read into buf_[slot_] from src_.pos while the chunk before was handled)
-                src_.pos += ra_n_;
-            } else {
-                if (!src_.more()) return 0;
-                if (int rc = wait_slot_(slot_)) {
-                    user_error_ = rc;
-                    return -2;
-                }
-                const long got = fill(hp, stage_);
-                if (got < 0) return -1;
-                if (got == 0) return 0;
-                n = (size_t)got;
-            }
-            // the next chunk: the pool reads it while this one is scanned, copied and its kernels are issued
-            if (src_.prefix_left == 0 && src_.pos < src_.end) {
-                const int other = slot_ ^ 1;
-                if (int rc = wait_slot_(other)) {
-                    user_error_ = rc;
-                    return -2;
-                }
-                ra_n_ = (size_t)std::min<uint64_t>(stage_, src_.end - src_.pos);
-                fa_copy_start(src_, buf_[other], src_.pos, ra_n_, ra_ok_, split_);
-                ra_active_ = true;
-            }
-            const int slot = slot_;
-            slot_ ^= 1;
+            StagedChunk raw;
+            if (int rc = reader_.next(raw); rc != 1) return rc;
+            const uint8_t *hp = raw.data;
+            const size_t n = raw.n;
             size_t first = 0;
             if (skipping_) {
                 first = fasta_first_header(hp, n, at_line_start_);
@@ -187,7 +264,7 @@ public:
             out.data = hp + first;
             out.n = n - first;
             out.state = state_;
-            out.slot = slot;
+            out.slot = raw.slot;
             out.tail_trailing = true;
             if (fa_host_is_blank(hp[n - 1]) && src_.more()) {
                 const int t = peek_trailing();
@@ -209,33 +286,6 @@ public:
     }
 
 private:
-    // The next bytes of the source (at most `want`) into dst, now; returns how many (0: the end), -1 on a read error.
-    long fill(uint8_t *dst, size_t want)
-    {
-        size_t got = 0;
-        if (src_.prefix_left) {
-            const size_t n = std::min(want, src_.prefix_left);
-            memcpy(dst, src_.prefix, n);
-            src_.prefix += n;
-            src_.prefix_left -= n;
-            got = n;
-        }
-        const size_t n = (size_t)std::min<uint64_t>(want - got, src_.end - src_.pos);
-        if (n) {
-            std::vector<int> ok;
-            fa_copy_start(src_, dst + got, src_.pos, n, ok, split_);
-            HostPool::instance().wait();
-            for (int e : ok)
-                if (e) {
-                    io_errno_ = e;
-                    return -1;
-                }
-            src_.pos += n;
-            got += n;
-        }
-        return (long)got;
-    }
-
     // The first byte of the source, from its current position on, that is not a blank: 1 if it ends a line or the text ends
     // first (the blanks before it trail their line), 0 otherwise; -1 on a read error.  The source is not advanced.
     int peek_trailing()
@@ -249,7 +299,7 @@ private:
             const uint8_t *p = tmp;
             if (src_.mem) p = src_.mem + at;
             else if (int e = pread_all(src_.fd, tmp, n, at)) {
-                io_errno_ = e;
+                peek_errno_ = e;
                 return -1;
             }
             for (size_t i = 0; i < n; ++i)
@@ -260,18 +310,11 @@ private:
     }
 
     FaSource &src_;
-    uint8_t *buf_[2];
-    size_t stage_;
-    std::function<int(int)> wait_slot_;
-    size_t split_;
-    int slot_ = 0;
-    bool ra_active_ = false;
-    size_t ra_n_ = 0;
-    std::vector<int> ra_ok_;
+    StagedReader reader_;
     int state_ = 0;               // what the next chunk's first byte continues
     bool skipping_ = true;        // only text before the first header so far
     bool at_line_start_ = true;
-    int io_errno_ = 0, user_error_ = 0;
+    int peek_errno_ = 0;
 };
 
 }  // namespace kpal

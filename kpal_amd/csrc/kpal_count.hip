@@ -525,21 +525,14 @@ KPAL_API int kpal_count_feed_device(kpal_ctx *ctx, const void *dev_buf, size_t n
     return rc;
 }
 
-// Host copy into a pinned staging buffer on several cores (host_pool.hpp): one core's memcpy (~9 GB/s) is what limits a
+// Host copy into a pinned staging buffer on several cores (fa_read, host_pool.hpp): one core's memcpy (~9 GB/s) is what limits a
 // pageable-memory feed otherwise, the PCIe link takes six times that.  Pieces below 4 MiB are not split.
 static void staged_memcpy(void *dst, const void *src, size_t n)
 {
-    HostPool &pool = HostPool::instance();
-    const int parts = (int)std::min<size_t>((size_t)pool.size(), n / ((size_t)4 << 20));
-    if (parts <= 1) {
-        memcpy(dst, src, n);
-        return;
-    }
-    const size_t part = (((n + (size_t)parts - 1) / (size_t)parts) + 4095) & ~(size_t)4095;
-    pool.run(parts, [=](int i) {
-        const size_t off = (size_t)i * part;
-        if (off < n) memcpy((uint8_t *)dst + off, (const uint8_t *)src + off, std::min(part, n - off));
-    });
+    FaSource s;
+    s.mem = (const uint8_t *)src;
+    s.end = n;
+    (void)fa_read(s, (uint8_t *)dst, 0, n);   // (a memory source cannot fail)
 }
 
 // Page-locked host memory on the NUMA node the GPU is attached to: the calling thread's memory policy is set to "prefer that node"
@@ -579,6 +572,24 @@ static int ensure_pinned(kpal_ctx *ctx)
     return KPAL_OK;
 }
 
+// The reuse protocol of the pinned staging buffers, for every path that writes ctx->pinned[slot]: pinned_wait before the buffer
+// is written (the DMA out of its previous contents has finished), pinned_h2d for the DMA out of it (ev_copied[slot] marks its
+// end; ctx->stream waits for it).
+static int pinned_wait(kpal_ctx *ctx, int slot)
+{
+    if (ctx->stage_used[slot]) HIPCHK(hipEventSynchronize(ctx->ev_copied[slot]));
+    return KPAL_OK;
+}
+
+static int pinned_h2d(kpal_ctx *ctx, int slot, void *dst, const void *src, size_t n)
+{
+    HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, ctx->copy_stream));
+    HIPCHK(hipEventRecord(ctx->ev_copied[slot], ctx->copy_stream));
+    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied[slot], 0));
+    ctx->stage_used[slot] = true;
+    return KPAL_OK;
+}
+
 // pinned_source: host_buf came from kpal_host_alloc -- the DMA engine reads it in place, no staging copy; the call returns
 // when the last copy has left it (the kernels may still run).
 static int count_feed_host(kpal_ctx *ctx, const uint8_t *host_buf, size_t nbytes, bool pinned_source)
@@ -593,10 +604,8 @@ static int count_feed_host(kpal_ctx *ctx, const uint8_t *host_buf, size_t nbytes
         const size_t len = std::min(stage, nbytes - off);
         const size_t h = std::min(km1, off);
         // the pinned/device slot is free once the H2D copy (pinned) and the kernels (device) that used it are done
-        if (ctx->stage_used[slot]) {
-            HIPCHK(hipEventSynchronize(ctx->ev_copied[slot]));
-            HIPCHK(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_done[slot], 0));
-        }
+        CHK(pinned_wait(ctx, slot));
+        if (ctx->stage_used[slot]) HIPCHK(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_done[slot], 0));
         const uint8_t *hp = host_buf + off - h;
         if (!pinned_source) {
             uint8_t *staged = (uint8_t *)ctx->pinned[slot] + (pad - h);
@@ -604,12 +613,9 @@ static int count_feed_host(kpal_ctx *ctx, const uint8_t *host_buf, size_t nbytes
             hp = staged;
         }
         uint8_t *dp = (uint8_t *)ctx->dstage[slot].p + (pad - h);
-        HIPCHK(hipMemcpyAsync(dp, hp, len + h, hipMemcpyHostToDevice, ctx->copy_stream));
-        HIPCHK(hipEventRecord(ctx->ev_copied[slot], ctx->copy_stream));
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied[slot], 0));
+        CHK(pinned_h2d(ctx, slot, dp, hp, len + h));
         CHK(count_device_range(ctx, dp + h, len, h));
         HIPCHK(hipEventRecord(ctx->ev_done[slot], ctx->stream));
-        ctx->stage_used[slot] = true;
     }
     if (pinned_source) HIPCHK(hipStreamSynchronize(ctx->copy_stream));   // the caller may refill its buffer
     return KPAL_OK;
@@ -663,8 +669,32 @@ KPAL_API int kpal_host_free(kpal_ctx *ctx, void *host)
 // FASTA ingest: text (a byte range of a file, or host memory) -> pinned staging -> device -> flattened on the device -> counted,
 // chunk i+1 being read, copied and flattened while chunk i is counted.  Nothing in the loop waits for the GPU except for the
 // flattened SIZE of the chunk before (read back asynchronously, needed on the host to launch its count), which is one whole
-// chunk old by then.
+// chunk old by then.  The text ingests share their host side: open_text_range opens a file's range, the reader of
+// fasta_host.hpp (StagedReader; FaChunker on top of it for FASTA; fa_read for one range) fills the pinned buffers, pinned_wait /
+// pinned_h2d guard their reuse, and fa_flatten is the FASTA flattening of the stream and of the by-record index.
 // ----------------------------------------------------------------------------------------------
+// The flattening of raw[0, m) into flat (fasta_kernels.hpp): `state` says what raw[0] continues, `tail` whether blanks at its end
+// trail their line (FaChunk).  Its scratch in meta: last_eol, eol_before, offs, kept.  Returns offs (offs[nblocks]: the flattened
+// size) and in *rest the first 8-byte aligned byte of meta behind the scratch.
+static int fa_flatten(kpal_ctx *ctx, const uint8_t *raw, uint64_t m, int state, int tail, uint8_t *flat, void *meta, uint64_t **offs_out,
+                      void **rest = nullptr)
+{
+    const uint32_t nblocks = (uint32_t)((m + kFaBlockBytes - 1) / kFaBlockBytes);
+    long long *last_eol = (long long *)meta;
+    long long *eol_before = last_eol + nblocks;
+    uint64_t *offs = (uint64_t *)(eol_before + nblocks);
+    uint32_t *kept = (uint32_t *)(offs + nblocks + 1);
+    LAUNCH(ctx, "fa_last_eol", fa_last_eol_kernel, dim3(nblocks), dim3(kFaThreads), raw, m, last_eol);
+    LAUNCH(ctx, "fa_carry", fa_carry_kernel, dim3(1), dim3(256), (const long long *)last_eol, nblocks, eol_before);
+    LAUNCH(ctx, "fa_count", fa_count_kernel, dim3(nblocks), dim3(kFaThreads), raw, m, (const long long *)eol_before, state, tail, kept);
+    LAUNCH(ctx, "fa_offset", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)kept, nblocks, offs);
+    LAUNCH(ctx, "fa_scatter", fa_scatter_kernel, dim3(nblocks), dim3(kFaThreads), raw, m, (const long long *)eol_before, state, tail,
+           (const uint64_t *)offs, flat);
+    *offs_out = offs;
+    if (rest) *rest = (void *)(((uintptr_t)(kept + nblocks) + 7) & ~(uintptr_t)7);
+    return KPAL_OK;
+}
+
 // The pipeline.  count: the flattened chunks are counted into the running count (windows span chunk seams through the saved
 // tail of the chunk before, never a record boundary: every header leaves a '\n' in the stream); else they are copied to host_out.
 static int fasta_pipeline(kpal_ctx *ctx, FaSource &src, bool count, uint8_t *host_out, uint64_t *n_out)
@@ -707,10 +737,7 @@ static int fasta_pipeline(kpal_ctx *ctx, FaSource &src, bool count, uint8_t *hos
 
     // The chunker (fasta_host.hpp) reads chunk i + 1 into the other pinned buffer while the launches of chunk i are issued; a
     // pinned buffer is written again only after the DMA out of it has finished.
-    FaChunker chunker(src, (uint8_t *)ctx->pinned[0], (uint8_t *)ctx->pinned[1], stage, [ctx](int slot) -> int {
-        if (ctx->stage_used[slot] && hipEventSynchronize(ctx->ev_copied[slot]) != hipSuccess) return KPAL_E_HIP;
-        return 0;
-    });
+    FaChunker chunker(src, (uint8_t *)ctx->pinned[0], (uint8_t *)ctx->pinned[1], stage, [ctx](int slot) { return pinned_wait(ctx, slot); });
     FaChunk ck;
     for (;;) {
         const int got = chunker.next(ck);
@@ -718,31 +745,15 @@ static int fasta_pipeline(kpal_ctx *ctx, FaSource &src, bool count, uint8_t *hos
         if (got == -1) return set_err(KPAL_E_IO, "reading the FASTA input failed: %s", strerror(chunker.io_errno()));
         if (got < 0) return set_err(KPAL_E_HIP, "hipEventSynchronize failed while reading the FASTA input");
         const int slot = ck.slot;
-        const uint8_t *chunk = ck.data;
-        const size_t m = ck.n;
-        const int state = ck.state;
-        const int tail = ck.tail_trailing ? 1 : 0;
-        const uint32_t nblocks = (uint32_t)((m + kFaBlockBytes - 1) / kFaBlockBytes);
+        const uint32_t nblocks = (uint32_t)((ck.n + kFaBlockBytes - 1) / kFaBlockBytes);
         uint8_t *raw = (uint8_t *)ctx->fa_raw[slot].p;
-        uint8_t *flat = (uint8_t *)ctx->fa_flat[slot].p + pad;
-        long long *last_eol = (long long *)ctx->fa_meta[slot].p;
-        long long *eol_before = last_eol + nblocks;
-        uint64_t *offs = (uint64_t *)(eol_before + nblocks);
-        uint32_t *kept = (uint32_t *)(offs + nblocks + 1);
         // the device copy of the raw text is free once the flattening that read it is done (two chunks ago)
         if (ctx->stage_used[slot]) HIPCHK(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_done[slot], 0));
-        HIPCHK(hipMemcpyAsync(raw, chunk, m, hipMemcpyHostToDevice, ctx->copy_stream));
-        HIPCHK(hipEventRecord(ctx->ev_copied[slot], ctx->copy_stream));
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied[slot], 0));
-        LAUNCH(ctx, "fa_last_eol", fa_last_eol_kernel, dim3(nblocks), dim3(kFaThreads), (const uint8_t *)raw, (uint64_t)m, last_eol);
-        LAUNCH(ctx, "fa_carry", fa_carry_kernel, dim3(1), dim3(256), (const long long *)last_eol, nblocks, eol_before);
-        LAUNCH(ctx, "fa_count", fa_count_kernel, dim3(nblocks), dim3(kFaThreads), (const uint8_t *)raw, (uint64_t)m, (const long long *)eol_before, state, tail, kept);
-        LAUNCH(ctx, "fa_offset", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)kept, nblocks, offs);
-        LAUNCH(ctx, "fa_scatter", fa_scatter_kernel, dim3(nblocks), dim3(kFaThreads), (const uint8_t *)raw, (uint64_t)m,
-               (const long long *)eol_before, state, tail, (const uint64_t *)offs, flat);
+        CHK(pinned_h2d(ctx, slot, raw, ck.data, ck.n));
+        uint64_t *offs;
+        CHK(fa_flatten(ctx, raw, ck.n, ck.state, ck.tail_trailing ? 1 : 0, (uint8_t *)ctx->fa_flat[slot].p + pad, ctx->fa_meta[slot].p, &offs));
         HIPCHK(hipMemcpyAsync(&ctx->fa_nflat_host[slot], offs + nblocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipEventRecord(ctx->ev_done[slot], ctx->stream));
-        ctx->stage_used[slot] = true;
         // the chunk before: its flattened size has long arrived; its count is queued behind this chunk's flattening
         if (prev_slot >= 0) CHK(consume(prev_slot));
         prev_slot = slot;
@@ -767,13 +778,10 @@ KPAL_API int kpal_count_feed_fasta(kpal_ctx *ctx, const uint8_t *host_buf, size_
     return fasta_pipeline(ctx, src, true, nullptr, nullptr);
 }
 
-KPAL_API int kpal_count_feed_fasta_file(kpal_ctx *ctx, const char *path, uint64_t begin, uint64_t end, const uint8_t *prefix, size_t prefix_len)
+// [begin, end) of the regular file `path` (end 0: up to its end) as src's range, opened for sequential reading; the caller
+// closes src.fd.
+static int open_text_range(const char *path, uint64_t begin, uint64_t end, FaSource &src)
 {
-    CTX_ENTER(ctx);
-    if (!ctx->counting) return set_err(KPAL_E_STATE, "kpal_count_feed_fasta_file before kpal_count_begin");
-    if (!path) return set_err(KPAL_E_INVALID, "path is NULL");
-    if (prefix_len && !prefix) return set_err(KPAL_E_INVALID, "prefix is NULL");
-    if (prefix_len > ((size_t)1 << 20)) return set_err(KPAL_E_INVALID, "prefix longer than 1 MiB");
     const int fd = open(path, O_RDONLY | O_CLOEXEC);
     if (fd < 0) return set_err(KPAL_E_IO, "cannot open %s: %s", path, strerror(errno));
     struct stat st;
@@ -789,14 +797,25 @@ KPAL_API int kpal_count_feed_fasta_file(kpal_ctx *ctx, const char *path, uint64_
                        (unsigned long long)size);
     }
     (void)posix_fadvise(fd, (off_t)begin, (off_t)(end - begin), POSIX_FADV_SEQUENTIAL);
-    FaSource src;
     src.fd = fd;
     src.pos = begin;
     src.end = end;
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_count_feed_fasta_file(kpal_ctx *ctx, const char *path, uint64_t begin, uint64_t end, const uint8_t *prefix, size_t prefix_len)
+{
+    CTX_ENTER(ctx);
+    if (!ctx->counting) return set_err(KPAL_E_STATE, "kpal_count_feed_fasta_file before kpal_count_begin");
+    if (!path) return set_err(KPAL_E_INVALID, "path is NULL");
+    if (prefix_len && !prefix) return set_err(KPAL_E_INVALID, "prefix is NULL");
+    if (prefix_len > ((size_t)1 << 20)) return set_err(KPAL_E_INVALID, "prefix longer than 1 MiB");
+    FaSource src;
+    CHK(open_text_range(path, begin, end, src));
     src.prefix = prefix;
     src.prefix_left = prefix_len;
     const int rc = fasta_pipeline(ctx, src, true, nullptr, nullptr);
-    close(fd);
+    close(src.fd);
     return rc;
 }
 
@@ -817,8 +836,8 @@ KPAL_API int kpal_fasta_flatten(kpal_ctx *ctx, const uint8_t *host_buf, size_t n
 // that no record finished -> tokenised on the device (fastq_kernels.hpp) -> counted.  Unlike a FASTA chunk, a FASTQ chunk cannot
 // tell from its own bytes where its records begin (a quality line may begin with '@'), so every chunk begins at a record: the
 // status of a chunk (where its unfinished rest begins, its flattened size, its first bad record) is read back once, and the next
-// chunk is tokenised behind that rest.  The count of chunk i is queued behind the tokenising of chunk i + 1, and the pool reads
-// chunk i + 1 while chunk i is copied and tokenised.
+// chunk is tokenised behind that rest.  The count of chunk i is queued behind the tokenising of chunk i + 1, and the reader
+// (StagedReader) reads chunk i + 1 while chunk i is copied and tokenised.
 // ----------------------------------------------------------------------------------------------
 static const char *fq_error_text(unsigned kind)
 {
@@ -858,7 +877,6 @@ static int fastq_pipeline(kpal_ctx *ctx, FaSource &src, const std::vector<uint8_
     }
     if (!ctx->fq_ev) HIPCHK(hipEventCreateWithFlags(&ctx->fq_ev, hipEventDisableTiming));
     CHK(ensure(ctx, ctx->fq_status, kFqStatusWords * sizeof(unsigned long long)));
-    HIPCHK(hipStreamSynchronize(ctx->copy_stream));   // (another path's copy out of a pinned buffer may still be running)
 
     // the carried text: fq_raw[cslot][cstart, cstart + clen)
     int cslot = 1;
@@ -867,17 +885,8 @@ static int fastq_pipeline(kpal_ctx *ctx, FaSource &src, const std::vector<uint8_
         CHK(ensure(ctx, ctx->fq_raw[1], clen + 64));
         HIPCHK(hipMemcpyAsync(ctx->fq_raw[1].p, carry_in.data(), clen, hipMemcpyHostToDevice, ctx->stream));
     }
-    uint8_t *pin[2] = {(uint8_t *)ctx->pinned[0], (uint8_t *)ctx->pinned[1]};
-    bool ra = false;               // the pool is reading the next chunk into pin[slot]
-    size_t ra_n = 0;
-    std::vector<int> ra_ok;
-    struct PoolGuard {
-        bool &active;
-        ~PoolGuard()
-        {
-            if (active) HostPool::instance().wait();   // (an error return must not leave the pool writing into a staging buffer)
-        }
-    } guard{ra};
+    // the reader (fasta_host.hpp) reads chunk i + 1 into the other pinned buffer while chunk i is copied and tokenised
+    StagedReader reader(src, (uint8_t *)ctx->pinned[0], (uint8_t *)ctx->pinned[1], stage, [ctx](int slot) { return pinned_wait(ctx, slot); });
     int pend_slot = -1;            // tokenised, not consumed yet: fq_flat[pend_slot], pend_n bytes
     uint64_t pend_n = 0, out_total = 0;
     auto consume = [&]() -> int {
@@ -891,38 +900,16 @@ static int fastq_pipeline(kpal_ctx *ctx, FaSource &src, const std::vector<uint8_
         pend_slot = -1;
         return KPAL_OK;
     };
-    auto read_failed = [&](const std::vector<int> &ok) -> int {
-        for (int e : ok)
-            if (e) return set_err(KPAL_E_IO, "reading the FASTQ input failed: %s", strerror(e));
-        return KPAL_OK;
-    };
 
-    int slot = 0;
     for (bool first = true;; first = false) {
-        size_t m_bytes = 0;
-        if (ra) {
-            HostPool::instance().wait();
-            ra = false;
-            CHK(read_failed(ra_ok));
-            m_bytes = ra_n;
-            src.pos += ra_n;
-        } else if (src.pos < src.end) {
-            m_bytes = (size_t)std::min<uint64_t>(stage, src.end - src.pos);
-            std::vector<int> ok;
-            fa_copy_start(src, pin[slot], src.pos, m_bytes, ok);
-            HostPool::instance().wait();
-            CHK(read_failed(ok));
-            src.pos += m_bytes;
-        } else if (!(first && clen)) {
-            break;
-        }
-        const bool last = src.pos >= src.end;
-        const bool fin = final_text && last;
-        if (!last) {   // the next chunk into the other pinned buffer (its copy to the device ended before the status below)
-            ra_n = (size_t)std::min<uint64_t>(stage, src.end - src.pos);
-            fa_copy_start(src, pin[slot ^ 1], src.pos, ra_n, ra_ok);
-            ra = true;
-        }
+        StagedChunk ck;   // (none: the carry alone, slot 0)
+        const int got = reader.next(ck);
+        if (got == -1) return set_err(KPAL_E_IO, "reading the FASTQ input failed: %s", strerror(reader.io_errno()));
+        if (got < 0) return set_err(KPAL_E_HIP, "hipEventSynchronize failed while reading the FASTQ input");
+        if (got == 0 && !(first && clen)) break;
+        const int slot = ck.slot;
+        const size_t m_bytes = ck.n;
+        const bool fin = final_text && src.pos >= src.end;
         const uint64_t n = clen + m_bytes;
         if (n >= ((uint64_t)1 << 32) - 64)
             return set_err(KPAL_E_INVALID, "FASTQ record %llu: a record (or a run of empty lines) longer than 4 GiB",
@@ -941,11 +928,7 @@ static int fastq_pipeline(kpal_ctx *ctx, FaSource &src, const std::vector<uint8_
         uint32_t *pos = (uint32_t *)ctx->fq_pos.p;
         unsigned long long *st = (unsigned long long *)ctx->fq_status.p;
         if (clen) HIPCHK(hipMemcpyAsync(raw, (const uint8_t *)ctx->fq_raw[cslot].p + cstart, clen, hipMemcpyDeviceToDevice, ctx->stream));
-        if (m_bytes) {
-            HIPCHK(hipMemcpyAsync(raw + clen, pin[slot], m_bytes, hipMemcpyHostToDevice, ctx->copy_stream));
-            HIPCHK(hipEventRecord(ctx->ev_copied[slot], ctx->copy_stream));
-            HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied[slot], 0));
-        }
+        if (m_bytes) CHK(pinned_h2d(ctx, slot, raw + clen, ck.data, m_bytes));
         HIPCHK(hipMemsetAsync(st, 0xFF, 2 * sizeof(unsigned long long), ctx->stream));
         HIPCHK(hipMemsetAsync(st + 2, 0, (kFqStatusWords - 2) * sizeof(unsigned long long), ctx->stream));
         const unsigned rec_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n / 4 / 256 + 1, (uint64_t)ctx->num_cu * 4));
@@ -974,7 +957,6 @@ static int fastq_pipeline(kpal_ctx *ctx, FaSource &src, const std::vector<uint8_
         clen = n - cstart;
         pend_slot = slot;
         pend_n = hs[4];
-        slot ^= 1;
     }
     if (carry_out) {
         carry_out->resize((size_t)clen);
@@ -1047,27 +1029,10 @@ KPAL_API int kpal_count_feed_fastq_file(kpal_ctx *ctx, const char *path, uint64_
     if (!path) return set_err(KPAL_E_INVALID, "path is NULL");
     FqMask m;
     CHK(fq_options(opt, m));
-    const int fd = open(path, O_RDONLY | O_CLOEXEC);
-    if (fd < 0) return set_err(KPAL_E_IO, "cannot open %s: %s", path, strerror(errno));
-    struct stat st;
-    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) {
-        close(fd);
-        return set_err(KPAL_E_IO, "%s is not a regular file", path);
-    }
-    const uint64_t size = (uint64_t)st.st_size;
-    if (end == 0) end = size;
-    if (begin > end || end > size) {
-        close(fd);
-        return set_err(KPAL_E_INVALID, "byte range %llu..%llu outside %s (%llu bytes)", (unsigned long long)begin, (unsigned long long)end, path,
-                       (unsigned long long)size);
-    }
-    (void)posix_fadvise(fd, (off_t)begin, (off_t)(end - begin), POSIX_FADV_SEQUENTIAL);
     FaSource src;
-    src.fd = fd;
-    src.pos = begin;
-    src.end = end;
-    const int rc = begin < end ? fastq_feed(ctx, src, m) : KPAL_OK;
-    close(fd);
+    CHK(open_text_range(path, begin, end, src));
+    const int rc = src.pos < src.end ? fastq_feed(ctx, src, m) : KPAL_OK;
+    close(src.fd);
     return rc;
 }
 
@@ -1147,39 +1112,25 @@ static int fasta_records_index_text(kpal_ctx *ctx, const uint8_t *host_text, siz
     CHK(ensure(ctx, ctx->rec_meta, (size_t)nblocks * (8 + 8 + 4 + 4) + 2 * (size_t)(nblocks + 1) * 8 + 128));
     uint8_t *raw = (uint8_t *)ctx->rec_raw.p;
     uint8_t *flat = (uint8_t *)ctx->rec_flat.p + pad;
-    long long *last_eol = (long long *)ctx->rec_meta.p;
-    long long *eol_before = last_eol + nblocks;
-    uint64_t *offs = (uint64_t *)(eol_before + nblocks);
-    uint64_t *offs2 = offs + nblocks + 1;
-    uint32_t *kept = (uint32_t *)(offs2 + nblocks + 1);
-    uint32_t *marks = kept + nblocks;
     // text -> device through the pinned staging buffers (host threads copy piece i + 1 while the DMA takes piece i)
     CHK(ensure_pinned(ctx));
     if (in_pinned0) {
-        if (ctx->stage_used[0]) HIPCHK(hipEventSynchronize(ctx->ev_copied[0]));   // (an earlier DMA out of the buffer: long done, the caller has refilled it)
-        HIPCHK(hipMemcpyAsync(raw, text, m, hipMemcpyHostToDevice, ctx->copy_stream));
-        HIPCHK(hipEventRecord(ctx->ev_copied[0], ctx->copy_stream));
-        ctx->stage_used[0] = true;
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied[0], 0));
+        CHK(pinned_wait(ctx, 0));   // (an earlier DMA out of the buffer: long done, the caller has refilled it)
+        CHK(pinned_h2d(ctx, 0, raw, text, m));
     } else {
         const size_t stage = kpal_ctx::kStage;
         int slot = 0;
         for (size_t off = 0; off < m; off += stage, slot ^= 1) {
             const size_t len = std::min(stage, m - off);
-            if (ctx->stage_used[slot]) HIPCHK(hipEventSynchronize(ctx->ev_copied[slot]));
+            CHK(pinned_wait(ctx, slot));
             staged_memcpy(ctx->pinned[slot], text + off, len);
-            HIPCHK(hipMemcpyAsync(raw + off, ctx->pinned[slot], len, hipMemcpyHostToDevice, ctx->copy_stream));
-            HIPCHK(hipEventRecord(ctx->ev_copied[slot], ctx->copy_stream));
-            ctx->stage_used[slot] = true;
-            if (off + stage >= m) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied[slot], 0));
+            CHK(pinned_h2d(ctx, slot, raw + off, ctx->pinned[slot], len));
         }
     }
-    LAUNCH(ctx, "fa_last_eol", fa_last_eol_kernel, dim3(nblocks), dim3(kFaThreads), (const uint8_t *)raw, (uint64_t)m, last_eol);
-    LAUNCH(ctx, "fa_carry", fa_carry_kernel, dim3(1), dim3(256), (const long long *)last_eol, nblocks, eol_before);
-    LAUNCH(ctx, "fa_count", fa_count_kernel, dim3(nblocks), dim3(kFaThreads), (const uint8_t *)raw, (uint64_t)m, (const long long *)eol_before, 0, 1, kept);
-    LAUNCH(ctx, "fa_offset", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)kept, nblocks, offs);
-    LAUNCH(ctx, "fa_scatter", fa_scatter_kernel, dim3(nblocks), dim3(kFaThreads), (const uint8_t *)raw, (uint64_t)m, (const long long *)eol_before, 0, 1,
-           (const uint64_t *)offs, flat);
+    // the flattening; behind its scratch the header lines' offsets (offs2) and the marks of both compactions
+    uint64_t *offs, *offs2;
+    CHK(fa_flatten(ctx, raw, m, 0, 1, flat, ctx->rec_meta.p, &offs, (void **)&offs2));
+    uint32_t *marks = (uint32_t *)(offs2 + nblocks + 1);
     // header lines of the text
     LAUNCH(ctx, "fa_mark_count", (fa_mark_count_kernel<1>), dim3(nblocks), dim3(kFaThreads), (const uint8_t *)raw, (uint64_t)m, marks);
     LAUNCH(ctx, "fa_offset", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)marks, nblocks, offs2);
@@ -1224,7 +1175,7 @@ KPAL_API int kpal_fasta_records_begin(kpal_ctx *ctx, const uint8_t *host_text, s
     return fasta_records_index_text(ctx, host_text, nbytes, false, n_records, flat_bytes);
 }
 
-// ---- the same over a FILE the library reads itself (the pool's threads pread into the pinned staging buffer: no byte of the text
+// ---- the same over a FILE the library reads itself (fa_read: the pool's threads pread into the pinned staging buffer; no byte of the text
 // passes through Python): every kpal_fasta_records_file_next indexes the next piece of WHOLE records -- up to the end of line
 // before the last header line of what fits the 64 MiB staging buffer; the unfinished record behind it is carried to the next
 // piece; a record longer than the buffer is gathered in pageable memory first.
@@ -1242,24 +1193,11 @@ KPAL_API int kpal_fasta_records_file_open(kpal_ctx *ctx, const char *path, uint6
     CTX_ENTER(ctx);
     if (!path) return set_err(KPAL_E_INVALID, "path is NULL");
     fasta_records_file_reset(ctx);
-    const int fd = open(path, O_RDONLY | O_CLOEXEC);
-    if (fd < 0) return set_err(KPAL_E_IO, "cannot open %s: %s", path, strerror(errno));
-    struct stat st;
-    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) {
-        close(fd);
-        return set_err(KPAL_E_IO, "%s is not a regular file", path);
-    }
-    const uint64_t size = (uint64_t)st.st_size;
-    if (end == 0) end = size;
-    if (begin > end || end > size) {
-        close(fd);
-        return set_err(KPAL_E_INVALID, "byte range %llu..%llu outside %s (%llu bytes)", (unsigned long long)begin, (unsigned long long)end, path,
-                       (unsigned long long)size);
-    }
-    (void)posix_fadvise(fd, (off_t)begin, (off_t)(end - begin), POSIX_FADV_SEQUENTIAL);
-    ctx->rec_fd = fd;
-    ctx->rec_pos = ctx->rec_piece_at = begin;
-    ctx->rec_end = end;
+    FaSource src;
+    CHK(open_text_range(path, begin, end, src));
+    ctx->rec_fd = src.fd;
+    ctx->rec_pos = ctx->rec_piece_at = src.pos;
+    ctx->rec_end = src.end;
     return KPAL_OK;
 }
 
@@ -1298,36 +1236,21 @@ KPAL_API int kpal_fasta_records_file_next(kpal_ctx *ctx, uint64_t *n_records, ui
         }
         const size_t c = ctx->rec_carry.size();
         const bool fits = c < stage;
+        const size_t want = (size_t)std::min<uint64_t>(fits ? stage - c : stage, ctx->rec_end - ctx->rec_pos);
         uint8_t *buf;
-        size_t n;
         if (fits) {   // the carried tail + the next bytes of the file into the pinned buffer
-            if (ctx->stage_used[0]) HIPCHK(hipEventSynchronize(ctx->ev_copied[0]));
+            CHK(pinned_wait(ctx, 0));
             buf = (uint8_t *)ctx->pinned[0];
             if (c) memcpy(buf, ctx->rec_carry.data(), c);
-            const size_t want = (size_t)std::min<uint64_t>(stage - c, ctx->rec_end - ctx->rec_pos);
-            if (want) {
-                std::vector<int> ok;
-                fa_copy_start(src, buf + c, ctx->rec_pos, want, ok);
-                HostPool::instance().wait();
-                for (int e : ok)
-                    if (e) return set_err(KPAL_E_IO, "reading the FASTA input failed: %s", strerror(e));
-                ctx->rec_pos += want;
-            }
-            n = c + want;
         } else {      // a record longer than the staging buffer: gathered in pageable memory, 64 MiB at a time
-            const size_t want = (size_t)std::min<uint64_t>(stage, ctx->rec_end - ctx->rec_pos);
             ctx->rec_carry.resize(c + want);
-            if (want) {
-                std::vector<int> ok;
-                fa_copy_start(src, ctx->rec_carry.data() + c, ctx->rec_pos, want, ok);
-                HostPool::instance().wait();
-                for (int e : ok)
-                    if (e) return set_err(KPAL_E_IO, "reading the FASTA input failed: %s", strerror(e));
-                ctx->rec_pos += want;
-            }
             buf = ctx->rec_carry.data();
-            n = c + want;
         }
+        if (want) {
+            if (int e = fa_read(src, buf + c, ctx->rec_pos, want)) return set_err(KPAL_E_IO, "reading the FASTA input failed: %s", strerror(e));
+            ctx->rec_pos += want;
+        }
+        const size_t n = c + want;
         const bool at_end = ctx->rec_pos >= ctx->rec_end;
         // whole records: up to the end of line before the last header line (searched in the new bytes only; a boundary is two bytes)
         const size_t cut = at_end ? n : fasta_last_boundary(buf, n, c ? c - 1 : 0);

@@ -1,11 +1,15 @@
-// fasta_host_check.cpp -- AddressSanitizer / ThreadSanitizer harness of kpal_amd/csrc/fasta_host.hpp: the host side of the FASTA
-// ingest (source = memory or a byte range of a file read with pread by the pool's threads, optional prefix; read-ahead into the
-// other staging buffer; text before the first header skipped; line state and the look-ahead behind a run of blanks carried with
-// every chunk).  The chunks are flattened by a sequential restatement of the rules of fasta_kernels.hpp (which the GPU tests
-// check against the tokeniser of tests/test_gpu_fasta.py) and their concatenation must equal the text flattened in ONE piece --
-// for chunk sizes from 16 bytes (a seam at every position, runs of blanks many chunks long) to the whole text, staging buffers
-// of exactly the chunk size (a byte written past one is an ASan finding), and a pool whose jobs really split (KPAL_READ_THREADS
-// from the test, split = 1 KiB).  Test infrastructure; run by tests/test_native_sanitized.py.
+// fasta_host_check.cpp -- AddressSanitizer / ThreadSanitizer harness of kpal_amd/csrc/fasta_host.hpp, the host side of the text
+// ingest.  StagedReader, driven the way the FASTQ ingest drives it (memory and file sources): the chunks, concatenated, are the
+// source; every chunk is non-empty, at most `stage` bytes and inside its own buffer; the slots alternate; wait_slot(s) runs before
+// buffer s is written again (the buffer still holds the chunk it last handed out); a range past the end of the file is a read
+// error.  fa_read, the synchronous read of one range (one part on the calling thread, many on the pool), and its read error.
+// FaChunker, the FASTA ingest (source = memory or a byte range of a file read with pread by the pool's threads, optional prefix;
+// read-ahead into the other staging buffer; text before the first header skipped; line state and the look-ahead behind a run of
+// blanks carried with every chunk): the chunks are flattened by a sequential restatement of the rules of fasta_kernels.hpp (which
+// the GPU tests check against the tokeniser of tests/test_gpu_fasta.py) and their concatenation must equal the text flattened in
+// ONE piece.  Both for chunk sizes from 16 bytes (a seam at every position, runs of blanks many chunks long) to the whole text,
+// staging buffers of exactly the chunk size (a byte written past one is an ASan finding), and a pool whose jobs really split
+// (KPAL_READ_THREADS from the test, split = 1 KiB).  Test infrastructure; run by tests/test_native_sanitized.py.
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -122,6 +126,34 @@ static std::string chunked(FaSource src, size_t stage, size_t *nchunks)
     return out;
 }
 
+static std::string staged(FaSource src, size_t stage)
+{
+    uint8_t *b[2] = {(uint8_t *)malloc(stage), (uint8_t *)malloc(stage)};   // exactly `stage` bytes each
+    std::string out;
+    std::string held[2];     // what buffer s last handed out: it must be intact when wait_slot(s) is called
+    bool waited[2] = {false, false};
+    {
+        StagedReader rd(src, b[0], b[1], stage, [&](int s) {
+            if (s < 0 || s > 1 || held[s].compare(0, std::string::npos, (const char *)b[s], held[s].size()) != 0) ++failures;
+            waited[s & 1] = true;
+            return 0;
+        }, 1024);
+        StagedChunk c;
+        int rc, expect = 0;
+        while ((rc = rd.next(c)) == 1) {
+            if (c.slot != expect || c.n == 0 || c.n > stage || c.data != b[c.slot] || !waited[c.slot]) ++failures;
+            expect = c.slot ^ 1;
+            waited[c.slot] = false;
+            held[c.slot].assign((const char *)c.data, c.n);
+            out += held[c.slot];
+        }
+        if (rc != 0) ++failures;
+    }
+    free(b[0]);
+    free(b[1]);
+    return out;
+}
+
 int main()
 {
     char path[] = "/tmp/kpal_fasta_host_check_XXXXXX";
@@ -177,7 +209,26 @@ int main()
                     ++failures;
                 }
             }
-            cases += 3;
+            // the plain reader over the same sources
+            if (staged(mem, stage) != text || staged(file, stage) != text) {
+                std::printf("MISMATCH staged reader, round %d, stage %zu\n", round, stage);
+                ++failures;
+            }
+            cases += 5;
+        }
+        // fa_read: ranges of one part (the calling thread) and of many (the pool), from memory and from the file
+        for (int r = 0; r < 8; ++r) {
+            const size_t pos = (size_t)(rnd() % text.size()), n = (size_t)(rnd() % (text.size() - pos + 1));
+            const size_t split = r & 1 ? 64 : ((size_t)4 << 20);
+            std::string got(n, '\0');
+            FaSource mem, file;
+            mem.mem = (const uint8_t *)text.data();
+            mem.end = file.end = text.size();
+            file.fd = fd;
+            if (fa_read(mem, (uint8_t *)&got[0], pos, n, split) != 0 || got.compare(0, n, text, pos, n) != 0) ++failures;
+            got.assign(n, '\0');
+            if (fa_read(file, (uint8_t *)&got[0], pos, n, split) != 0 || got.compare(0, n, text, pos, n) != 0) ++failures;
+            cases += 2;
         }
     }
     // a read error surfaces as -1 with the errno: a range beyond the end of the file
@@ -195,6 +246,17 @@ int main()
             }
             if (rc != -1 || ck.io_errno() == 0) ++failures;
         }
+        {
+            StagedReader rd(bad, b0, b1, 4096, [](int) { return 0; }, 1024);
+            StagedChunk c;
+            int rc;
+            while ((rc = rd.next(c)) == 1) {
+            }
+            if (rc != -1 || rd.io_errno() == 0) ++failures;
+        }
+        const size_t size = (size_t)lseek(fd, 0, SEEK_END);
+        for (size_t split : {(size_t)1024, (size_t)4 << 20})
+            if (fa_read(bad, b0, size - 100, 4096, split) == 0) ++failures;
         free(b0);
         free(b1);
     }
