@@ -685,6 +685,10 @@ class Context(object):
         _check(self._L.kpal_merge(self._h, l.size, l.ctypes.data, r.ctypes.data, int(merger), out.ctypes.data))
         return out
 
+    def merge_device(self, n, dev_left, dev_right, merger, dev_out):
+        """kpal_merge on n int64 entries already on the device; dev_out may be dev_left or dev_right."""
+        _check(self._L.kpal_merge_device(self._h, int(n), _vp(dev_left), _vp(dev_right), int(merger), _vp(dev_out)))
+
     def shrink(self, counts, k, factor):
         """Sums of 4**factor consecutive counts (klib.py:329-352) -> new array of 4**(k-factor)."""
         c = _as_i64(counts)
@@ -695,6 +699,10 @@ class Context(object):
         out = np.empty(4 ** (k - factor), dtype=np.int64)
         _check(self._L.kpal_shrink(self._h, int(k), int(factor), c.ctypes.data, out.ctypes.data))
         return out
+
+    def shrink_device(self, k, factor, dev_in, dev_out):
+        """kpal_shrink from 4**k int64 entries at dev_in into 4**(k-factor) at dev_out, both on the device."""
+        _check(self._L.kpal_shrink_device(self._h, int(k), int(factor), _vp(dev_in), _vp(dev_out)))
 
     def profile_distance_matrix(self, profiles, k, options):
         arrs = [_as_i64(p) for p in profiles]

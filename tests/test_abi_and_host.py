@@ -862,3 +862,81 @@ def test_the_gatherer_against_its_contract(built):
                 break
             pos = nxt + 1 if (status == 2 or nxt == pos) else nxt
     assert calls > 500
+
+
+@pytest.mark.parametrize('k', [5, 6, 7, 8, 9, 10])
+def test_large_k_restatements_equal_the_dense_oracle(k):
+    """The support restatements of tests/large_k_cases.py, which stand in for the dense oracle at k = 15 and 16 in
+    tests/test_gpu_large_k.py, against the dense oracle on the same structured sparse tables at k = 5 to 10: integers exactly,
+    distances within 1e-10 relative."""
+    import large_k_cases as lk
+    import oracle
+    n = 4 ** k
+    li, lv, ri, rv = lk.sparse_pair(k, 100 + k, n_random=min(n // 6, 20000))
+    L, R = lk.dense(li, lv, n), lk.dense(ri, rv, n)
+    assert li.size < n and (lv != 0).all() and (rv != 0).all()
+    sample = np.unique(np.concatenate([li[:500], li[-500:]]))
+    assert [oracle.reverse_complement(int(i), k) for i in sample] == lk.rc_index(sample, k).tolist()
+    # the structure is there: palindromes, i / rc(i) pairs, both table ends, every tile bit on either side
+    rc = lk.rc_index(li, k)
+    assert (li[0], li[-1]) == (0, n - 1)
+    assert np.isin(rc, li).sum() >= min(1000, li.size // 2)
+    if k % 2 == 0:
+        assert (rc == li).sum() >= 10
+    if k >= 7:
+        tiles = np.unique(lk.tile_of(li, k))
+        for bit in range(2 * (k - 6)):
+            assert ((tiles >> bit) & 1).min() == 0 and ((tiles >> bit) & 1).max() == 1
+    # balance
+    bi, bv = lk.balance(li, lv, k)
+    np.testing.assert_array_equal(lk.dense(bi, bv, n), oracle.balance(L, k))
+    # smoothing, every summary
+    u, ul, ur = lk.union(li, lv, ri, rv)
+    for summary, th in (('min', 0), ('average', 1), ('median', 2.5), ('min', 2.5)):
+        si, sl, sr = lk.smooth(u, ul, ur, k, summary, th)
+        ol, orr = oracle.dynamic_smooth(L, R, k, summary, th)
+        np.testing.assert_array_equal(lk.dense(si, sl, n), ol, err_msg=summary)
+        np.testing.assert_array_equal(lk.dense(si, sr, n), orr, err_msg=summary)
+    # the option grid, on these tables and on tables without negatives or values beyond 2^24 (finite distances)
+    narrow = lk.sparse_pair(k, 200 + k, n_random=min(n // 6, 20000), wide=False)
+    for ti, tv, si, sv in ((li, lv, ri, rv), narrow):
+        TL, TR = lk.dense(ti, tv, n), lk.dense(si, sv, n)
+        for o in lk.OPTION_GRID:
+            got = lk.profile_distance(ti, tv, si, sv, k, **o)
+            want = oracle.profile_distance(TL, TR, k, **lk.oracle_options(o))
+            assert lk.close(got, want, 1e-10), (k, o, got, want)
+            assert ti is li or np.isfinite(want), (k, o, want)
+    # merge, shrink, stats
+    for merger in lk.MERGERS:
+        np.testing.assert_array_equal(lk.dense(u, lk.merge(ul, ur, merger), n), oracle.merge(L, R, merger), err_msg=merger)
+    for factor in sorted({1, 2, 3, 4, k - 1} & set(range(1, k))):
+        si, sv = lk.shrink(li, lv, factor)
+        np.testing.assert_array_equal(lk.dense(si, sv, 4 ** (k - factor)), oracle.shrink(L, k, factor), err_msg=str(factor))
+    for idx, val in ((li, lv), (ri, np.abs(rv) % 7 + 1), (li[:3], lv[:3])):
+        got, _ = lk.stats(idx, val, n)
+        want = oracle.stats(lk.dense(idx, val, n))
+        for key in ('total', 'non_zero', 'min', 'max', 'median'):
+            assert got[key] == want[key], (key, got[key], want[key])
+        for key in ('mean', 'std'):
+            assert abs(got[key] - want[key]) <= 1e-10 * abs(want[key]) + 1e-300, (key, got[key], want[key])
+
+
+def test_large_k_dense_table_tallies():
+    """DenseTable's exact value counts against the table it hands out chunk by chunk, and the summaries from them against
+    oracle.stats of the whole table (k = 6 and 8, in chunks of 4^3 and 4^4)."""
+    import large_k_cases as lk
+    import oracle
+    for k, bits in ((6, 6), (8, 8)):
+        t = lk.DenseTable(k, 5 + k, chunk_bits=bits)
+        full = np.concatenate([t.get(c) for c in range(t.chunks)])
+        assert full.size == 4 ** k
+        vals, cnt = np.unique(full, return_counts=True)
+        assert t.counts() == {v: c for v, c in zip(vals.tolist(), cnt.tolist())}
+        assert np.isin(lk.DenseTable.EXTREMES, full).sum() >= 3
+        got, _ = lk.stats_from_counts(t.counts(), t.n)
+        want = oracle.stats(full)
+        assert got['median'] != 0
+        for key in ('total', 'non_zero', 'min', 'max', 'median'):
+            assert got[key] == want[key], (k, key)
+        for key in ('mean', 'std'):
+            assert abs(got[key] - want[key]) <= 1e-10 * abs(want[key]), (k, key)
