@@ -7,16 +7,19 @@ count tables to rank 0 -- ncclReduce(int64, sum) issued by libkpal_hip.so on its
 table (Profile.balance).  Inputs are generated on the device before the timed region (HBM-resident); weak scaling:
 every rank holds --reads reads.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--k 12]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--k 12] [--full]
 
 --gpus N > 1 started as a plain command spawns the N ranks itself (python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>) BEFORE anything touches the GPU, relays rank
 0's JSON line and exits with the ranks' status; started under torch.distributed.run (RANK / WORLD_SIZE set) it is a rank.
 
-The default one-GPU run appends to its JSON line, after the headline measurement, `extra`: BASELINE config 4 (k = 15,
+A plain run does what the headline needs and nothing more: set up, warm up, time the steps, check the result, write
+--dump-outputs, print the line.  --full adds everything else the benchmark measures, after the headline: the CPU baseline
+(`cpu_baseline`; --no-cpu leaves it out), and at N = 1 `extra` (--no-extra leaves it out): BASELINE config 4 (k = 15,
 same 100 M reads), config 5 (64-profile distance matrix at k = 12, multiset prod and euclidean), each with its own
 ms_per_step / roofline / parity flag, and `end_to_end` (host-resident input: H2D, kernels, D2H of the table) for
-config 2.  --no-extra skips them; --workload matrix runs config 5 alone as the headline.
+config 2.  At N > 1 a plain run stops after the first reduce mode whose merged table is right (the headline); --full
+measures every mode.  --workload matrix runs config 5 alone as the headline; --full adds its comparison with the oracle.
 
 --dump-outputs DIR (one GPU) writes what the last timed step computed -- `counts` (the balanced 4^k table) or, for --workload
 matrix, `distances` (the lower triangle, pair (i, j < i) at i * (i - 1) / 2 + j) -- as DIR/<name>.npy in float64, so that two
@@ -344,8 +347,9 @@ def matrix_workload(args):
     """BASELINE config 5 on one GPU as the headline: value = Gterms/s of the 64 x 64 lower triangle (2016 pairs x 4^12 bins)."""
     from kpal_amd import _native
     ctx = _native.Context(0)
-    dprof, host = matrix_profiles(ctx, args.k, args.profiles, args.profile_reads, keep_host=0 if args.no_cpu else 8)
-    r = matrix_measure(ctx, args.k, args.profiles, dprof, host, args.metric, args.balance, args.steps, args.warmup, check=not args.no_cpu)
+    check = args.full and not args.no_cpu
+    dprof, host = matrix_profiles(ctx, args.k, args.profiles, args.profile_reads, keep_host=8 if check else 0)
+    r = matrix_measure(ctx, args.k, args.profiles, dprof, host, args.metric, args.balance, args.steps, args.warmup, check=check)
     if args.dump_outputs is not None:
         dump_outputs(args.dump_outputs, {'distances': r['values']})
     line = {
@@ -883,7 +887,8 @@ def multi_gpu_worker(args):
     warm-up and EXACTLY --steps timed steps between barriers, max over the ranks: the in-library RCCL reduce pipelined with
     the next count (the design default), the same serially, and torch.distributed's reduce serially.  After each mode rank 0
     compares the merged + balanced table of its last step BIN FOR BIN with the single-stream count of all shards (recounted
-    on rank 0 into one table).  The headline is the first mode, in that order, whose table is right; the others are `extra`."""
+    on rank 0 into one table).  The headline is the first mode, in that order, whose table is right; a plain run stops there,
+    --full measures the others as well, as `extra`."""
     import numpy as np
     import torch
     import torch.distributed as td
@@ -1123,7 +1128,7 @@ def multi_gpu_worker(args):
     for mode in modes:
         r = measure(mode)
         if rank == 0:
-            if cpu[0] is None and not args.no_cpu:
+            if cpu[0] is None and args.full and not args.no_cpu:
                 # the same bounded CPU sample as at N = 1, on rank 0's host cores, outside every timed region (the other ranks wait in
                 # the next mode's first collective, or in the final fence)
                 try:
@@ -1138,6 +1143,12 @@ def multi_gpu_worker(args):
                 headline = mode
             if headline is not None and args.worker:
                 set_flag(args.attempt, 'line', text=json.dumps(make_line(headline, results)))
+        if not args.full:
+            # a plain run ends with the headline: every rank learns from rank 0 whether it has one
+            found = torch.tensor([1 if headline is not None else 0], dtype=torch.int32, device='cuda')
+            td.all_reduce(found, op=td.ReduceOp.MAX)
+            if int(found.item()):
+                break
     ok = True
     if rank == 0:
         ok = headline is not None
@@ -1190,8 +1201,11 @@ def main():
     ap.add_argument('--strategy', default='auto')
     ap.add_argument('--cpu-reads', type=int, default=4_000_000, help='reads in the CPU-baseline sample')
     ap.add_argument('--cpu-big-reads', type=int, default=40_000_000, help='reads in the sample of the private-table all-cores plan (N = 1; taken from the device buffer)')
-    ap.add_argument('--no-cpu', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='N=1: skip BASELINE configs 4 / 5 and the end-to-end figures after the headline')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, measure everything else too: the CPU baseline, at N=1 BASELINE configs 4 / 5 and the end-to-end '
+                         'figures, at N>1 every reduce mode, for --workload matrix the comparison with the oracle (default: the headline only)')
+    ap.add_argument('--no-cpu', action='store_true', help='--full: skip the CPU baseline and the comparison with the oracle')
+    ap.add_argument('--no-extra', action='store_true', help='--full, N=1: skip BASELINE configs 4 / 5 and the end-to-end figures after the headline')
     ap.add_argument('--strong', action='store_true',
                     help='strong scaling: --reads is the TOTAL, split over the GPUs (default: weak, --reads per GPU)')
     ap.add_argument('--reduce-via', default='library', choices=['library', 'torch'],
@@ -1267,7 +1281,7 @@ def main():
         'checksum_ok': r['checksum_ok'], 'rccl_ranks': 1, 'src_sha': source_sha(), 'roofline': r['roofline'],
     }
     ok = r['checksum_ok']
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         # the private-table plan of the all-cores figure gets a sample that amortises its fixed cost: the first 40 M reads of the
         # device buffer (what the host's memory allows: the sample + 64..128 tables of 4^k entries)
         big = None
@@ -1277,7 +1291,7 @@ def main():
             ctx.d2h(big, dev_buf)
         line['cpu_baseline'] = cpu_baseline(k, L, args.cpu_reads, big=big)
         del big
-    if not args.no_extra and k == 12 and args.strategy == 'auto':
+    if args.full and not args.no_extra and k == 12 and args.strategy == 'auto':
         line['extra'] = ex = run_extras(ctx, args, dev_buf, nbytes, r['ms_per_step'])
         # the other BASELINE configs and the host-resident figures as SCALARS of `config` (the driver's record keeps scalars only)
         for key, src, field in (('config4_k15_ms_per_step', 'k15', 'ms_per_step'), ('config4_k15_Gbases_per_s', 'k15', 'value'),

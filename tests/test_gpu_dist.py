@@ -21,11 +21,11 @@ def test_rccl_collectives_on_table_view():
 
 
 def test_bench_single_gpu_small(tmp_path):
-    """bench.py contract on a small workload: one JSON line with roofline and a true checksum; --dump-outputs writes the sampled
+    """bench.py --full contract on a small workload: one JSON line with roofline and a true checksum; --dump-outputs writes the sampled
     balanced table of the last timed step, whose block sums add up to the checksum."""
     import json
     import numpy as np
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1',
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--full',
                         '--reads', '2000000', '--cpu-reads', '200000', '--cpu-big-reads', '1000000', '--profile-reads', '100000',
                         '--dump-outputs', str(tmp_path / 'out')], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
@@ -41,7 +41,7 @@ def test_bench_single_gpu_small(tmp_path):
     assert set(('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic')) <= set(line['roofline'])
     assert line['cpu_baseline']['kind'] == 'port' and line['cpu_baseline']['cores'] == 1
     assert line['rccl_ranks'] == 1 and line['roofline']['pipeline']['frac'] > 0
-    # the extras of the default run: BASELINE configs 4 and 5 and the end-to-end figure, each with its own parity flag
+    # the extras of a --full run: BASELINE configs 4 and 5 and the end-to-end figure, each with its own parity flag
     ex = line['extra']
     for name in ('end_to_end', 'k15', 'matrix_prod', 'matrix_euclidean'):
         assert 'error' not in ex[name], (name, ex[name])
@@ -52,6 +52,29 @@ def test_bench_single_gpu_small(tmp_path):
     # skew is a first-class figure of the line: uniform / 2 % low-complexity / homopolymer input at k = 12 and k = 15, as scalars of `config`
     for name in ('k12_uniform', 'k12_low_complexity_2pct', 'k12_homopolymer', 'k15_uniform', 'k15_low_complexity_2pct', 'k15_homopolymer'):
         assert ex['skew'][name]['Gbases_per_s'] > 0 and line['config']['skew_%s_Gbases_per_s' % name] == ex['skew'][name]['Gbases_per_s']
+
+
+def test_bench_single_gpu_plain_run(tmp_path):
+    """A plain bench.py run (no --full) does what its headline needs and no more: the headline fields, the roofline, a true checksum
+    and --dump-outputs, but neither the CPU baseline nor the extras."""
+    import json
+    import numpy as np
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--reads', '2000000',
+                        '--dump-outputs', str(tmp_path / 'out')], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    dumped = {f[:-4]: np.load(str(tmp_path / 'out' / f)) for f in os.listdir(str(tmp_path / 'out'))}
+    assert sorted(dumped) == ['counts_block_sums', 'counts_sample', 'counts_sample_index']
+    assert dumped['counts_block_sums'].sum() == 2 * 2000000 * (150 - 12 + 1)
+    lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+                'vs_baseline', 'dtype', 'data', 'config', 'roofline'):
+        assert key in line
+    assert line['metric'] == 'Gbases/s k-mer counted (k=12, 150bp synthetic)' and line['unit'] == 'Gbases/s' and line['dtype'] == 'int64'
+    assert line['higher_is_better'] is True and line['steps'] == 2 and line['warmup'] == 1 and line['ms_per_step'] > 0 and line['value'] > 0
+    assert line['checksum_ok'] is True and line['config']['checksum_ok'] is True and line['roofline']['pipeline']['frac'] > 0
+    assert 'cpu_baseline' not in line and 'extra' not in line and 'extras_ok' not in line['config']
 
 
 def test_library_rccl_world_1():
@@ -71,12 +94,13 @@ def test_bench_multi_gpu_code_path_on_one_gpu():
     """The N > 1 code of bench.py -- rank supervisor, worker process, the library's RCCL communicator and torch.distributed's,
     the three reduce modes (pipelined / serial in-library reduce, torch reduce) each timed with its own warm-up and steps, the
     per-bin comparison of the merged + balanced table with the single-stream count, the line's fields -- started exactly as
-    the driver starts the scaling runs (python -m torch.distributed.run ... bench.py --gpus N ...), with a world of ONE rank
+    the driver starts the scaling runs (python -m torch.distributed.run ... bench.py --gpus N ...) with --full, with a world of ONE rank
     (KPAL_BENCH_FORCE_MULTI=1: this box has one GPU; the 8-GPU run is the driver's)."""
     import json
     env = dict(os.environ, KPAL_BENCH_FORCE_MULTI='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     p = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
-                        '--master-port', '29633', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--reads', '3000000'],
+                        '--master-port', '29633', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--reads', '3000000',
+                        '--full'],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]
@@ -94,6 +118,24 @@ def test_bench_multi_gpu_code_path_on_one_gpu():
     # the N > 1 line carries the CPU baseline too (rank 0's host cores, the N = 1 sample)
     assert 'cpu_baseline' in line and line['cpu_baseline']['value'] > 0 and line['cpu_baseline']['kind'] == 'port'
     assert isinstance(line['config'].get('rccl_info'), str)       # (what RCCL said it chose: rank 0's NCCL_DEBUG=INFO log, condensed)
+
+
+def test_bench_multi_gpu_plain_run_stops_at_the_headline():
+    """The N > 1 path without --full: the first reduce mode whose merged table equals the single-stream count is the headline and the
+    last one measured -- every rank leaves the loop of modes there --, and rank 0 spends no time on the CPU baseline."""
+    import json
+    env = dict(os.environ, KPAL_BENCH_FORCE_MULTI='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
+    p = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
+                        '--master-port', '29635', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--reads', '3000000'],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    assert line['reduce_mode'] == 'library_pipelined' and line['attempt'] == 1 and 'later_modes_failed' not in line
+    assert line['merged_equals_single_stream'] is True and line['checksum_ok'] is True and line['value'] > 0
+    assert list(line['extra']) == ['pipelined_reduce'] and 'serial_reduce_ms_per_step' not in line['config']
+    assert 'cpu_baseline' not in line
 
 
 def test_bench_two_ranks_sharing_one_gpu():
@@ -212,14 +254,14 @@ def test_library_comm_world_over_fake_rccl(worlds, world, mode):
 def test_bench_two_ranks_library_modes_over_fake_rccl(tmp_path, mode):
     """bench.py's N > 1 path with TWO real ranks AND the library's reduce modes: as test_bench_two_ranks_sharing_one_gpu, with the
     stand-in of tests/native/fake_rccl.cpp behind the library's communicator -- pipelined and serial in-library reduce, the torch
-    reduce and the bin-range merge are each measured and each merged table is compared bin for bin with the single-stream count."""
+    reduce and the bin-range merge are each measured (--full) and each merged table is compared bin for bin with the single-stream count."""
     import json
     env = dict(os.environ, KPAL_BENCH_SHARED_GPU='1', KPAL_RCCL_LIBRARY=_build_fake_rccl(tmp_path), HSA_ENABLE_IPC_MODE_LEGACY='0')
     if mode == 'async':
         env.update(KPAL_FAKE_RCCL_ASYNC='1', KPAL_FAKE_RCCL_DELAY_MS='10')
     p = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                         '--master-port', '29647' if mode == 'sync' else '29649', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--reads', '1500000',
-                        '--no-cpu'],
+                        '--no-cpu', '--full'],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]

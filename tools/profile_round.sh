@@ -4,7 +4,7 @@
 #   pmc_hbm_traffic.json / _k15        FETCH_SIZE / WRITE_SIZE passes (separate), per kernel; taken FIRST and copied to
 #                                      profiles/<round>/ so that the bench lines of the same call report roofline.traffic
 #   pmc_lds_quad.json / _k15           SQ LDS / VALU / VMEM counters of the counting kernels
-#   bench_k12_n1.json                  the default bench command: headline + extra (config 4, config 5, end to end) + cpu_baseline
+#   bench_k12_n1.json                  bench.py --full: headline + extra (config 4, config 5, end to end) + cpu_baseline
 #   bench_k12_kernel_stats.csv         rocprofv3 --kernel-trace --stats of the headline alone (--no-extra: the extras launch
 #                                      kernels of the same names on other sizes and would blur the averages)
 #   bench_k15_*                        BASELINE config 4 as its own command, + kernel stats
@@ -44,7 +44,7 @@ pmc pmc_wave_k15 SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY 
 python3 "$ROOT/tools/pmc_counters.py" "rocprofv3 --pmc (two passes) -- python3 bench.py --no-cpu --no-extra $K15 (k=15, 6.04 GB per step)" "$OUT/pmc_lds_k15" "$OUT/pmc_wave_k15" > "$OUT/pmc_lds_quad_k15.json"
 cp "$OUT/pmc_lds_quad_k15.json" "$ROOT/profiles/$ROUND/pmc_lds_quad_k15.json"
 # ---- the bench lines (they read the counter profiles copied above)
-python3 "$B" --steps 20 --warmup 5 > "$OUT/bench_k12_n1.json" 2> "$OUT/bench_k12_n1.err"
+python3 "$B" --steps 20 --warmup 5 --full > "$OUT/bench_k12_n1.json" 2> "$OUT/bench_k12_n1.err"
 rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/stats_k12" -o k12 -- python3 "$B" --steps 10 --warmup 2 --no-cpu --no-extra > "$OUT/bench_k12_n1_under_rocprof.json" 2> "$OUT/stats_k12.err"
 find "$OUT/stats_k12" -name '*kernel_stats.csv' -exec cp {} "$OUT/bench_k12_kernel_stats.csv" \;
 python3 "$B" --k 15 --steps 5 --warmup 1 --no-cpu --no-extra > "$OUT/bench_k15_n1.json" 2> "$OUT/bench_k15_n1.err"
@@ -52,9 +52,9 @@ rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/stats_k15" -o k15 
 find "$OUT/stats_k15" -name '*kernel_stats.csv' -exec cp {} "$OUT/bench_k15_kernel_stats.csv" \;
 for k in 9 11 13 14; do python3 "$B" --k $k --steps 5 --warmup 1 --no-cpu --no-extra > "$OUT/bench_k${k}_n1.json" 2> "$OUT/bench_k${k}_n1.err"; done
 # ---- BASELINE config 5 (64 profiles, k = 12)
-python3 "$B" --workload matrix --steps 5 --warmup 1 > "$OUT/matrix_k12_P64_prod_bench.json" 2> "$OUT/matrix_prod.err"
-python3 "$B" --workload matrix --metric euclidean --steps 5 --warmup 1 > "$OUT/matrix_k12_P64_euclidean_bench.json" 2> "$OUT/matrix_eucl.err"
-python3 "$B" --workload matrix --metric sum --steps 3 --warmup 1 > "$OUT/matrix_k12_P64_sum_bench.json" 2> "$OUT/matrix_sum.err"
+python3 "$B" --workload matrix --steps 5 --warmup 1 --full > "$OUT/matrix_k12_P64_prod_bench.json" 2> "$OUT/matrix_prod.err"
+python3 "$B" --workload matrix --metric euclidean --steps 5 --warmup 1 --full > "$OUT/matrix_k12_P64_euclidean_bench.json" 2> "$OUT/matrix_eucl.err"
+python3 "$B" --workload matrix --metric sum --steps 3 --warmup 1 --full > "$OUT/matrix_k12_P64_sum_bench.json" 2> "$OUT/matrix_sum.err"
 rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/stats_matrix" -o m -- python3 "$B" --workload matrix --steps 5 --warmup 1 --no-cpu > "$OUT/matrix_k12_P64_prod_under_rocprof.json" 2> "$OUT/stats_matrix.err"
 find "$OUT/stats_matrix" -name '*kernel_stats.csv' -exec cp {} "$OUT/matrix_k12_P64_prod_kernel_stats.csv" \;
 rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/stats_matrix_s" -o m -- python3 "$B" --workload matrix --metric sum --steps 5 --warmup 1 --no-cpu > "$OUT/matrix_k12_P64_sum_under_rocprof.json" 2> "$OUT/stats_matrix_s.err"
@@ -112,8 +112,7 @@ hipcc -O3 --offload-arch=gfx950 -o /tmp/valu_bench tools/valu_bench.hip 2> /dev/
 hipcc -O3 --offload-arch=gfx950 -o /tmp/lds_bench tools/lds_bench.hip 2> /dev/null && timeout 300 /tmp/lds_bench > "$OUT/lds_bench.log" 2>&1
 # ---- the N > 1 path of bench.py with 2, 3, 4 and 8 real ranks on this one GPU over the test stand-in for RCCL, synchronous and
 #      asynchronous calls (correctness only: merged_equals_single_stream of every merge mode)
-mkdir -p gpurun_out/multi_rank
-{ bash tools/multi_rank_one_gpu.sh; echo "# KPAL_FAKE_RCCL_ASYNC=1 KPAL_FAKE_RCCL_DELAY_MS=5"; KPAL_FAKE_RCCL_ASYNC=1 KPAL_FAKE_RCCL_DELAY_MS=5 bash tools/multi_rank_one_gpu.sh; } > "$OUT/multi_rank_one_gpu.log" 2>&1
+{ bash tools/multi_rank_one_gpu.sh "$OUT/multi_rank"; echo "# KPAL_FAKE_RCCL_ASYNC=1 KPAL_FAKE_RCCL_DELAY_MS=5"; KPAL_FAKE_RCCL_ASYNC=1 KPAL_FAKE_RCCL_DELAY_MS=5 bash tools/multi_rank_one_gpu.sh "$OUT/multi_rank_async"; } > "$OUT/multi_rank_one_gpu.log" 2>&1
 # keep only the small summaries (the merge back is capped at 64 MiB)
 find "$OUT" -name '*.db' -delete; find "$OUT" -name '*kernel_trace.csv' -delete; find "$OUT" -name '*counter_collection.csv' -delete
 ls -la "$OUT"; for f in "$OUT"/bench_k1[25]_n1.json "$OUT"/matrix*_bench.json; do echo "== $f"; head -c 1200 "$f"; echo; done
