@@ -279,6 +279,17 @@ int kpal_distance_matrix(kpal_ctx *ctx, int P, int k, const int64_t *const *host
 int kpal_distance_matrix_device(kpal_ctx *ctx, int P, int k, const int64_t *dev_profiles /* P x 4^k */,
                                 int metric, int do_balance, double *out_lower);
 
+/* The rectangle of distances between two sets of profiles (no counterpart in kPAL: a sample against a panel):
+ * out[q * R + r] = distance(left[q], right[r]) for 0 <= q < Q, 0 <= r < R (row = left, column = right), metric and
+ * do_balance as for kpal_distance_matrix.  The sets are separate allocations and may alias or overlap (a set against
+ * itself gives the full symmetric square with a zero diagonal); no pair inside one set is evaluated.  The host variant
+ * uploads both sets through the context's scratch. */
+int kpal_cross_distance(kpal_ctx *ctx, int k, int Q, const int64_t *const *host_left, int R,
+                        const int64_t *const *host_right, int metric, int do_balance, double *out);
+int kpal_cross_distance_device(kpal_ctx *ctx, int k, int Q, const int64_t *dev_left /* Q x 4^k */, int R,
+                               const int64_t *dev_right /* R x 4^k */, int metric, int do_balance,
+                               double *out /* host, Q x R */);
+
 /* ---- ProfileDistance with its full option set, kdistlib.py:25-51,126-161 ----
  * The constructor arguments of kdistlib.ProfileDistance that select built-in behaviour; a
  * user-supplied summary / pairwise / distance callable cannot enter a kernel and stays in Python. */

@@ -13,4 +13,4 @@ __version__ = '0.3.0'
 from . import _native, metrics, klib, kdistlib, files, kmer, dist  # noqa: E402,F401
 from .files import FileType, ProfileFileType  # noqa: F401
 from .klib import Profile  # noqa: F401
-from .kdistlib import ProfileDistance, distance_matrix  # noqa: F401
+from .kdistlib import ProfileDistance, distance_matrix, cross_distances  # noqa: F401

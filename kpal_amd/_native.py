@@ -124,6 +124,10 @@ SIGNATURES = {
                                             ctypes.c_int, _f64p]),
     'kpal_distance_matrix_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
                                                    ctypes.c_int, _f64p]),
+    'kpal_cross_distance': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp), ctypes.c_int,
+                                           ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, _f64p]),
+    'kpal_cross_distance_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int,
+                                                  ctypes.c_int, _f64p]),
     'kpal_profile_distance': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _optp, _f64p]),
     'kpal_profile_distance_device': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _optp, _f64p]),
     'kpal_dynamic_smooth': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_double]),
@@ -639,6 +643,27 @@ class Context(object):
         out = np.zeros(P * (P - 1) // 2, dtype=np.float64)
         _check(self._L.kpal_distance_matrix_device(self._h, int(P), int(k), _vp(dev_profiles), int(metric),
                                                    int(bool(do_balance)), out.ctypes.data_as(_f64p)))
+        return out
+
+    def cross_distance(self, left, right, k, metric, do_balance=False):
+        """left, right: lists of int64[4**k] host vectors -> float64[Q, R], [q, r] = distance(left[q], right[r])."""
+        la, ra = [_as_i64(p) for p in left], [_as_i64(p) for p in right]
+        for a in la + ra:
+            if a.size != 4 ** k:
+                raise ValueError('profile length %d != 4**%d' % (a.size, k))
+        Q, R = len(la), len(ra)
+        out = np.zeros((Q, R), dtype=np.float64)
+        lp = (_vp * Q)(*[a.ctypes.data for a in la])
+        rp = (_vp * R)(*[a.ctypes.data for a in ra])
+        _check(self._L.kpal_cross_distance(self._h, int(k), Q, lp, R, rp, int(metric), int(bool(do_balance)),
+                                           out.ctypes.data_as(_f64p)))
+        return out
+
+    def cross_distance_device(self, k, Q, dev_left, R, dev_right, metric, do_balance=False):
+        """dev_left: Q consecutive tables, dev_right: R consecutive tables (device addresses) -> float64[Q, R]."""
+        out = np.zeros((int(Q), int(R)), dtype=np.float64)
+        _check(self._L.kpal_cross_distance_device(self._h, int(k), int(Q), _vp(dev_left), int(R), _vp(dev_right),
+                                                  int(metric), int(bool(do_balance)), out.ctypes.data_as(_f64p)))
         return out
 
     # -- ProfileDistance with options ------------------------------------------------------------

@@ -1,0 +1,150 @@
+// kpal_cross.hip -- kpal_cross_distance[_device]: the Q x R rectangle of distances between a left and a right set of
+// profiles in separate allocations (cross_kernels.hpp).  One call is a fixed number of launches whatever Q and R are:
+// the balance of each profile (do_balance), one rectangle kernel (two when a fast form gives up on the values), one
+// fixed-order reduction of the per-workgroup partials.
+#include "kpal_host.hpp"
+
+#include "cross_kernels.hpp"
+
+// Euclidean from the fp64 dot products of cross_gram_kernel and the norms of cross_norm_kernel.  *exact = false (and
+// `out` untouched) when some |x|^2 >= 2^53 -- gram_euclidean's rule: the caller then takes the wrapping-int64 kernel.
+static int cross_gram_euclidean(kpal_ctx *ctx, const CrossSets &c, double *out, bool *exact)
+{
+    const int blocksQ = (c.Q + 63) / 64, blocksR = (c.R + 63) / 64;
+    const uint32_t nblocks = (uint32_t)blocksQ * (uint32_t)blocksR, nprof = (uint32_t)c.Q + (uint32_t)c.R;
+    const uint64_t slabs = c.n / kGramBins;
+    // one 132 KiB workgroup per CU
+    const uint32_t gx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(slabs, (uint64_t)ctx->num_cu / nblocks));
+    const size_t dots = (size_t)nblocks * 4096, groups = dots + nprof;
+    if (groups > 0x7fffffffu / gx) return set_err(KPAL_E_INVALID, "cross distance: %d x %d profiles are too many for one call", c.Q, c.R);
+    CHK(ensure(ctx, ctx->partials, groups * gx * sizeof(Partial)));
+    Partial *pp = (Partial *)ctx->partials.p;
+    LAUNCH(ctx, "cross_gram", cross_gram_kernel, dim3(nblocks * gx), dim3(256), c, gx, blocksR, pp);
+    LAUNCH(ctx, "cross_norm", cross_norm_kernel, dim3(nprof * gx), dim3(256), c, gx, pp + dots * gx);
+    std::vector<Partial> res;
+    CHK(finish_partials(ctx, (uint32_t)groups, gx, res));
+    const double limit = 9007199254740992.0;     // 2^53
+    for (uint32_t p = 0; p < nprof; ++p)
+        if (!(res[dots + p].s < limit)) {
+            *exact = false;
+            return KPAL_OK;
+        }
+    for (int q = 0; q < c.Q; ++q)
+        for (int r = 0; r < c.R; ++r) {
+            const size_t block = (size_t)(q / 64) * blocksR + (size_t)(r / 64);
+            const size_t tile = (size_t)((q % 64) / 16) * 4 + (size_t)((r % 64) / 16);
+            const double dot = res[(block * 16 + tile) * 256 + (size_t)((q % 16) * 16 + (r % 16))].s;
+            // exact integers below 2^53 each: the int64 expression is the reference's sum of squared differences
+            const int64_t d2 = (int64_t)res[dots + q].s + (int64_t)res[dots + c.Q + r].s - 2 * (int64_t)dot;
+            out[(size_t)q * c.R + r] = std::sqrt((double)d2);   // metrics.py:46: np.sqrt(np.dot(v, v))
+        }
+    *exact = true;
+    return KPAL_OK;
+}
+
+static int cross_core(kpal_ctx *ctx, const CrossSets &c, int metric, double *out)
+{
+    constexpr int TILE = 4;
+    // the LDS-staged kernels take 64 bins at a time (k >= 6) and pay when both sides fill more than one register tile; with
+    // at most four profiles on a side the register-tile kernel already reads the long side once
+    const bool staged = c.n >= 4096 && c.Q > TILE && c.R > TILE;
+    if (metric == KPAL_EUCLIDEAN && staged) {
+        bool exact = false;
+        CHK(cross_gram_euclidean(ctx, c, out, &exact));
+        if (exact) return KPAL_OK;
+    }
+    const int sideQ = (c.Q + TILE - 1) / TILE, sideR = (c.R + TILE - 1) / TILE;
+    const uint64_t slots = (uint64_t)sideQ * sideR * TILE * TILE;
+    uint32_t gx;
+    if (staged) {
+        const int superQ = (c.Q + 15) / 16, superR = (c.R + 15) / 16;
+        const uint32_t nsuper = (uint32_t)superQ * (uint32_t)superR;
+        gx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(c.n / kSuperBins, std::max<uint64_t>(1, (uint64_t)ctx->num_cu * 8 / nsuper)));
+        gx = std::max(8u, gx / 8u * 8u);   // (cross_block deals bin-groups to the 8 XCDs; n / 64 >= 64 for k >= 6)
+        if (slots > 0x7fffffffu / gx) return set_err(KPAL_E_INVALID, "cross distance: %d x %d profiles are too many for one call", c.Q, c.R);
+        CHK(ensure(ctx, ctx->partials, slots * gx * sizeof(Partial)));
+        CHK(ensure(ctx, ctx->scratch[3], 16));
+        Partial *pp = (Partial *)ctx->partials.p;
+        bool done = false;
+        if (metric != KPAL_EUCLIDEAN) {
+            // the reciprocal forms, valid while every count is below 2^16 ('prod') or fits the table ('sum'): the kernel says
+            // whether it saw a larger one
+            uint32_t *big = (uint32_t *)ctx->scratch[3].p;
+            HIPCHK(hipMemsetAsync(big, 0, sizeof(uint32_t), ctx->stream));
+            HIPCHK(hipMemsetAsync(pp, 0, slots * gx * sizeof(Partial), ctx->stream));   // (.s / .m of a slot come from different threads)
+            if (metric == KPAL_PAIRWISE_PROD) LAUNCH(ctx, "cross_rdiff", (cross_recip_kernel<0>), dim3(gx * nsuper), dim3(256), c, nsuper, superR, pp, big);
+            else LAUNCH(ctx, "cross_rsum", (cross_recip_kernel<1>), dim3(gx * nsuper), dim3(256), c, nsuper, superR, pp, big);
+            uint32_t saw_big = 0;
+            HIPCHK(hipMemcpyAsync(&saw_big, big, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            done = saw_big == 0;
+        }
+        if (done) {
+        } else if (metric == KPAL_PAIRWISE_PROD) LAUNCH(ctx, "cross_super", (cross_super_kernel<0>), dim3(gx * nsuper), dim3(256), c, nsuper, superR, pp);
+        else if (metric == KPAL_PAIRWISE_SUM) LAUNCH(ctx, "cross_super", (cross_super_kernel<1>), dim3(gx * nsuper), dim3(256), c, nsuper, superR, pp);
+        else LAUNCH(ctx, "cross_super", (cross_super_kernel<2>), dim3(gx * nsuper), dim3(256), c, nsuper, superR, pp);
+    } else {
+        const uint64_t ntiles = (uint64_t)sideQ * sideR;
+        gx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((c.n + 255) / 256, std::max<uint64_t>(1, (uint64_t)ctx->num_cu * 16 / ntiles)));
+        if (slots > 0x7fffffffu / gx) return set_err(KPAL_E_INVALID, "cross distance: %d x %d profiles are too many for one call", c.Q, c.R);
+        CHK(ensure(ctx, ctx->partials, slots * gx * sizeof(Partial)));
+        Partial *pp = (Partial *)ctx->partials.p;
+        const dim3 grid((unsigned)(ntiles * gx));
+        if (metric == KPAL_PAIRWISE_PROD) LAUNCH(ctx, "cross_tile", (cross_tile_kernel<0>), grid, dim3(256), c, gx, pp);
+        else if (metric == KPAL_PAIRWISE_SUM) LAUNCH(ctx, "cross_tile", (cross_tile_kernel<1>), grid, dim3(256), c, gx, pp);
+        else LAUNCH(ctx, "cross_tile", (cross_tile_kernel<2>), grid, dim3(256), c, gx, pp);
+    }
+    std::vector<Partial> res;
+    CHK(finish_partials(ctx, (uint32_t)slots, gx, res));
+    for (int q = 0; q < c.Q; ++q)
+        for (int r = 0; r < c.R; ++r) {
+            const size_t slot = ((size_t)(q / TILE) * sideR + (size_t)(r / TILE)) * TILE * TILE + (size_t)((q % TILE) * TILE + r % TILE);
+            out[(size_t)q * c.R + r] = finish_value(metric, res[slot], nullptr);
+        }
+    return KPAL_OK;
+}
+
+static int cross_check(int k, int Q, int R, int metric, const void *left, const void *right, const double *out)
+{
+    if (Q < 1 || R < 1) return set_err(KPAL_E_INVALID, "Q and R must be >= 1");
+    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
+    if (metric < 0 || metric > 2) return set_err(KPAL_E_INVALID, "unknown metric %d", metric);
+    if (!left || !right || !out) return set_err(KPAL_E_INVALID, "NULL pointer");
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_cross_distance_device(kpal_ctx *ctx, int k, int Q, const int64_t *dev_left, int R, const int64_t *dev_right,
+                                        int metric, int do_balance, double *out)
+{
+    CTX_ENTER(ctx);
+    CHK(cross_check(k, Q, R, metric, dev_left, dev_right, out));
+    if (((uintptr_t)dev_left & 15) || ((uintptr_t)dev_right & 15)) return set_err(KPAL_E_INVALID, "device tables must be 16-byte aligned");
+    const uint64_t n = 1ULL << (2 * k);
+    CrossSets c = {dev_left, dev_right, Q, R, n};
+    if (do_balance) {
+        // balance once per profile: identical to the reference balancing copies per pair (kdistlib.py:136-141)
+        CHK(ensure(ctx, ctx->scratch[2], ((size_t)Q + (size_t)R) * n * 8));
+        int64_t *bl = (int64_t *)ctx->scratch[2].p, *br = bl + (uint64_t)Q * n;
+        for (int q = 0; q < Q; ++q) CHK(launch_balance(ctx, k, dev_left + (uint64_t)q * n, bl + (uint64_t)q * n));
+        for (int r = 0; r < R; ++r) CHK(launch_balance(ctx, k, dev_right + (uint64_t)r * n, br + (uint64_t)r * n));
+        c.left = bl;
+        c.right = br;
+    }
+    return cross_core(ctx, c, metric, out);
+}
+
+KPAL_API int kpal_cross_distance(kpal_ctx *ctx, int k, int Q, const int64_t *const *host_left, int R,
+                                 const int64_t *const *host_right, int metric, int do_balance, double *out)
+{
+    CTX_ENTER(ctx);
+    CHK(cross_check(k, Q, R, metric, host_left, host_right, out));
+    const uint64_t n = 1ULL << (2 * k);
+    CHK(ensure(ctx, ctx->scratch[0], ((size_t)Q + (size_t)R) * n * 8));
+    int64_t *dl = (int64_t *)ctx->scratch[0].p, *dr = dl + (uint64_t)Q * n;
+    for (int p = 0; p < Q + R; ++p) {
+        const int64_t *src = p < Q ? host_left[p] : host_right[p - Q];
+        if (!src) return set_err(KPAL_E_INVALID, "%s profile %d is NULL", p < Q ? "left" : "right", p < Q ? p : p - Q);
+        HIPCHK(hipMemcpyAsync(dl + (uint64_t)p * n, src, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return kpal_cross_distance_device(ctx, k, Q, dl, R, dr, metric, do_balance, out);
+}

@@ -2,7 +2,7 @@
 // workspace buffers, per-kernel HIP-event timing, the launch / dispatch macros and the few host functions
 // one unit calls in another.  (kpal_ctx.hip: context + profiling API; kpal_count.hip: counting front end and the
 // round-1 pipelines; kpal_quads.hip / kpal_quads2.hip: the quad record pipelines; kpal_vec.hip: balance, split,
-// distances, matrices, options, summaries; kpal_multi.hip: multi-GPU entry points over RCCL.)
+// distances, matrices, options, summaries; kpal_cross.hip: the rectangle of distances between two sets; kpal_multi.hip: multi-GPU entry points over RCCL.)
 #pragma once
 #include "../../include/kpal_hip.h"
 
@@ -309,4 +309,7 @@ int table_ready(kpal_ctx *ctx);                                           // kpa
 int launch_balance(kpal_ctx *ctx, int k, const int64_t *in, int64_t *out);   // kpal_vec.hip
 int distance_matrix_core(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof, int metric, double *out_lower, bool allreduce,
                          int tiled = -1);   // kpal_vec.hip (tiled: -1 decided from n; 0 / 1 agreed between the ranks)
+namespace kpal { struct Partial; }   // vec_kernels.hpp
+int finish_partials(kpal_ctx *ctx, uint32_t nq, uint32_t nblocks, std::vector<Partial> &out, bool allreduce = false);   // kpal_vec.hip: reduce nq groups of nblocks partials, fetch them
+double finish_value(int metric, const Partial &p, int64_t *aux);         // kpal_vec.hip: the distance of one reduced partial
 int comm_allreduce_partials(kpal_ctx *ctx, void *dev_partials, size_t count);   // kpal_multi.hip: {double sum, uint64 count} pairs added over the ranks, in place

@@ -137,7 +137,7 @@ KPAL_API int kpal_split(kpal_ctx *ctx, int k, const int64_t *host_counts, int64_
 }
 
 // Reduce `nq` groups of `nblocks` partials and fetch them.
-static int finish_partials(kpal_ctx *ctx, uint32_t nq, uint32_t nblocks, std::vector<Partial> &out, bool allreduce = false)
+int finish_partials(kpal_ctx *ctx, uint32_t nq, uint32_t nblocks, std::vector<Partial> &out, bool allreduce)
 {
     CHK(ensure(ctx, ctx->result, (size_t)nq * sizeof(Partial)));
     LAUNCH(ctx, "reduce_partials", reduce_partials_kernel, dim3(nq), dim3(256), (const Partial *)ctx->partials.p,
@@ -149,7 +149,7 @@ static int finish_partials(kpal_ctx *ctx, uint32_t nq, uint32_t nblocks, std::ve
     return KPAL_OK;
 }
 
-static double finish_value(int metric, const Partial &p, int64_t *aux)
+double finish_value(int metric, const Partial &p, int64_t *aux)
 {
     if (metric == KPAL_EUCLIDEAN) {
         if (aux) *aux = (int64_t)p.m;

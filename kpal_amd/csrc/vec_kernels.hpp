@@ -9,8 +9,15 @@
 // fp64 sums are reduced in a FIXED order (per-thread serial, wave shuffle tree, block tree,
 // then a single-workgroup pass over the per-block partials) so results are run-to-run
 // reproducible; they agree with NumPy's pairwise summation to ~1e-15 relative.
+// (Kernels that are not templates are `inline`: kpal_vec.hip and kpal_cross.hip both include this header, and the keyword
+// lets the host-side stubs of the two units coexist at link time -- only the unit that launches a kernel emits its stub.
+// The DEVICE code of every kernel here is still compiled into both units' code objects, unused in kpal_cross's.  clang
+// notes that CUDA would ignore the keyword on a kernel; HIP does not.)
 #pragma once
 #include "kpal_device.hpp"
+
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wcuda-compat"
 
 namespace kpal {
 
@@ -66,7 +73,7 @@ __device__ __forceinline__ Partial block_reduce(Partial p)
 
 // ---- balance ------------------------------------------------------------------------------
 // out[i] = in[i] + in[rc(i)] (i == rc(i) gives 2*in[i], klib.py:297-298).  Out of place.
-__global__ __launch_bounds__(256) void balance_oop_kernel(const int64_t *__restrict__ in, int64_t *__restrict__ out,
+inline __global__ __launch_bounds__(256) void balance_oop_kernel(const int64_t *__restrict__ in, int64_t *__restrict__ out,
                                                           int k, uint64_t n)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
@@ -74,7 +81,7 @@ __global__ __launch_bounds__(256) void balance_oop_kernel(const int64_t *__restr
 }
 
 // In place: the thread owning i < rc(i) updates both ends of the pair (klib.py:290-296).
-__global__ __launch_bounds__(256) void balance_inplace_kernel(int64_t *__restrict__ c, int k, uint64_t n)
+inline __global__ __launch_bounds__(256) void balance_inplace_kernel(int64_t *__restrict__ c, int k, uint64_t n)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t r = revcomp(i, k);
@@ -99,7 +106,7 @@ __global__ __launch_bounds__(256) void balance_inplace_kernel(int64_t *__restric
 // persistent workgroups take them round robin -- every workgroup gets the same number of pairs to within one.  (Striding through
 // M itself and skipping the non-canonical ones left the work badly spread: a workgroup's M share their low digits, and those
 // decide whether M <= rc(M) for nearly all of them -- a quarter of the workgroups had eight pairs, a quarter none.)
-__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void balance_tiled_kernel(const int64_t *in, int64_t *out, int k,
+inline __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void balance_tiled_kernel(const int64_t *in, int64_t *out, int k,
                                                                                                      const uint32_t *__restrict__ canon, uint32_t ncanon)
 {
     constexpr int T = 3, S = 64;
@@ -162,7 +169,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
 // segment; the host scans the (small) count array; pass 2 writes.
 constexpr int kSplitSeg = 4096;  // indices per block
 
-__global__ __launch_bounds__(256) void split_count_kernel(int k, uint64_t n, uint32_t *__restrict__ seg_count)
+inline __global__ __launch_bounds__(256) void split_count_kernel(int k, uint64_t n, uint32_t *__restrict__ seg_count)
 {
     const uint64_t base = (uint64_t)blockIdx.x * kSplitSeg;
     uint32_t c = 0;
@@ -178,7 +185,7 @@ __global__ __launch_bounds__(256) void split_count_kernel(int k, uint64_t n, uin
     if (threadIdx.x == 0) seg_count[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-__global__ __launch_bounds__(256) void split_write_kernel(const int64_t *__restrict__ c, int k, uint64_t n,
+inline __global__ __launch_bounds__(256) void split_write_kernel(const int64_t *__restrict__ c, int k, uint64_t n,
                                                           const uint64_t *__restrict__ seg_offset,
                                                           int64_t *__restrict__ fwd, int64_t *__restrict__ rev)
 {
@@ -448,7 +455,7 @@ __global__ __launch_bounds__(1024) void strand_balance_tiled_kernel(const int64_
 }
 
 // Final fixed-order reduction of per-block partials: out[q] = sum over blocks of partials[q*nblocks + b].
-__global__ __launch_bounds__(256) void reduce_partials_kernel(const Partial *__restrict__ partials, uint32_t nblocks,
+inline __global__ __launch_bounds__(256) void reduce_partials_kernel(const Partial *__restrict__ partials, uint32_t nblocks,
                                                               Partial *__restrict__ out)
 {
     const Partial *src = partials + (uint64_t)blockIdx.x * nblocks;
@@ -813,7 +820,7 @@ constexpr unsigned long long kRdiffMaxCount = 1ull << 16;   // counts the differ
 constexpr int kRdiffTable = 512;    // reciprocals 1 / (c + 1) of counts c < 512 (4 KiB: four workgroups per CU)
 constexpr int kRdiffRow = 64;       // staged row: 64 bins, unpadded -- with 16-byte reads a 16-lane group covers all 64 banks, and
                                     // rows a multiple of 8 doubles apart keep the lanes of two groups that share a read pass apart
-__global__ __launch_bounds__(256) void matrix_rdiff_kernel(const int64_t *__restrict__ prof, int P, uint64_t n,
+inline __global__ __launch_bounds__(256) void matrix_rdiff_kernel(const int64_t *__restrict__ prof, int P, uint64_t n,
                                                            const int2 *__restrict__ supers, uint32_t nsuper,
                                                            Partial *__restrict__ partials, uint32_t *__restrict__ big)
 {
@@ -970,7 +977,7 @@ __global__ __launch_bounds__(256) void matrix_rdiff_kernel(const int64_t *__rest
 // such stages cost the kernel its occupancy: 200 registers).
 //   Accuracy: R within 1 ulp, |x - y| exact: a term within 1.5 ulp of the correctly rounded quotient the reference computes.
 constexpr int kRsumTable = 2048;
-__global__ __launch_bounds__(256) void matrix_rsum_kernel(const int64_t *__restrict__ prof, int P, uint64_t n,
+inline __global__ __launch_bounds__(256) void matrix_rsum_kernel(const int64_t *__restrict__ prof, int P, uint64_t n,
                                                           const int2 *__restrict__ supers, uint32_t nsuper,
                                                           Partial *__restrict__ partials, uint32_t *__restrict__ big)
 {
@@ -1101,3 +1108,5 @@ __global__ __launch_bounds__(256) void matrix_rsum_kernel(const int64_t *__restr
 }
 
 }  // namespace kpal
+
+#pragma clang diagnostic pop

@@ -9,6 +9,9 @@ steps (kpal/kdistlib.py:143-157) and cosine similarity run on the device too
 (``kpal_profile_distance``) whenever every callable is one of kPAL's built-ins (the values of
 ``metrics.summary`` / ``metrics.pairwise`` / ``metrics.vector_distance``, recognised by identity);
 a user-supplied callable cannot enter a kernel and keeps the reference's NumPy formulation.
+
+Beyond the reference: :func:`cross_distances` / :func:`cross_distance_matrix` / :func:`nearest` -- the Q x R rectangle of
+distances between a left and a right set of profiles (``kpal_cross_distance_device``), a fixed number of launches per chunk of the right side.
 """
 import numpy as np
 
@@ -178,6 +181,158 @@ def distance_matrix(profiles, output, precision, dist):
         values = [dist.distance(profiles[i], profiles[j]) for i in range(1, count) for j in range(i)]
 
     _write_matrix(output, count, values, precision)
+
+
+#: Right-side tables resident at a time in :func:`cross_distances` unless ``max_bytes`` says otherwise: an eighth of the
+#: 288 GB of an MI355X, so the default needs no device query.
+CROSS_MAX_BYTES = 32 << 30
+
+
+def cross_chunks(table_bytes, count, max_bytes):
+    """Bounds ``[(start, stop), ...]`` of the chunks ``count`` right-side tables of ``table_bytes`` each are processed in so
+    that at most ``max_bytes`` of them are resident at a time -- never less than one table per chunk."""
+    per = _chunk_tables(table_bytes, max_bytes)
+    return [(at, min(at + per, count)) for at in range(0, count, per)]
+
+
+def _chunk_tables(table_bytes, max_bytes):
+    return max(1, int(max_bytes) // int(table_bytes))
+
+
+def _chunked(iterable, size):
+    chunk = []
+    for item in iterable:
+        chunk.append(item)
+        if len(chunk) == size:
+            yield chunk
+            chunk = []
+    if chunk:
+        yield chunk
+
+
+class _DeviceSet(object):
+    """The tables of ``profiles`` (one k) as consecutive int64 tables in HBM on ``ctx``: where they lie when they are
+    consecutive tables of one batch on that context, otherwise gathered (device-to-device copies for tables in HBM on that
+    context, uploads for host counts) into an allocation that ``release`` frees."""
+
+    def __init__(self, ctx, profiles):
+        k = profiles[0].length
+        table_bytes = 8 * 4 ** k
+        devs = []
+        for p in profiles:
+            d = getattr(p, '_device_counts', None)
+            d = d() if d is not None else None
+            devs.append(d if d and d[0] is ctx else None)
+        self.ctx, self.owned = ctx, None
+        if all(devs) and all(devs[i][1] == devs[0][1] + i * table_bytes for i in range(len(devs))):
+            self.ptr = devs[0][1]
+            return
+        self.ptr = self.owned = ctx.alloc(len(profiles) * table_bytes)
+        try:
+            for i, (p, d) in enumerate(zip(profiles, devs)):
+                if d:
+                    ctx.d2d(self.ptr + i * table_bytes, d[1], table_bytes)
+                else:
+                    ctx.h2d(self.ptr + i * table_bytes, _native._as_i64(p.counts))
+        except BaseException:
+            self.release()
+            raise
+
+    def release(self):
+        if self.owned is not None:
+            owned, self.owned = self.owned, None
+            self.ctx.sync()
+            self.ctx.free(owned)
+
+
+def _cross_context(profiles):
+    """The context the first device-resident profile lives on, else the default one."""
+    for p in profiles:
+        d = getattr(p, '_device_counts', None)
+        d = d() if d is not None else None
+        if d:
+            return d[0]
+    return _native.context()
+
+
+def _integer_counts(profile):
+    return getattr(profile, '_device_counts', lambda: None)() is not None or np.asanyarray(profile.counts).dtype.kind in 'iub'
+
+
+def cross_distances(left_profiles, right_profiles, dist, max_bytes=None):
+    """``values[q, r] = dist.distance(left_profiles[q], right_profiles[r])`` as a float64 array of shape (Q, R).
+
+    A plain ``dist`` (no positive / smooth / scale step, a built-in metric other than cosine) over integer profiles of one k
+    is a fixed number of launches per chunk of the right side (``kpal_cross_distance_device``: a rectangle kernel and a
+    reduction, a balance per profile with ``do_balance``, a second rectangle kernel when a fast form gives up on the values): the left tables stay resident,
+    ``right_profiles`` -- any iterable, read once -- is taken in chunks of at most ``max_bytes`` of tables (default
+    ``CROSS_MAX_BYTES``, never less than one table).  Tables that are consecutive in one device batch are used where they
+    lie.  Any other ``dist`` is ``dist.distance`` pair by pair."""
+    left = list(left_profiles)
+    if not left:
+        raise ValueError('cross_distances needs at least one left profile')
+    metric = dist._native_metric()
+    k = left[0].length
+    fast = (dist._is_plain() and metric is not None and metric != _native.COSINE
+            and all(p.length == k for p in left) and all(_integer_counts(p) for p in left))
+    if not fast:
+        right = list(right_profiles)
+        return np.array([[dist.distance(l, r) for r in right] for l in left], dtype=np.float64).reshape(len(left), len(right))
+    table_bytes = 8 * 4 ** k
+    per = _chunk_tables(table_bytes, CROSS_MAX_BYTES if max_bytes is None else max_bytes)
+    ctx = _cross_context(left)
+    blocks = []
+    lset = _DeviceSet(ctx, left)
+    try:
+        for chunk in _chunked(right_profiles, per):
+            if any(p.length != k or not _integer_counts(p) for p in chunk):
+                # a mixed-k pair raises what dist.distance raises; other counts (scaled profiles) keep its formulation
+                blocks.append(np.array([[dist.distance(l, r) for r in chunk] for l in left], dtype=np.float64))
+                continue
+            rset = lset if (len(chunk) == len(left) and all(a is b for a, b in zip(chunk, left))) else _DeviceSet(ctx, chunk)
+            try:
+                blocks.append(ctx.cross_distance_device(k, len(left), lset.ptr, len(chunk), rset.ptr, metric,
+                                                        do_balance=dist._do_balance))
+            finally:
+                if rset is not lset:
+                    rset.release()
+    finally:
+        lset.release()
+    if not blocks:
+        return np.zeros((len(left), 0), dtype=np.float64)
+    return np.concatenate(blocks, axis=1)
+
+
+def nearest(values, n):
+    """For each row of ``values`` the indices of its ``n`` smallest entries, ascending, ties by the lower index, NaN last
+    (an int array of shape (rows, min(n, columns)))."""
+    values = np.asarray(values, dtype=np.float64)
+    if values.ndim != 2:
+        raise ValueError('nearest needs a two-dimensional array')
+    n = max(0, min(int(n), values.shape[1]))
+    return np.argsort(values, axis=1, kind='stable')[:, :n]
+
+
+def cross_distance_matrix(left_profiles, right_profiles, output, precision, dist, max_bytes=None):
+    """Write the rectangle of :func:`cross_distances` to ``output``: ``Q R``, the Q left names, the R right names, then Q
+    lines of R distances, ``precision`` decimals, space separated.  Returns the values."""
+    left = list(left_profiles)
+    right_names = []
+
+    def named(profiles):
+        for p in profiles:
+            right_names.append(p.name)
+            yield p
+
+    values = cross_distances(left, named(right_profiles), dist, max_bytes=max_bytes)
+    print('{0} {1}'.format(len(left), len(right_names)), file=output)
+    for name in [p.name for p in left] + right_names:
+        print(name, file=output)
+    fmt = '{{0:.{0}f}}'.format(precision)
+    for row in values:
+        output.write(' '.join(fmt.format(v) for v in row))
+        output.write('\n')
+    return values
 
 
 def _write_matrix(output, count, values, precision):

@@ -339,6 +339,44 @@ def distance_matrix(input_handle, output_handle, names=None, distance_function='
     kdistlib.distance_matrix(profiles, output_handle, precision, dist)
 
 
+def cross(input_handle_left, input_handle_right, output_handle, names_left=None, names_right=None,
+          distance_function='default', pairwise='prod', custom_pairwise=None, do_smooth=False, summary='min',
+          custom_summary=None, threshold=0, do_scale=False, down=False, do_positive=False, do_balance=False,
+          precision=10, nearest=None):
+    """Distances of every profile of the left file to every profile of the right file: ``Q R``, the left names, the
+    right names, then Q lines of R distances; with --nearest N, ``left right distance`` lines of the N closest right
+    profiles per left profile instead.
+
+    A fixed number of kernel launches per chunk of the right file for the built-in functions; the right file is read profile by
+    profile, so only a chunk of it is resident at a time."""
+    names_left = _profile_names(input_handle_left, names_left)
+    names_right = _profile_names(input_handle_right, names_right)
+    if not names_left or not names_right:
+        raise ValueError('you must give at least one k-mer profile on each side')
+    if nearest is not None and nearest < 1:
+        raise ValueError('--nearest needs a positive number')
+    dist = _profile_distance(distance_function, pairwise, custom_pairwise, do_smooth, summary, custom_summary,
+                             threshold, do_scale, down, do_positive, do_balance)
+    left = [klib.Profile.from_file(input_handle_left, name=name) for name in names_left]
+
+    def right():
+        for name in names_right:
+            profile = klib.Profile.from_file(input_handle_right, name=name)
+            if profile.length != left[0].length:
+                raise ValueError(LENGTH_ERROR)
+            yield profile
+
+    if any(profile.length != left[0].length for profile in left):
+        raise ValueError(LENGTH_ERROR)
+    if nearest is None:
+        kdistlib.cross_distance_matrix(left, right(), output_handle, precision, dist)
+        return
+    values = kdistlib.cross_distances(left, right(), dist)
+    for q, row in enumerate(kdistlib.nearest(values, nearest)):
+        for r in row:
+            print(names_left[q], names_right[r], _fixed(precision, values[q, r]), file=output_handle)
+
+
 def _parsers():
     """The option groups shared by the sub-commands (kpal/kmer.py:712-824), as argparse parents."""
     def parent():
@@ -411,7 +449,7 @@ def _parsers():
 
 
 def build_parser():
-    """The ``kpal`` command line (kpal/kmer.py:826-964): seventeen sub-commands, same options and defaults."""
+    """The ``kpal`` command line (kpal/kmer.py:826-964): seventeen sub-commands, same options and defaults, and ``cross``."""
     p = _parsers()
     parser = argparse.ArgumentParser(formatter_class=argparse.RawDescriptionHelpFormatter, description=files.USAGE[0],
                                      epilog=files.USAGE[1])
@@ -469,6 +507,10 @@ def build_parser():
     command('smooth', smooth, ['paired_input_profile', 'paired_output_profile', 'smooth'])
     command('distance', distance, ['paired_input_profile', 'dist'], output_handle=sys.stdout)
     command('matrix', distance_matrix, ['input_profile', 'output', 'dist'])
+    sub = command('cross', cross, ['paired_input_profile', 'output', 'dist'])
+    sub.add_argument('--nearest', dest='nearest', metavar='N', type=int, default=None,
+                     help='write "left right distance" lines for the N closest right profiles of every left profile '
+                     'instead of the matrix')
     return parser
 
 
