@@ -312,10 +312,27 @@ int kpal_profile_distance_device(kpal_ctx *ctx, int k, const int64_t *dev_left, 
 /* ProfileDistance.dynamic_smooth(left, right), kdistlib.py:112-124: both vectors smoothed in place. */
 int kpal_dynamic_smooth(kpal_ctx *ctx, int k, int64_t *host_left_inout, int64_t *host_right_inout,
                         int summary, double threshold);
-/* kdistlib.distance_matrix values (kdistlib.py:179-186) for any option set: profiles are uploaded
- * (and balanced) once, every pair runs the option pipeline on the device. */
+/* kdistlib.distance_matrix values (kdistlib.py:179-186) for any option set: profiles are uploaded once and handed to
+ * kpal_profile_distance_matrix_device. */
 int kpal_profile_distance_matrix(kpal_ctx *ctx, int P, int k, const int64_t *const *host_profiles,
                                  const kpal_distance_options *opt, double *out_lower);
+/* The same values from P consecutive 16-byte aligned tables on the device, replacing the loop of dist.distance calls of
+ * kdistlib.py:179-186 (and the per-pair balance / get_scale / scale_down of kdistlib.py:136-157, metrics.py:49-86): every
+ * profile is balanced once; positive, scale (+- down) and prod / sum / euclidean / cosine run as rectangle kernels over the
+ * tiles on or below the diagonal, a number of launches that does not grow with P; plain options are
+ * kpal_distance_matrix_device.  With do_smooth the pair pipeline of kpal_profile_distance_device runs once per pair on the
+ * balanced tables (smoothed tables depend on both partners, kdistlib.py:53-124). */
+int kpal_profile_distance_matrix_device(kpal_ctx *ctx, int P, int k, const int64_t *dev_profiles /* P x 4^k */,
+                                        const kpal_distance_options *opt, double *out_lower);
+/* The rectangle of kpal_cross_distance for any option set: out[q * R + r] = ProfileDistance.distance(left[q], right[r])
+ * (kdistlib.py:126-161 per pair, with metrics.get_scale / scale_down of metrics.py:49-86 and the masks of metrics.positive,
+ * kdistlib.py:143-145, applied per pair on the device).  Launches as for kpal_profile_distance_matrix_device; plain options
+ * are kpal_cross_distance_device.  The sets may alias; the host variant uploads both through the context's scratch. */
+int kpal_cross_profile_distance(kpal_ctx *ctx, int k, int Q, const int64_t *const *host_left, int R,
+                                const int64_t *const *host_right, const kpal_distance_options *opt, double *out);
+int kpal_cross_profile_distance_device(kpal_ctx *ctx, int k, int Q, const int64_t *dev_left /* Q x 4^k */, int R,
+                                       const int64_t *dev_right /* R x 4^k */, const kpal_distance_options *opt,
+                                       double *out /* host, Q x R, row-major */);
 
 /* ---- profile summaries, merge, shrink ---- */
 /* Profile.total / non_zero / mean / median / std (kpal/klib.py:193-225) of one int64 vector in two

@@ -128,11 +128,16 @@ SIGNATURES = {
                                            ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, _f64p]),
     'kpal_cross_distance_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int,
                                                   ctypes.c_int, _f64p]),
+    'kpal_cross_profile_distance': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp), ctypes.c_int,
+                                                   ctypes.POINTER(_vp), _optp, _f64p]),
+    'kpal_cross_profile_distance_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, _optp,
+                                                          _f64p]),
     'kpal_profile_distance': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _optp, _f64p]),
     'kpal_profile_distance_device': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _optp, _f64p]),
     'kpal_dynamic_smooth': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_double]),
     'kpal_profile_distance_matrix': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp), _optp,
                                                     _f64p]),
+    'kpal_profile_distance_matrix_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _optp, _f64p]),
     'kpal_stats': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _statp]),
     'kpal_stats_device': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _statp]),
     'kpal_merge': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, _vp]),
@@ -666,6 +671,27 @@ class Context(object):
                                                   int(metric), int(bool(do_balance)), out.ctypes.data_as(_f64p)))
         return out
 
+    def cross_profile_distance(self, left, right, k, options):
+        """cross_distance for a DistanceOptions: [q, r] = ProfileDistance.distance(left[q], right[r]) (kdistlib.py:126-161)."""
+        la, ra = [_as_i64(p) for p in left], [_as_i64(p) for p in right]
+        for a in la + ra:
+            if a.size != 4 ** k:
+                raise ValueError('profile length %d != 4**%d' % (a.size, k))
+        Q, R = len(la), len(ra)
+        out = np.zeros((Q, R), dtype=np.float64)
+        lp = (_vp * Q)(*[a.ctypes.data for a in la])
+        rp = (_vp * R)(*[a.ctypes.data for a in ra])
+        _check(self._L.kpal_cross_profile_distance(self._h, int(k), Q, lp, R, rp, ctypes.byref(options),
+                                                   out.ctypes.data_as(_f64p)))
+        return out
+
+    def cross_profile_distance_device(self, k, Q, dev_left, R, dev_right, options):
+        """dev_left: Q consecutive tables, dev_right: R consecutive tables (device addresses) -> float64[Q, R]."""
+        out = np.zeros((int(Q), int(R)), dtype=np.float64)
+        _check(self._L.kpal_cross_profile_distance_device(self._h, int(k), int(Q), _vp(dev_left), int(R), _vp(dev_right),
+                                                          ctypes.byref(options), out.ctypes.data_as(_f64p)))
+        return out
+
     # -- ProfileDistance with options ------------------------------------------------------------
     def profile_distance(self, left, right, k, options):
         """ProfileDistance.distance for a DistanceOptions (kdistlib.py:126-161)."""
@@ -739,6 +765,13 @@ class Context(object):
         ptrs = (_vp * P)(*[a.ctypes.data for a in arrs])
         _check(self._L.kpal_profile_distance_matrix(self._h, P, int(k), ptrs, ctypes.byref(options),
                                                     out.ctypes.data_as(_f64p)))
+        return out
+
+    def profile_distance_matrix_device(self, P, k, dev_profiles, options):
+        """dev_profiles: P consecutive tables (device address) -> float64[P(P-1)/2] for a DistanceOptions."""
+        out = np.zeros(P * (P - 1) // 2, dtype=np.float64)
+        _check(self._L.kpal_profile_distance_matrix_device(self._h, int(P), int(k), _vp(dev_profiles), ctypes.byref(options),
+                                                           out.ctypes.data_as(_f64p)))
         return out
 
     # -- profiling ---------------------------------------------------------------------------

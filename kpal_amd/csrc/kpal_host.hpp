@@ -307,6 +307,9 @@ int quad2_finalize(kpal_ctx *ctx, bool balance);                          // kpa
 int quad2_resolve_fresh(kpal_ctx *ctx);                                   // kpal_quads2.hip: a FRESH piece whose lists overflowed is counted again (the fed buffer is read)
 int table_ready(kpal_ctx *ctx);                                           // kpal_quads2.hip: zeros materialised, pending finalisation done: the table is the table
 int launch_balance(kpal_ctx *ctx, int k, const int64_t *in, int64_t *out);   // kpal_vec.hip
+int check_options(const kpal_distance_options *opt);                       // kpal_vec.hip
+int profile_distance_pair(kpal_ctx *ctx, int k, const int64_t *dl, const int64_t *dr, const kpal_distance_options *opt, bool balanced,
+                          double *out);   // kpal_vec.hip: the option pipeline of one pair of 16-byte aligned device tables (balanced: do_balance is not applied again)
 int distance_matrix_core(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof, int metric, double *out_lower, bool allreduce,
                          int tiled = -1);   // kpal_vec.hip (tiled: -1 decided from n; 0 / 1 agreed between the ranks)
 namespace kpal { struct Partial; }   // vec_kernels.hpp

@@ -507,7 +507,7 @@ KPAL_API int kpal_distance_matrix(kpal_ctx *ctx, int P, int k, const int64_t *co
 // ----------------------------------------------------------------------------------------------
 // ProfileDistance with options (kdistlib.py:126-161)
 // ----------------------------------------------------------------------------------------------
-static int check_options(const kpal_distance_options *opt)
+int check_options(const kpal_distance_options *opt)
 {
     if (!opt) return set_err(KPAL_E_INVALID, "options are NULL");
     if (opt->metric < 0 || opt->metric > KPAL_COSINE) return set_err(KPAL_E_INVALID, "unknown metric %d", opt->metric);
@@ -556,8 +556,8 @@ static void launch_option_distance(kpal_ctx *ctx, unsigned grid, bool scaled, co
 
 // One pair, both vectors on the device and 16-byte aligned; `balanced`: the inputs are already
 // balanced (matrix path), so opt->do_balance is not applied again.
-static int profile_distance_pair(kpal_ctx *ctx, int k, const int64_t *dl, const int64_t *dr,
-                                 const kpal_distance_options *opt, bool balanced, double *out)
+int profile_distance_pair(kpal_ctx *ctx, int k, const int64_t *dl, const int64_t *dr, const kpal_distance_options *opt, bool balanced,
+                          double *out)
 {
     const uint64_t n = 1ULL << (2 * k);
     const bool do_balance = opt->do_balance && !balanced;
@@ -686,14 +686,9 @@ KPAL_API int kpal_profile_distance_matrix(kpal_ctx *ctx, int P, int k, const int
     for (int p = 0; p < P; ++p) {
         if (!host_profiles[p]) return set_err(KPAL_E_INVALID, "profile %d is NULL", p);
         HIPCHK(hipMemcpyAsync(prof + (uint64_t)p * n, host_profiles[p], n * 8, hipMemcpyHostToDevice, ctx->stream));
-        // balancing copies inside every pair (kdistlib.py:136-141) == balancing each profile once
-        if (opt->do_balance) CHK(launch_balance(ctx, k, prof + (uint64_t)p * n, prof + (uint64_t)p * n));
     }
-    for (int i = 1; i < P; ++i)
-        for (int j = 0; j < i; ++j)
-            CHK(profile_distance_pair(ctx, k, prof + (uint64_t)i * n, prof + (uint64_t)j * n, opt, true,
-                                      &out_lower[(size_t)i * (i - 1) / 2 + j]));
-    return KPAL_OK;
+    // uploaded once; balanced once per profile and every pair in a fixed number of launches there (kpal_cross.hip)
+    return kpal_profile_distance_matrix_device(ctx, P, k, prof, opt, out_lower);
 }
 
 // ----------------------------------------------------------------------------------------------

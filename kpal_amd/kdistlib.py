@@ -11,7 +11,8 @@ steps (kpal/kdistlib.py:143-157) and cosine similarity run on the device too
 a user-supplied callable cannot enter a kernel and keeps the reference's NumPy formulation.
 
 Beyond the reference: :func:`cross_distances` / :func:`cross_distance_matrix` / :func:`nearest` -- the Q x R rectangle of
-distances between a left and a right set of profiles (``kpal_cross_distance_device``), a fixed number of launches per chunk of the right side.
+distances between a left and a right set of profiles (``kpal_cross_distance_device``; with positive / scale / cosine
+``kpal_cross_profile_distance_device``), a fixed number of launches per chunk of the right side.
 """
 import numpy as np
 
@@ -267,13 +268,20 @@ def cross_distances(left_profiles, right_profiles, dist, max_bytes=None):
     reduction, a balance per profile with ``do_balance``, a second rectangle kernel when a fast form gives up on the values): the left tables stay resident,
     ``right_profiles`` -- any iterable, read once -- is taken in chunks of at most ``max_bytes`` of tables (default
     ``CROSS_MAX_BYTES``, never less than one table).  Tables that are consecutive in one device batch are used where they
-    lie.  Any other ``dist`` is ``dist.distance`` pair by pair."""
+    lie.  Any other ``dist`` made of built-ins -- positive, scale, cosine -- takes the same route through
+    ``kpal_cross_profile_distance_device``: each profile balanced once, the masks and the pairs' scale factors applied inside
+    the rectangle kernels (one totals pass, or one more rectangle pass for the masked totals of positive + scale), still a
+    fixed number of launches per chunk.  Dynamic smoothing is one call per chunk as well, but runs the pair pipeline once per
+    pair inside the library (smoothed tables depend on both partners).  A user-supplied callable, a non-numeric threshold,
+    mixed k or non-integer counts are ``dist.distance`` pair by pair."""
     left = list(left_profiles)
     if not left:
         raise ValueError('cross_distances needs at least one left profile')
     metric = dist._native_metric()
     k = left[0].length
-    fast = (dist._is_plain() and metric is not None and metric != _native.COSINE
+    plain = dist._is_plain() and metric is not None and metric != _native.COSINE
+    options = None if plain else dist._native_options()
+    fast = ((plain or options is not None)
             and all(p.length == k for p in left) and all(_integer_counts(p) for p in left))
     if not fast:
         right = list(right_profiles)
@@ -291,8 +299,11 @@ def cross_distances(left_profiles, right_profiles, dist, max_bytes=None):
                 continue
             rset = lset if (len(chunk) == len(left) and all(a is b for a, b in zip(chunk, left))) else _DeviceSet(ctx, chunk)
             try:
-                blocks.append(ctx.cross_distance_device(k, len(left), lset.ptr, len(chunk), rset.ptr, metric,
-                                                        do_balance=dist._do_balance))
+                if plain:
+                    blocks.append(ctx.cross_distance_device(k, len(left), lset.ptr, len(chunk), rset.ptr, metric,
+                                                            do_balance=dist._do_balance))
+                else:
+                    blocks.append(ctx.cross_profile_distance_device(k, len(left), lset.ptr, len(chunk), rset.ptr, options))
             finally:
                 if rset is not lset:
                     rset.release()
@@ -373,14 +384,14 @@ def _device_matrix(profiles, dist, metric):
         return None
     ctx, k, P = devs[0][0], profiles[0].length, len(profiles)
     table_bytes = 8 * 4 ** k
-    if not plain:        # the option kernels work pair by pair (balancing, positive, smoothing and scaling depend on the partner)
-        return [ctx.profile_distance_device(k, devs[i][1], devs[j][1], options) for i in range(1, P) for j in range(i)]
     base, gathered = devs[0][1], None
-    if any(devs[i][1] != base + i * table_bytes for i in range(P)):
-        gathered = base = ctx.alloc(P * table_bytes)
-        for i in range(P):
-            ctx.d2d(base + i * table_bytes, devs[i][1], table_bytes)
     try:
+        if any(devs[i][1] != base + i * table_bytes for i in range(P)):
+            gathered = base = ctx.alloc(P * table_bytes)
+            for i in range(P):
+                ctx.d2d(base + i * table_bytes, devs[i][1], table_bytes)
+        if not plain:    # one call: profiles balanced once, the partner-dependent steps inside the triangle kernels
+            return ctx.profile_distance_matrix_device(P, k, base, options)
         return ctx.distance_matrix_device(P, k, base, metric, do_balance=dist._do_balance)
     finally:
         if gathered is not None:

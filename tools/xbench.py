@@ -6,7 +6,11 @@ with the rectangle picked out (timed as a caller meets it -- allocation, the two
 triangle, the pick-out -- and, for the kernel-against-kernel comparison, the triangle call alone on an allocation gathered
 beforehand).  Host clock around synchronised calls, a warm-up, then --reps repeats of each.  Writes one
 JSON record (and prints it).
-    python tools/xbench.py --Q 16 --R 512 --k 10 [--metric prod] [--reps 10] [--reads 200000] [--out FILE]"""
+    python tools/xbench.py --Q 16 --R 512 --k 10 [--metric prod] [--reps 10] [--reads 200000] [--out FILE]
+With --options="-S --positive" (any of -b --positive -S -d, -D cosine|euclidean, -P sum): kpal_cross_profile_distance_device
+timed against one kpal_profile_distance_device call per pair -- what cross_distances did for such a distance before the
+rectangle took options -- in the same process on the same tables.
+    python tools/xbench.py --Q 64 --R 64 --k 12 --options=-S --out profiles/cross/xbench_options_k12_64x64_S.json"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -24,6 +28,7 @@ ap.add_argument('--reps', type=int, default=10)
 ap.add_argument('--pair-reps', type=int, default=None, help='repeats of the per-pair loop (default: --reps, fewer when one takes long)')
 ap.add_argument('--reads', type=int, default=200_000)
 ap.add_argument('--out', default=None)
+ap.add_argument('--options', default=None, help='time the option rectangle for this option set; write it as --options="-S --positive"')
 a = ap.parse_args()
 assert a.reps >= 10, 'at least ten repeats'
 ctx = _native.Context(0)
@@ -87,6 +92,57 @@ def concatenated():
 def triangle_alone():
     return ctx.distance_matrix_device(Q + R, a.k, both_kept, metric)
 
+
+def option_run():
+    op = argparse.ArgumentParser()
+    op.add_argument('-b', dest='do_balance', action='store_true')
+    op.add_argument('--positive', dest='do_positive', action='store_true')
+    op.add_argument('-S', dest='do_scale', action='store_true')
+    op.add_argument('-d', dest='down', action='store_true')
+    op.add_argument('-D', dest='function', default=None, choices=('euclidean', 'cosine'))
+    op.add_argument('-P', dest='pairwise', default='prod', choices=('prod', 'sum'))
+    o = op.parse_args(a.options.split())
+    code = {'euclidean': 2, 'cosine': 3}[o.function] if o.function else {'prod': 0, 'sum': 1}[o.pairwise]
+    options = _native.DistanceOptions(do_balance=int(o.do_balance), do_positive=int(o.do_positive), do_scale=int(o.do_scale),
+                                      down=int(o.down), metric=code)
+
+    def rectangle():
+        return ctx.cross_profile_distance_device(a.k, Q, dleft, R, dright, options)
+
+    def pair_loop():
+        out = np.empty((Q, R))
+        for q in range(Q):
+            for r in range(R):
+                out[q, r] = ctx.profile_distance_device(a.k, dleft + q * table, dright + r * table, options)
+        return out
+
+    got, t_rect = timed(rectangle, a.reps)
+    ctx.prof_enable(True); ctx.prof_reset()
+    rectangle()
+    kernels = {name: {'ms': ms, 'launches': cnt} for name, (ms, cnt) in ctx.prof_get().items() if cnt}
+    ctx.prof_enable(False)
+    want, t_pair = timed(pair_loop, a.pair_reps or a.reps)
+    with np.errstate(all='ignore'):
+        rel = np.abs(got - want) / np.where(want == 0, 1.0, np.abs(want))
+    same_kind = bool((np.isnan(got) == np.isnan(want)).all() and (got[np.isinf(want)] == want[np.isinf(want)]).all())
+    worst_rel = float(rel[np.isfinite(want)].max()) if np.isfinite(want).any() else 0.0
+    assert same_kind and worst_rel <= 2e-9, (same_kind, worst_rel)        # each is within 1e-9 of the reference's value
+    rec = {'tool': 'tools/xbench.py --options', 'src_sha': bench.source_sha(), 'k': a.k, 'Q': Q, 'R': R, 'options': a.options,
+           'reads_per_profile': a.reads, 'cross_profile_distance_device': t_rect, 'per_pair_loop': t_pair,
+           'median_below_per_pair_min': t_rect['median_ms'] < t_pair['min_ms'],
+           'speedup_median_over_per_pair_min': t_pair['min_ms'] / t_rect['median_ms'],
+           'table_bytes_read_once': (Q + R) * table, 'kernels_of_one_call': kernels, 'max_relative_difference': worst_rel}
+    text = json.dumps(rec, indent=1, sort_keys=True)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as fh:
+            fh.write(text + '\n')
+
+
+if a.options is not None:
+    option_run()
+    sys.exit(0)
 
 got, t_cross = timed(cross, a.reps)
 ctx.prof_enable(True); ctx.prof_reset()
