@@ -126,10 +126,15 @@ int kpal_fasta_flatten(kpal_ctx *ctx, const uint8_t *host_buf, size_t nbytes, ui
  * qual[i] - quality_offset < min_quality, and a quality byte below quality_offset or above '~' is malformed; min_quality < 0
  * (no mask) only length-checks the quality line.  quality_offset is 33 or 64; min_quality <= 93.
  * The text of one count may be cut ANYWHERE between the feeds of kpal_count_begin .. kpal_count_finish: the library carries the
- * unfinished record (in host memory) into the next FASTQ feed, and kpal_count_finish ends the text -- it tokenises what is left
- * with the options of the last FASTQ feed, and returns KPAL_E_INVALID if that is a cut-off record.  A malformed record makes the
- * feed (or the finish) return KPAL_E_INVALID with "malformed FASTQ record N: ..." (N 1-based over the count's text) in
- * kpal_last_error(); the count is abandoned then (the next call that needs it is KPAL_E_STATE until kpal_count_begin).
+ * unfinished record (in host memory) into the next FASTQ feed -- feeds of other kinds in between leave it alone -- and every call
+ * that takes the table for complete ENDS the text first: kpal_count_finish, kpal_count_balance, kpal_comm_reduce_table,
+ * kpal_comm_reduce_table_async and kpal_comm_reduce_scatter_table.  Ending the text tokenises and counts what is left with the
+ * options of the last FASTQ feed (the carried record takes the options of the later feed, not of the feed it began in), and
+ * returns KPAL_E_INVALID if that is a cut-off record.  A FASTQ feed after such a call begins a NEW text (nothing carried, records
+ * numbered from 1 again).  kpal_count_table is a plain accessor: it does not end the text, and the table it hands out lacks a
+ * record that is still carried.  A malformed record makes the feed (or the call that ends the text) return KPAL_E_INVALID with
+ * "malformed FASTQ record N: ..." (N 1-based over the count's text) in kpal_last_error(); the count is abandoned then (the next
+ * call that needs it is KPAL_E_STATE until kpal_count_begin).
  * The text goes to the device in 64 MiB chunks (KPAL_FASTA_CHUNK) by the pinned staging of the FASTA path; every chunk is
  * tokenised on the device (fastq_kernels.hpp) behind the carried rest of the chunk before, its status read back once, and counted
  * while the next chunk is copied and tokenised. */
@@ -174,7 +179,8 @@ int kpal_fasta_records_file_close(kpal_ctx *ctx);
 int kpal_count_finish(kpal_ctx *ctx, int64_t *host_out /* 4^k, or NULL to keep the result on the device */); /* klib.py:170 */
 /* Profile.balance (klib.py:285-298) on the count table in place, on the device: count + balance is the unit the
  * north-star metric is quoted on.  Call after the last feed, before kpal_count_finish (which then returns the balanced
- * counts).  For k >= 13 on the two-level quad pipeline the balance is fused into the pass that finalises the table
+ * counts).  An open FASTQ text is ended first, exactly as kpal_count_finish ends it (the carried last record is counted before
+ * the balance; a cut-off record is KPAL_E_INVALID and the count is abandoned).  For k >= 13 on the two-level quad pipeline the balance is fused into the pass that finalises the table
  * (one read and one write of the 4^k entries instead of two each); otherwise it is kpal_balance_device on the table. */
 int kpal_count_balance(kpal_ctx *ctx);
 /* Diagnostics (tests, A/B timing): the pipeline the last piece of the last feed actually took (a KPAL_STRATEGY_* value: AUTO
@@ -192,7 +198,7 @@ int kpal_count_last_plan(kpal_ctx *ctx, int *strategy, int *steps1, int *steps2)
  * values are written.  Synchronises the context's stream. */
 #define KPAL_COUNT_STATS 9
 int kpal_count_stats(kpal_ctx *ctx, uint64_t *out, int n);
-int kpal_count_table(kpal_ctx *ctx, void **dev_table, uint64_t *n_bins); /* device pointer of the int64 table (for the RCCL reduce) */
+int kpal_count_table(kpal_ctx *ctx, void **dev_table, uint64_t *n_bins); /* device pointer of the int64 table (for the RCCL reduce); a plain accessor: an open FASTQ text is NOT ended */
 
 /* Deterministic synthetic reads (same bytes as oracle/kpal_oracle.c
  * kpal_oracle_synth_reads): n_reads*(read_len+1) bytes, each read followed by '\n'. */
@@ -210,7 +216,9 @@ int kpal_synth_reads_device(kpal_ctx *ctx, uint64_t seed, uint64_t first_read, u
  *   every rank:  kpal_comm_init(ctx, lib, rank, world, id)
  *   per job:     kpal_count_begin / feed ...; kpal_comm_reduce_table(ctx, root, balance); kpal_count_finish(root's host buffer)
  * kpal_comm_reduce_table: ncclReduce(int64, sum) of the count table onto `root` and, if balance != 0, Profile.balance there -- all
- * queued on the context's stream, no host synchronisation.  kpal_comm_reduce_table_async: the same on a copy of the table and on a
+ * queued on the context's stream, no host synchronisation (except that a count fed FASTQ text has that text ended first, as by
+ * kpal_count_finish: the record still carried is counted, which reads one status word back; a cut-off record is KPAL_E_INVALID on
+ * that rank and nothing is reduced -- the same holds for the two calls below).  kpal_comm_reduce_table_async: the same on a copy of the table and on a
  * second stream, so that the next kpal_count_begin / feed overlaps it (throughput pipelines; two extra tables of HBM); the merged table
  * is then read with kpal_comm_merged_table (valid until the reduce after next, or until a kpal_count_begin that changes k or -- serial
  * form, where the merged table IS the count table -- starts the next count) after kpal_sync. */

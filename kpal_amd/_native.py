@@ -388,9 +388,11 @@ class Context(object):
         return out[:n.value].tobytes()
 
     def count_feed_fastq(self, buf, min_quality=None, quality_offset=33):
-        """buf: FASTQ text (bytes-like) cut anywhere -- the library carries an unfinished record into the next FASTQ feed and
-        ``count_finish`` ends the text; tokenised (and masked: bases whose quality is below ``min_quality``) and counted on the GPU.
-        A malformed record raises ValueError naming it."""
+        """buf: FASTQ text (bytes-like) cut anywhere -- the library carries an unfinished record into the next FASTQ feed (it takes
+        that feed's options) and ``count_finish``, ``count_balance``, ``comm_reduce_table`` and ``comm_reduce_scatter_table`` end
+        the text first: the carried record is counted, or -- cut off -- raises ValueError and abandons the count.  A FASTQ feed
+        after one of them begins a new text.  ``count_table`` does not end the text.  Tokenised (and masked: bases whose quality
+        is below ``min_quality``) and counted on the GPU.  A malformed record raises ValueError naming it."""
         a = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf, dtype=np.uint8)
         opt = _fastq_options(min_quality, quality_offset)
         if a.size:
@@ -398,7 +400,8 @@ class Context(object):
 
     def count_feed_fastq_file(self, path, begin=0, end=0, min_quality=None, quality_offset=33):
         """The bytes [begin, end) of a FASTQ file (end = 0: to its end), read by the library itself (parallel preads into its
-        pinned staging buffers), tokenised and counted on the GPU, chunks pipelined."""
+        pinned staging buffers), tokenised and counted on the GPU, chunks pipelined.  The range continues the text of the FASTQ
+        feeds before it (``count_feed_fastq``); an empty range (begin == end != 0) is a no-op."""
         opt = _fastq_options(min_quality, quality_offset)
         _check(self._L.kpal_count_feed_fastq_file(self._h, os.fsencode(path), int(begin), int(end), ctypes.byref(opt)))
 
@@ -425,13 +428,17 @@ class Context(object):
         return out
 
     def count_table(self):
+        """-> (device pointer, bins) of the count table.  A plain accessor: an open FASTQ text is not ended, so the table lacks a
+        record that is still carried."""
         p = _vp()
         n = ctypes.c_uint64(0)
         _check(self._L.kpal_count_table(self._h, ctypes.byref(p), ctypes.byref(n)))
         return p.value, n.value
 
     def count_balance(self):
-        """Profile.balance on the device count table, in place (fused into the finalisation of the table for k >= 13)."""
+        """Profile.balance on the device count table, in place (fused into the finalisation of the table for k >= 13).  An open
+        FASTQ text is ended first, as ``count_finish`` ends it: the record still carried is counted before the balance, a
+        cut-off record raises ValueError and abandons the count."""
         _check(self._L.kpal_count_balance(self._h))
 
     def count_last_plan(self):
@@ -536,7 +543,8 @@ class Context(object):
 
     def comm_reduce_table(self, root=0, balance=True, pipelined=False):
         """ONE ncclReduce(int64, sum) of the count tables onto ``root`` (+ Profile.balance there), queued on the
-        context's streams.  ``pipelined``: on a copy of the table and a second stream -- the next count overlaps it."""
+        context's streams.  ``pipelined``: on a copy of the table and a second stream -- the next count overlaps it.  An open
+        FASTQ text is ended first, as ``count_finish`` ends it (ValueError on a cut-off record, nothing reduced)."""
         fn = self._L.kpal_comm_reduce_table_async if pipelined else self._L.kpal_comm_reduce_table
         _check(fn(self._h, int(root), int(bool(balance))))
 
@@ -548,7 +556,8 @@ class Context(object):
 
     def comm_reduce_scatter_table(self, balance=False):
         """The bin-range merge: ONE ncclReduceScatter leaves this rank its range of the merged table (in place), balanced through
-        one all-to-all of the mirrored entries when asked (power-of-two worlds)."""
+        one all-to-all of the mirrored entries when asked (power-of-two worlds).  An open FASTQ text is ended first, as
+        ``count_finish`` ends it."""
         _check(self._L.kpal_comm_reduce_scatter_table(self._h, int(bool(balance))))
 
     def comm_gather_table(self):

@@ -994,9 +994,12 @@ static int fastq_feed(kpal_ctx *ctx, FaSource &src, const FqMask &m)
     return rc;
 }
 
-// kpal_count_finish: the end of the FASTQ text -- the record the last feed left unfinished is tokenised and counted, or is an error.
-static int fastq_end(kpal_ctx *ctx)
+// The end of the count's text (kpal_count_finish, kpal_count_balance, the kpal_comm_reduce_* calls: everything that takes the table
+// for complete): the record the last FASTQ feed left unfinished is tokenised and counted, or is an error that abandons the count.
+// A no-op without a FASTQ feed since kpal_count_begin (or since the last end); a FASTQ feed afterwards begins a new text.
+int count_end_text(kpal_ctx *ctx)
 {
+    if (!ctx->fq_open) return KPAL_OK;
     int rc = KPAL_OK;
     if (!ctx->fq_carry.empty()) {
         FaSource src;
@@ -1359,7 +1362,7 @@ KPAL_API int kpal_count_finish(kpal_ctx *ctx, int64_t *host_out)
 {
     CTX_ENTER(ctx);
     if (!ctx->counting) return set_err(KPAL_E_STATE, "kpal_count_finish before kpal_count_begin");
-    if (ctx->fq_open) CHK(fastq_end(ctx));   // the end of a FASTQ text: its last record
+    CHK(count_end_text(ctx));   // the end of a FASTQ text: its last record
     CHK(table_ready(ctx));
     uint32_t pool_error = 0, quad_error = 0;
     if (ctx->chunk_error_armed)
@@ -1385,6 +1388,7 @@ KPAL_API int kpal_count_balance(kpal_ctx *ctx)
 {
     CTX_ENTER(ctx);
     if (!ctx->counting) return set_err(KPAL_E_STATE, "kpal_count_balance before kpal_count_begin");
+    CHK(count_end_text(ctx));   // (a FASTQ record still carried belongs to the table that is balanced)
     // two-level quad pipeline: the pending finalisation of the table balances it in the same pass
     if (ctx->finalize_pending) return quad2_finalize(ctx, true);
     CHK(table_ready(ctx));

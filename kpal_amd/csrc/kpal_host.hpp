@@ -138,11 +138,11 @@ struct kpal_ctx {
     DevBuf fq_raw[2], fq_flat[2], fq_meta, fq_pos, fq_status;
     unsigned long long *fq_status_host = nullptr;
     hipEvent_t fq_ev = nullptr;
-    // ... and the record a count's last FASTQ feed left unfinished (kpal_count_finish ends it), with that feed's mask options
+    // ... and the record a count's last FASTQ feed left unfinished (count_end_text ends it), with that feed's mask options
     std::vector<uint8_t> fq_carry;
     uint64_t fq_records = 0;                 // records of this count finished so far (error messages name record fq_records + r + 1)
     int fq_min_quality = -1, fq_offset = 33;
-    bool fq_open = false;                    // a FASTQ feed happened since kpal_count_begin: kpal_count_finish ends the text
+    bool fq_open = false;                    // a FASTQ feed happened since kpal_count_begin or the last end of the text: count_end_text ends it
     std::vector<void *> host_allocs;         // kpal_host_alloc buffers still owned by callers (released with the context at the latest)
     size_t fa_chunk = kStage;                // text bytes per chunk (KPAL_FASTA_CHUNK: tests put the seams everywhere)
     // host-feed staging
@@ -305,6 +305,7 @@ double quad_expected_backlog(const std::vector<double> &mu, int slots);   // kpa
 constexpr double kQuadBacklogMax = 1500.0;   // quad_choose_steps: expected steady-state backlog a tile size may bring (list: 2048)
 int quad2_finalize(kpal_ctx *ctx, bool balance);                          // kpal_quads2.hip: no-op unless a finalisation is pending
 int quad2_resolve_fresh(kpal_ctx *ctx);                                   // kpal_quads2.hip: a FRESH piece whose lists overflowed is counted again (the fed buffer is read)
+int count_end_text(kpal_ctx *ctx);                                        // kpal_count.hip: an open FASTQ text is ended (its carried record counted, or the count abandoned)
 int table_ready(kpal_ctx *ctx);                                           // kpal_quads2.hip: zeros materialised, pending finalisation done: the table is the table
 int launch_balance(kpal_ctx *ctx, int k, const int64_t *in, int64_t *out);   // kpal_vec.hip
 int check_options(const kpal_distance_options *opt);                       // kpal_vec.hip

@@ -161,6 +161,7 @@ KPAL_API int kpal_comm_reduce_table(kpal_ctx *ctx, int root, int balance)
     if (!ctx->counting) return set_err(KPAL_E_STATE, "kpal_comm_reduce_table before kpal_count_begin");
     if (!ctx->comm) return set_err(KPAL_E_STATE, "no communicator (kpal_comm_init)");
     if (root < 0 || root >= ctx->comm_world) return set_err(KPAL_E_INVALID, "root %d not in 0..%d", root, ctx->comm_world - 1);
+    CHK(count_end_text(ctx));   // (a FASTQ record still carried belongs to the table that is reduced)
     CHK(table_ready(ctx));   // the complete, unbalanced table goes on the wire
     {
         ProfScope ps_(ctx, "rccl_reduce");
@@ -223,6 +224,7 @@ KPAL_API int kpal_comm_reduce_table_async(kpal_ctx *ctx, int root, int balance)
     if (!ctx->counting) return set_err(KPAL_E_STATE, "kpal_comm_reduce_table_async before kpal_count_begin");
     if (!ctx->comm) return set_err(KPAL_E_STATE, "no communicator (kpal_comm_init)");
     if (root < 0 || root >= ctx->comm_world) return set_err(KPAL_E_INVALID, "root %d not in 0..%d", root, ctx->comm_world - 1);
+    CHK(count_end_text(ctx));   // (a FASTQ record still carried belongs to the table that is reduced)
     CHK(table_ready(ctx));
     HipCommRuntime rt{ctx};
     CommPipeState st;
@@ -317,6 +319,7 @@ KPAL_API int kpal_comm_reduce_scatter_table(kpal_ctx *ctx, int balance)
         return set_err(KPAL_E_HIP, "this RCCL library lacks ncclReduceScatter / ncclSend / ncclRecv");
     RangeIndex R{0, 0};
     CHK(comm_range_geometry(ctx, R));
+    CHK(count_end_text(ctx));   // (a FASTQ record still carried belongs to the table that is reduced)
     CHK(table_ready(ctx));
     const uint32_t W = (uint32_t)ctx->comm_world, r = (uint32_t)ctx->comm_rank;
     const uint64_t n1 = R.range_bins(), n2 = R.pair_bins();

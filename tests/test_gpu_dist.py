@@ -90,6 +90,18 @@ def test_library_rccl_world_1():
     assert 'RCCL_LIBRARY_OK' in out
 
 
+def test_library_rccl_world_1_ends_a_fastq_text():
+    """kpal_comm_reduce_table (serial, pipelined) and kpal_comm_reduce_scatter_table with balance = 1 on a count whose FASTQ
+    text lacks its final newline (world size 1): the carried last record is counted before the reduce, so the merged table
+    is oracle.balance(oracle.from_sequences(reads)); a cut-off record makes the reduce raise ValueError.  In a child
+    process, as test_library_rccl_world_1."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'rccl_fastq_reduce_check.py')],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    out = p.stdout.decode()
+    assert p.returncode == 0, out[-3000:]
+    assert 'RCCL_FASTQ_REDUCE_OK' in out
+
+
 def test_bench_multi_gpu_code_path_on_one_gpu():
     """The N > 1 code of bench.py -- rank supervisor, worker process, the library's RCCL communicator and torch.distributed's,
     the three reduce modes (pipelined / serial in-library reduce, torch reduce) each timed with its own warm-up and steps, the

@@ -1,5 +1,5 @@
 """FASTQ ingest on the device (kpal_count_feed_fastq / _file / kpal_fastq_flatten, Profile.from_fastq, ``kpal count --fastq``)
-against an independent restatement of the format rules (four-line records, CR before LF dropped, roles by line index mod 4,
+against an independent restatement of the format rules (tests/fastq_cases.py: four-line records, CR before LF dropped, roles by line index mod 4,
 length check, optional quality mask, trailing empty lines ignored, malformed records refused) and the oracle's counts.  The
 reference reads FASTA only, so the rules are the specification.  Run on the GPU box: pytest -m gpu."""
 import gzip
@@ -12,59 +12,11 @@ import pytest
 
 import memh5
 import oracle
+from fastq_cases import Malformed, Ragged, fastq_reads, flat_of, random_fastq
 
 pytestmark = pytest.mark.gpu
 
 KS = (1, 3, 8, 12, 13)
-
-
-class Malformed(Exception):
-    def __init__(self, record):
-        super().__init__(record)
-        self.record = record
-
-
-def fastq_reads(data, min_quality=None, offset=33):
-    """The reads of a FASTQ text by the rules (written independently of kpal_amd.klib): the sequence lines, masked bases as
-    'N'.  Raises Malformed(1-based number of the first bad record)."""
-    pieces = data.split(b'\n')
-    lines = [p[:-1] if i < len(pieces) - 1 and p.endswith(b'\r') else p for i, p in enumerate(pieces)]
-    last = max([i for i, line in enumerate(lines) if line] or [-1])
-    reads = []
-    for r in range((last + 4) // 4):
-        rec = lines[4 * r:4 * r + 4]
-        if not rec[0].startswith(b'@') or len(rec) < 4 or not rec[2].startswith(b'+') or len(rec[3]) != len(rec[1]):
-            raise Malformed(r + 1)
-        seq, qual = bytearray(rec[1]), rec[3]
-        if min_quality is not None:
-            for i, q in enumerate(qual):
-                if q < offset or q > 126:
-                    raise Malformed(r + 1)
-                if q - offset < min_quality:
-                    seq[i] = ord('N')
-        reads.append(bytes(seq))
-    return reads
-
-
-def flat_of(reads):
-    return b''.join(b'\n' + r for r in reads)
-
-
-def random_fastq(rnd, n, max_len=300, crlf=False, offset=33, noise=True):
-    """n records: titles and quality lines that begin with '@' or '+', empty reads, non-ACGT bytes, mixed or CRLF line ends."""
-    out = []
-    for i in range(n):
-        eol = b'\r\n' if crlf or (noise and rnd.random() < 0.1) else b'\n'
-        length = 0 if rnd.random() < 0.05 else rnd.randint(1, max_len)
-        alphabet = b'ACGTACGTACGTacgtN' + (b'@+.- \t>' if noise else b'')
-        seq = bytes(rnd.choice(alphabet) for _ in range(length))
-        qual = bytes(rnd.randint(offset, 126) for _ in range(length))
-        if length and offset == 33 and rnd.random() < 0.2:
-            qual = bytes([rnd.choice(b'@+')]) + qual[1:]
-        title = b'@' + rnd.choice([b'', b'read%d' % i, b'@@x +y', b'+plus'])
-        sep = rnd.choice([b'+', b'+' + title[1:]])
-        out.append(title + eol + seq + eol + sep + eol + qual + eol)
-    return b''.join(out)
 
 
 def texts_for(seed):
@@ -101,19 +53,6 @@ def test_flatten_matches_restatement(monkeypatch):
             for mq in (None, 20):
                 want = flat_of(fastq_reads(text, mq))
                 assert c.fastq_flatten(text, min_quality=mq) == want, (chunk, t, mq)
-
-
-class Ragged(object):
-    """A binary handle whose reads return pieces of random length (1 byte .. a few KiB)."""
-
-    def __init__(self, data, seed):
-        self._data, self._at, self._rnd = data, 0, random.Random(seed)
-
-    def read(self, n=-1):
-        take = self._rnd.choice([1, 2, 3, 7, 64, 333, 4096])
-        piece = self._data[self._at:self._at + take]
-        self._at += len(piece)
-        return piece
 
 
 def test_counts_every_path(tmp_path, ctx):
