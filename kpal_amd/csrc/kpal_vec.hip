@@ -598,6 +598,10 @@ int profile_distance_pair(kpal_ctx *ctx, int k, const int64_t *dl, const int64_t
         if (tl < tr) ls = (double)tr / (double)tl;
         else rs = (double)tl / (double)tr;
         if (opt->down) {   // metrics.scale_down, metrics.py:75-86
+            // Python's max(left, right) keeps `left` unless right > left; this keeps `rs` unless ls > rs.  The operand kept
+            // differs only when a factor is NaN (totals 0 == 0), and then every metric is NaN whichever it is: the G13 cases
+            // totals_k1_vboth_zero, totals_k2_vboth_zero and totals_k4_vboth_zero (tests/golden/option_edges.json) pin NaN
+            // with and without `down`.
             const double top = ls > rs ? ls : rs;
             ls /= top;
             rs /= top;

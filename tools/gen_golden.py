@@ -16,10 +16,12 @@ merger and Profile.shrink (kpal/klib.py:193-225,269-283,329-352); G11 pins the c
 row a14 (kmer.count/merge/balance/get_balance/get_stats/distance/distance_matrix) through real HDF5
 files; G12 pins the command line: kpal.kmer.main([...]) for every sub-command on the tutorial files
 (kpal/kmer.py:703-975) -- stdout / text outputs, the stored counts (sha256), dataset and file attributes,
-and the usage errors.  Only DATA is written: inputs and the reference's outputs.
+and the usage errors; G13 pins the pair pipeline (smoothing, scaling, positive) at value and threshold edges on the cases of
+tests/option_cases.py.  Only DATA is written: inputs and the reference's outputs.
 
     ... tools/gen_golden.py            # everything
     ... tools/gen_golden.py g12        # only tests/golden/cli.json
+    ... tools/gen_golden.py g13        # only tests/golden/option_edges.json and option_edges.npz
 """
 from __future__ import print_function
 
@@ -442,6 +444,82 @@ def g10(arrays):
     return {'n': len(vecs), 'cases': cases, 'merges': merges}
 
 
+def enc(x):
+    """A float for JSON: non-finite values as the strings float() reads back."""
+    x = float(x)
+    return x if np.isfinite(x) else ('nan' if np.isnan(x) else ('inf' if x > 0 else '-inf'))
+
+
+def write_npz(path, arrays):
+    """np.savez_compressed with fixed member times and order, so that the same arrays give the same bytes."""
+    with zipfile.ZipFile(path, 'w', zipfile.ZIP_DEFLATED) as z:
+        for name in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[name]), allow_pickle=False)
+            info = zipfile.ZipInfo(name + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+
+
+def g13(arrays):
+    """The pair pipeline at value and threshold edges: the cases of tests/option_cases.py (ties of every summary function at
+    every level, collapse at the root / nowhere / at each depth, sums near 2^53 and 2^62, negative counts, zero / equal /
+    wrapping totals, k = 1 and 2) through ProfileDistance.dynamic_smooth and .distance (kdistlib.py:53-161)."""
+    sys.path.insert(0, os.path.join(HERE, '..', 'tests'))
+    import option_cases
+    summaries = {'min': metrics.summary['min'], 'average': metrics.summary['average'], 'median': metrics.summary['median']}
+    dist_funcs = {'prod': None, 'sum': None, 'euclidean': metrics.vector_distance['euclidean'],
+                  'cosine': metrics.vector_distance['cosine']}
+
+    def distance(left, right, o):
+        d = kdistlib.ProfileDistance(
+            do_balance=o['do_balance'], do_positive=o['do_positive'], do_smooth=o.get('do_smooth', False),
+            summary=summaries[o.get('summary', 'min')], threshold=o.get('threshold', 0), do_scale=o['do_scale'], down=o['down'],
+            distance_function=dist_funcs[o['metric']],
+            pairwise=metrics.pairwise[o['metric'] if o['metric'] in ('prod', 'sum') else 'prod'])
+        with np.errstate(all='ignore'):
+            return enc(d.distance(left, right))
+
+    rs = np.random.RandomState(13)
+    odd = [-1.5, float('inf'), float('nan'), 1e300]
+    grid = option_cases.GRID
+    cases, inputs, changed = [], [], {'idx': [], 'l': [], 'r': []}
+    for ci, case in enumerate(option_cases.golden_cases()):
+        l, r = case.left, case.right
+        rec_at = sum(v.size for v in inputs)             # both vectors, left first, at this offset of 'g13_inputs'
+        inputs.extend([l, r])
+        left, right = klib.Profile(l.copy(), 'l'), klib.Profile(r.copy(), 'r')
+        rec = {'name': case.name, 'kind': case.kind, 'k': case.k, 'args': case.args, 'summary': case.summary,
+               'threshold': enc(case.threshold), 'at': rec_at, 'smoothed': [], 'plain': [], 'smooth': [], 'extra': []}
+        for si, (fn, th) in enumerate(option_cases.smooth_settings(case)):
+            a, b = left.copy(), right.copy()
+            with np.errstate(all='ignore'):
+                kdistlib.ProfileDistance(do_smooth=True, summary=summaries[fn], threshold=th).dynamic_smooth(a, b)
+            idx = np.nonzero((a.counts != l) | (b.counts != r))[0]      # stored as the bins that changed
+            rec['smoothed'].append([fn, enc(th), sum(v.size for v in changed['idx']), int(idx.size)])   # offset, count in 'g13_changed_*'
+            changed['idx'].append(idx.astype('int32'))
+            changed['l'].append(np.asarray(a.counts, dtype='int64')[idx])
+            changed['r'].append(np.asarray(b.counts, dtype='int64')[idx])
+        with np.errstate(all='ignore'):
+            rec['scale'] = [enc(x) for x in metrics.get_scale(l, r)]
+        picks = list(range(len(grid))) if option_cases.full_grid(case) else sorted(rs.choice(len(grid), 16, replace=False).tolist())
+        for gi in picks:
+            rec['plain'].append([gi, distance(left, right, grid[gi])])
+        picks = list(range(len(grid))) if option_cases.full_grid(case) else sorted(rs.choice(len(grid), 16, replace=False).tolist())
+        for gi in picks:
+            rec['smooth'].append([gi, distance(left, right, dict(grid[gi], do_smooth=True, summary=case.summary, threshold=case.threshold))])
+        for _ in range(3):
+            gi, fn, th = int(rs.randint(len(grid))), option_cases.SUMMARIES[rs.randint(3)], odd[rs.randint(len(odd))]
+            rec['extra'].append([gi, fn, enc(th), distance(left, right, dict(grid[gi], do_smooth=True, summary=fn, threshold=th))])
+        assert (left.counts == l).all() and (right.counts == r).all()
+        cases.append(rec)
+    arrays['g13_inputs'] = np.concatenate(inputs)
+    for key, parts in changed.items():
+        arrays['g13_changed_' + key] = np.concatenate(parts)
+    return {'grid': grid, 'cases': cases}
+
+
 def g11():
     """The callers of SURVEY.md 8 row a14 -- kmer.count / merge / balance / get_balance / get_stats /
     distance / distance_matrix (kpal/kmer.py:112-271,541-700) -- on the tutorial FASTA files through
@@ -680,6 +758,13 @@ def main():
     arrays = {}
     meta = {'generator': 'tools/gen_golden.py', 'reference': 'kPAL 2.1.2.dev (/root/reference)',
             'python': sys.version.split()[0], 'numpy': np.__version__}
+    if sys.argv[1:] == ['g13']:
+        edge_arrays = {}
+        with open(os.path.join(OUT, 'option_edges.json'), 'w') as fh:
+            json.dump({'meta': meta, 'G13': g13(edge_arrays)}, fh, indent=0, sort_keys=True)
+        write_npz(os.path.join(OUT, 'option_edges.npz'), edge_arrays)
+        print('wrote option_edges.json, option_edges.npz')
+        return
     if sys.argv[1:] == ['g12']:
         with open(os.path.join(OUT, 'cli.json'), 'w') as fh:
             json.dump({'meta': meta, 'G12': g12()}, fh, indent=0)
@@ -705,6 +790,10 @@ def main():
         json.dump({'meta': meta, 'G11': g11()}, fh, indent=0)
     with open(os.path.join(OUT, 'cli.json'), 'w') as fh:
         json.dump({'meta': meta, 'G12': g12()}, fh, indent=0)
+    edge_arrays = {}
+    with open(os.path.join(OUT, 'option_edges.json'), 'w') as fh:
+        json.dump({'meta': meta, 'G13': g13(edge_arrays)}, fh, indent=0, sort_keys=True)
+    write_npz(os.path.join(OUT, 'option_edges.npz'), edge_arrays)
     print('wrote', sorted(os.listdir(OUT)))
 
 
