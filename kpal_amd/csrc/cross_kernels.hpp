@@ -1,35 +1,61 @@
-// cross_kernels.hpp -- the Q x R rectangle of distances between two SETS of profiles (kpal_cross_distance[_device]).
-// The triangle kernels of vec_kernels.hpp take one base pointer and walk a list of lower-triangle tiles; these take a
-// left set (rows) and a right set (columns) in separate allocations and cover every tile of the rectangle, so no pair
-// inside one set is ever evaluated.  The arithmetic is the triangle's (matrix_accumulate, matrix_accumulate_prod_rcp,
-// rcp_counts, the byte-counter term counts); only the addressing, the masks and the partial layout are new.
-//   cross_tile_kernel    4 x 4 register tiles straight from global memory: few queries (Q <= 4 or R <= 4: the long side
-//                        streams past once, the short side's bins stay in the caches) and k < 6
-//   cross_super_kernel   16 x 16 super-tiles staged through LDS, any values (the fallback of the two below, and euclidean
-//                        where the Gram form does not apply)
-//   cross_recip_kernel<0> multiset 'prod' as a difference of reciprocals, counts in [0, 2^16)   (matrix_rdiff_kernel's form)
-//   cross_recip_kernel<1> multiset 'sum' with the reciprocal of the denominator from a table     (matrix_rsum_kernel's form)
-//   cross_gram_kernel    euclidean from A . B^T on the fp64 matrix cores plus the norms of cross_norm_kernel, exact while
-//                        every |x|^2 < 2^53
-// Partials of the first four: slot ((i / 4) * sideR + j / 4) * 16 + (i % 4) * 4 + j % 4 of pair (left i, right j), sideR =
-// ceil(R / 4), `ngroups` workgroup partials per slot -- reduced in a fixed order by reduce_partials_kernel.  Rows past the
-// end of a set are masked (their address is clamped to the last profile, their results are never written).
+// cross_kernels.hpp -- every pair (left i, right j) of two SETS of profiles: the Q x R rectangle of kpal_cross_distance[_device]
+// and, with CrossSets::tri, the lower triangle of one set against itself (kdistlib.distance_matrix, kpal/kdistlib.py:179-186:
+// kpal_distance_matrix[_device]).  One set of kernels serves both -- the triangle is a set crossed with itself of which only
+// the tiles on or below the diagonal exist -- and both kinds of arithmetic: the plain metrics (PlainAcc below) and every
+// ProfileDistance with options (OptAcc, cross_option_kernels.hpp) are accumulators plugged into the same two skeletons.
+//   cross_tile_kernel     4 x 4 register tiles straight from global memory: few profiles on a side (the long side streams
+//                         past once, the short side's bins stay in the caches) and k < 6
+//   cross_super_kernel    16 x 16 super-tiles staged through LDS, any values (the fallback of the two below, and euclidean
+//                         where the Gram form does not apply)
+//   cross_recip_kernel<0> multiset 'prod' as a difference of reciprocals, counts in [0, 2^16)
+//   cross_recip_kernel<1> multiset 'sum' with the reciprocal of the denominator from a table
+//   cross_gram_kernel     euclidean from A . B^T on the fp64 matrix cores plus the norms of cross_norm_kernel, exact while
+//                         every |x|^2 < 2^53 (rectangle only; the triangle's is gram_kernels.hpp)
+// Tiles: tile (ti, tj) of 4 x 4 pairs has number ti * sideR + tj, sideR = ceil(R / 4), or -- tri, tj <= ti -- ti (ti + 1) / 2 + tj;
+// super-tiles of 16 x 16 pairs likewise.  The number is computed from the block id: no list of tiles is uploaded.
+// Partials of the first four: accumulator a of pair (i, j) lies at (a * slots + cross_slot(i, j)) * ngroups + group, slots =
+// 16 * tiles, `ngroups` workgroup partials per slot -- reduced in a fixed order by reduce_partials_kernel.  Rows past the end
+// of a set are masked (their address is clamped to the last profile, their results are never written); so are, in a
+// triangle, the tiles above the diagonal.
 #pragma once
-#include "vec_kernels.hpp"
+#include "matrix_common.hpp"
 #include "gram_kernels.hpp"
 
 namespace kpal {
 
-struct CrossSets {
-    const int64_t *left;    // Q x n
-    const int64_t *right;   // R x n
-    int Q, R;
-    uint64_t n;
+// What a kernel of the two skeletons is launched with; the plain accumulators read `c` alone.
+struct CrossOpt {
+    CrossSets c;
+    int down;                // metrics.scale_down
+    const Partial *totals;   // SCALED: reduced totals (.m), per profile (left 0 .. Q-1, right from `roff`) or per pair slot
+    uint32_t roff;
+    uint32_t slots;          // 16 * tiles: the stride between the accumulators of one pair
 };
 
-__device__ __forceinline__ uint64_t cross_slot(int sideR, int i, int j)
+// Number t of a tile (or super-tile) -> (ti, tj): row-major over `side` columns, or the lower triangle's ti (ti + 1) / 2 + tj.
+__device__ __forceinline__ void cross_tile(uint32_t t, int side, bool tri, int &ti, int &tj)
 {
-    return ((uint64_t)(i >> 2) * (uint64_t)sideR + (uint64_t)(j >> 2)) * 16u + (uint64_t)((i & 3) * 4 + (j & 3));
+    if (!tri) {
+        ti = (int)(t / (uint32_t)side);
+        tj = (int)(t % (uint32_t)side);
+        return;
+    }
+    uint32_t i = (uint32_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while ((i + 1u) * (i + 2u) / 2u <= t) ++i;
+    while (i * (i + 1u) / 2u > t) --i;
+    ti = (int)i;
+    tj = (int)(t - i * (i + 1u) / 2u);
+}
+
+__device__ __forceinline__ uint32_t cross_tile_number(int ti, int tj, int side, bool tri)
+{
+    return tri ? (uint32_t)ti * ((uint32_t)ti + 1u) / 2u + (uint32_t)tj : (uint32_t)ti * (uint32_t)side + (uint32_t)tj;
+}
+
+// Slot of pair (i, j) among the 16 * tiles of one accumulator.
+__device__ __forceinline__ uint64_t cross_slot(const CrossSets &c, int sideR, int i, int j)
+{
+    return (uint64_t)cross_tile_number(i >> 2, j >> 2, sideR, c.tri != 0) * 16u + (uint64_t)((i & 3) * 4 + (j & 3));
 }
 
 // Staged row r of super-tile (si, sj): rows 0..15 are left profiles, 16..31 right ones.
@@ -38,96 +64,139 @@ __device__ __forceinline__ const int64_t *cross_row(const CrossSets &c, int si, 
     return r < 16 ? c.left + (uint64_t)min(si * 16 + r, c.Q - 1) * c.n : c.right + (uint64_t)min(sj * 16 + (r - 16), c.R - 1) * c.n;
 }
 
-// The 1-D grid of the staged kernels, cut like matrix_rdiff_kernel's: the `nsuper` workgroups that stage the SAME bins are
-// neighbours on ONE XCD (the left rows of a bin range are then read from HBM once per XCD and hit its L2 afterwards).
-// Linear id L = (c * nsuper + s) * 8 + x  ->  super-tile s, bin-group c * 8 + x; the host launches nsuper * a multiple of 8.
+// The 1-D grid of the staged kernels.  Every profile is staged by several super-tiles (64 profiles in a triangle: 10
+// super-tiles x 32 rows = 5 x the profiles' bytes, 43 GB at k = 12 -- more than the arithmetic takes).  Workgroups are
+// dispatched round-robin over the 8 XCDs, each with its own L2: the grid is cut so that the `nsuper` workgroups that stage the
+// SAME bins are neighbours on ONE XCD -- linear id L = (c * nsuper + s) * 8 + x  ->  super-tile s, bin-group c * 8 + x -- and the
+// second to tenth reader of a line hits that L2.  The host launches nsuper * a multiple of 8 workgroups.
 struct CrossBlock {
     int si, sj;
     uint32_t group, ngroups;
 };
-__device__ __forceinline__ CrossBlock cross_block(uint32_t nsuper, int superR)
+__device__ __forceinline__ CrossBlock cross_block(const CrossSets &c, uint32_t nsuper, int superR)
 {
     const uint32_t lin = blockIdx.x, xcd = lin & 7u, sidx = (lin >> 3) % nsuper, cgrp = (lin >> 3) / nsuper;
-    return CrossBlock{(int)(sidx / (uint32_t)superR), (int)(sidx % (uint32_t)superR), cgrp * 8u + xcd, gridDim.x / nsuper};
+    CrossBlock blk = {0, 0, cgrp * 8u + xcd, gridDim.x / nsuper};
+    cross_tile(sidx, superR, c.tri != 0, blk.si, blk.sj);
+    return blk;
 }
 
-// blockIdx.x = tile * gx + slice: tile (tq, tr) of 4 x 4 pairs, the slices stride over the bins.
-template <int METRIC>
-__global__ __launch_bounds__(256) void cross_tile_kernel(const CrossSets c, uint32_t gx, Partial *__restrict__ partials)
+// The tile of group g (16 lanes, one 4 x 4 register tile) of a staged workgroup: (4 si + g / 4, 4 sj + g % 4).  A group whose
+// tile lies outside the rectangle, or above the diagonal of a triangle, only helps with the staging.
+struct CrossGroup {
+    int ti, tj, sideR;
+    bool mine;
+};
+__device__ __forceinline__ CrossGroup cross_group(const CrossSets &c, const CrossBlock &blk, int g)
 {
-    constexpr int TILE = 4;
-    const int sideR = (c.R + TILE - 1) / TILE;
-    const uint32_t tile = blockIdx.x / gx, slice = blockIdx.x % gx;
-    const int tq = (int)(tile / (uint32_t)sideR), tr = (int)(tile % (uint32_t)sideR);
-    double s[TILE][TILE];
-    unsigned long long m[TILE][TILE];
-    uint32_t mf[TILE][TILE];
+    const int ti = blk.si * 4 + (g >> 2), tj = blk.sj * 4 + (g & 3);
+    const int sideQ = (c.Q + 3) / 4, sideR = (c.R + 3) / 4;
+    return CrossGroup{ti, tj, sideR, ti < sideQ && tj < sideR && (!c.tri || tj <= ti)};
+}
+
+// The plain metrics (0 / 1: multiset prod / sum, metrics.py:121-123; 2: euclidean as a wrapping int64 dot, metrics.py:135,46)
+// as an accumulator of the two skeletons.  An accumulator says how many (s, m) pairs it writes per pair of profiles (NACC),
+// whether the staged skeleton should stage the reciprocals 1 / (x + 1) beside the values (RCP: 'prod' then takes
+// matrix_accumulate_prod_rcp), and what a pair's (s, m) is once the bins are through.
+template <int METRIC>
+struct PlainAcc {
+    static constexpr int NACC = 1;
+    static constexpr bool RCP = METRIC == 0;
+    double s[4][4];
+    unsigned long long m[4][4];   // the euclidean dots
+    uint32_t mf[4][4];            // multiset: number of terms (a thread sees fewer than 2^32 bins)
+    TermBytes<4> tb;
+
+    __device__ __forceinline__ void begin(const CrossOpt &, int, int, uint32_t)
+    {
 #pragma unroll
-    for (int a = 0; a < TILE; ++a)
+        for (int a = 0; a < 4; ++a) {
 #pragma unroll
-        for (int b = 0; b < TILE; ++b) {
-            s[a][b] = 0.0;
-            m[a][b] = 0ULL;
-            mf[a][b] = 0u;
+            for (int b = 0; b < 4; ++b) {
+                s[a][b] = 0.0;
+                m[a][b] = 0ULL;
+                mf[a][b] = 0u;
+            }
+            tb.packed[a] = 0u;
         }
-    TermBytes<TILE> tb = {{0u, 0u, 0u, 0u}, 0u};
-    const int64_t *rowp[TILE];
-    const int64_t *colp[TILE];
+        tb.bins = 0u;
+    }
+    __device__ __forceinline__ void add(const int64_t (&x)[4], const int64_t (&y)[4]) { matrix_accumulate<METRIC, 4>(x, y, s, m, mf, tb); }
+    __device__ __forceinline__ void add(const int64_t (&x)[4], const int64_t (&y)[4], const double (&rx)[4], const double (&ry)[4])
+    {
+        matrix_accumulate_prod_rcp<4>(x, y, rx, ry, s, m, mf, tb);
+    }
+    __device__ __forceinline__ void finish() { term_bytes_flush(tb, mf); }
+    __device__ __forceinline__ Partial partial(int, int a, int b) const
+    {
+        return Partial{s[a][b], METRIC != 2 ? (unsigned long long)mf[a][b] : m[a][b]};
+    }
+};
+
+// blockIdx.x = tile * gx + slice: tile (tq, tr) of 4 x 4 pairs, the slices stride over the bins.  Each thread streams one
+// bin at a time of the four row and four column profiles (coalesced 512-byte wave loads per profile).
+template <class Acc>
+__global__ __launch_bounds__(256) void cross_tile_kernel(const CrossOpt o, uint32_t gx, Partial *__restrict__ partials)
+{
+    const CrossSets &c = o.c;
+    const int sideR = (c.R + 3) / 4;
+    const uint32_t tile = blockIdx.x / gx, slice = blockIdx.x % gx;
+    int tq, tr;
+    cross_tile(tile, sideR, c.tri != 0, tq, tr);
+    Acc acc;
+    acc.begin(o, tq, tr, tile);
+    const int64_t *rowp[4];
+    const int64_t *colp[4];
 #pragma unroll
-    for (int a = 0; a < TILE; ++a) {
-        rowp[a] = c.left + (uint64_t)min(tq * TILE + a, c.Q - 1) * c.n;
-        colp[a] = c.right + (uint64_t)min(tr * TILE + a, c.R - 1) * c.n;
+    for (int a = 0; a < 4; ++a) {
+        rowp[a] = c.left + (uint64_t)min(tq * 4 + a, c.Q - 1) * c.n;
+        colp[a] = c.right + (uint64_t)min(tr * 4 + a, c.R - 1) * c.n;
     }
     for (uint64_t i = (uint64_t)slice * blockDim.x + threadIdx.x; i < c.n; i += (uint64_t)gx * blockDim.x) {
-        int64_t x[TILE], y[TILE];
+        int64_t x[4], y[4];
 #pragma unroll
-        for (int a = 0; a < TILE; ++a) {
+        for (int a = 0; a < 4; ++a) {
             x[a] = rowp[a][i];
             y[a] = colp[a][i];
         }
-        matrix_accumulate<METRIC, TILE>(x, y, s, m, mf, tb);
+        acc.add(x, y);
     }
-    term_bytes_flush(tb, mf);
+    acc.finish();
 #pragma unroll
-    for (int a = 0; a < TILE; ++a)
+    for (int n = 0; n < Acc::NACC; ++n)
 #pragma unroll
-        for (int b = 0; b < TILE; ++b) {
-            Partial p = {s[a][b], METRIC != 2 ? (unsigned long long)mf[a][b] : m[a][b]};
-            p = block_reduce(p);
-            if (threadIdx.x == 0) partials[((uint64_t)tile * TILE * TILE + a * TILE + b) * gx + slice] = p;
-        }
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const Partial p = block_reduce(acc.partial(n, a, b));
+                if (threadIdx.x == 0) partials[((uint64_t)n * o.slots + (uint64_t)tile * 16u + (uint64_t)(a * 4 + b)) * gx + slice] = p;
+            }
 }
 
-// matrix_super_kernel over a rectangle: 64 bins of 16 left and 16 right profiles per stage, the next stage's loads in
-// flight during the arithmetic, sixteen 16-lane groups with one 4 x 4 register tile each.
-template <int METRIC>
-__global__ __launch_bounds__(256) void cross_super_kernel(const CrossSets c, uint32_t nsuper, int superR, Partial *__restrict__ partials)
+// 16 x 16 SUPER-tiles staged through LDS (k >= 6): a workgroup loads 64 bins of its 16 row and 16 column profiles once
+// (512-byte runs, the next stage's loads in flight during the arithmetic) and its 16 groups of 16 lanes compute the sixteen
+// 4 x 4 register tiles from LDS -- a quarter of the global loads per term of cross_tile_kernel, whose 146 GB of (cached)
+// loads bound the euclidean matrix of 64 profiles at k = 12 and nearly bound the multiset one.  Rows are padded to 68 bins
+// so that the column rows of the two groups of a half-wave (4 rows apart) sit 32 banks apart for ds_read_b64.  Grid:
+// cross_block; bin-group g takes the chunks g, g + ngroups, ...
+template <class Acc>
+__global__ __launch_bounds__(256) void cross_super_kernel(const CrossOpt o, uint32_t nsuper, int superR, Partial *__restrict__ partials)
 {
-    constexpr int TILE = 4;
-    constexpr bool RCP = METRIC == 0;              // 'prod': reciprocals 1 / (x + 1) staged next to the values
+    constexpr bool RCP = Acc::RCP;                 // 'prod': reciprocals 1 / (x + 1) staged next to the values
     __shared__ int64_t stage[2][32][kSuperRow];
     __shared__ double rstage[RCP ? 2 : 1][RCP ? 32 : 1][RCP ? kSuperRow : 1];
     auto put = [&](int buf, int row, int col, int64_t v) {
         stage[buf][row][col] = v;
         if constexpr (RCP) rstage[buf][row][col] = rcp_counts((double)(uint32_t)v + 1.0);   // (unused when v >= 2^31)
     };
-    const CrossBlock blk = cross_block(nsuper, superR);
+    const CrossSets &c = o.c;
+    const CrossBlock blk = cross_block(c, nsuper, superR);
     const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
-    const int ti = blk.si * 4 + (g >> 2), tj = blk.sj * 4 + (g & 3);
-    const int sideQ = (c.Q + TILE - 1) / TILE, sideR = (c.R + TILE - 1) / TILE;
-    const bool mine = ti < sideQ && tj < sideR;        // this group's 4 x 4 tile is part of the rectangle
-    double s[TILE][TILE];
-    unsigned long long m[TILE][TILE];
-    uint32_t mf[TILE][TILE];
-#pragma unroll
-    for (int a = 0; a < TILE; ++a)
-#pragma unroll
-        for (int b = 0; b < TILE; ++b) {
-            s[a][b] = 0.0;
-            m[a][b] = 0ULL;
-            mf[a][b] = 0u;
-        }
-    TermBytes<TILE> tb = {{0u, 0u, 0u, 0u}, 0u};
+    const CrossGroup grp = cross_group(c, blk, g);
+    const bool mine = grp.mine;
+    const uint32_t tile = mine ? cross_tile_number(grp.ti, grp.tj, grp.sideR, c.tri != 0) : 0u;
+    Acc acc;
+    acc.begin(o, mine ? grp.ti : 0, mine ? grp.tj : 0, tile);
     // loader: value q of thread t is bin (t & 63) of staged row 4 q + (t >> 6): a wave reads one 512-byte run
     const int lrow = threadIdx.x >> 6, lcol = threadIdx.x & 63;
     const int64_t *src[8];
@@ -149,24 +218,24 @@ __global__ __launch_bounds__(256) void cross_super_kernel(const CrossSets c, uin
             for (int q = 0; q < 8; ++q) next[q] = src[q][(ch + blk.ngroups) * kSuperBins];
         }
         if (mine) {
-#pragma unroll 1
+#pragma unroll 1   // (unrolled 2 / 4 times: 21.3 / 20.4 ms against 19.9 for 64 profiles at k = 12)
             for (int u = 0; u < kSuperBins / 16; ++u) {
-                int64_t x[TILE], y[TILE];
+                int64_t x[4], y[4];
 #pragma unroll
-                for (int a = 0; a < TILE; ++a) {
+                for (int a = 0; a < 4; ++a) {
                     x[a] = stage[cur][4 * (g >> 2) + a][16 * u + l];
                     y[a] = stage[cur][16 + 4 * (g & 3) + a][16 * u + l];
                 }
                 if constexpr (RCP) {
-                    double rx[TILE], ry[TILE];
+                    double rx[4], ry[4];
 #pragma unroll
-                    for (int a = 0; a < TILE; ++a) {
+                    for (int a = 0; a < 4; ++a) {
                         rx[a] = rstage[cur][4 * (g >> 2) + a][16 * u + l];
                         ry[a] = rstage[cur][16 + 4 * (g & 3) + a][16 * u + l];
                     }
-                    matrix_accumulate_prod_rcp<TILE>(x, y, rx, ry, s, m, mf, tb);
+                    acc.add(x, y, rx, ry);
                 } else {
-                    matrix_accumulate<METRIC, TILE>(x, y, s, m, mf, tb);
+                    acc.add(x, y);
                 }
             }
         }
@@ -177,36 +246,65 @@ __global__ __launch_bounds__(256) void cross_super_kernel(const CrossSets c, uin
         __syncthreads();
         cur ^= 1;
     }
-    term_bytes_flush(tb, mf);
+    acc.finish();
     // per-group reduction over its 16 lanes (fixed order), lane 0 of the group writes
 #pragma unroll
-    for (int a = 0; a < TILE; ++a)
+    for (int n = 0; n < Acc::NACC; ++n)
 #pragma unroll
-        for (int b = 0; b < TILE; ++b) {
-            double ps = s[a][b];
-            unsigned long long pm = METRIC != 2 ? (unsigned long long)mf[a][b] : m[a][b];
+        for (int a = 0; a < 4; ++a)
 #pragma unroll
-            for (int d = 8; d >= 1; d >>= 1) {
-                ps += __shfl_down(ps, d, 16);
-                pm += __shfl_down(pm, d, 16);
+            for (int b = 0; b < 4; ++b) {
+                Partial p = acc.partial(n, a, b);
+#pragma unroll
+                for (int d = 8; d >= 1; d >>= 1) {
+                    p.s += __shfl_down(p.s, d, 16);
+                    p.m += __shfl_down(p.m, d, 16);
+                }
+                if (mine && l == 0) partials[((uint64_t)n * o.slots + (uint64_t)tile * 16u + (uint64_t)(a * 4 + b)) * blk.ngroups + blk.group] = p;
             }
-            if (mine && l == 0)
-                partials[(((uint64_t)ti * sideR + tj) * TILE * TILE + a * TILE + b) * blk.ngroups + blk.group] = Partial{ps, pm};
-        }
 }
 
-// The zero mask of a staged row from the loader's two ballots (matrix_rdiff_kernel): bit c = bin 2c, bit 32 + c = bin 2c + 1.
+
+// The zero mask of a staged row from the loader's two ballots: bit c = bin 2c, bit 32 + c = bin 2c + 1 (the same permutation
+// of the bins in every row).
 __device__ __forceinline__ unsigned long long cross_zero_mask(const longlong2 &v, int lhalf)
 {
     const unsigned long long z0 = __builtin_amdgcn_ballot_w64(v.x == 0), z1 = __builtin_amdgcn_ballot_w64(v.y == 0);
     return lhalf ? ((z0 >> 32) | (z1 & 0xFFFFFFFF00000000ull)) : ((z0 & 0xFFFFFFFFull) | (z1 << 32));
 }
 
-// FORM 0: multiset 'prod' as | 1/(y + 1) - 1/(x + 1) | over staged reciprocals (matrix_rdiff_kernel: accuracy, table and
-// the kRdiffMaxCount limit are argued there).  FORM 1: multiset 'sum' as |x - y| * T[x + y] over staged 32-bit counts
-// (matrix_rsum_kernel).  Same loader (16-byte loads, two rows per wave), zero masks and popcounts for the term counts.  A count
-// outside the form's range raises *big and the caller reruns cross_super_kernel; the partials must be zeroed before the
-// launch (.s and .m of a slot come from different threads).
+// The two reciprocal forms of the multiset metrics over staged super-tiles (cross_super_kernel's structure, cross_block's grid).
+//
+// FORM 0: the 'prod' pairwise function (the default of kpal distance / matrix; metrics.py:101-123, 159-162) as a difference
+// of reciprocals:
+//        |x - y| / ((x + 1)(y + 1))  =  |(x + 1) - (y + 1)| / ((x + 1)(y + 1))  =  | 1/(y + 1) - 1/(x + 1) |.
+// With r = 1 / (count + 1) staged instead of the counts a term is ONE subtraction and ONE add of an absolute value -- two
+// fp64 instructions (cross_super_kernel with PlainAcc<0>: three, plus the conversions; the plain division: ~12) -- and the
+// number of terms (bins where x != 0 or y != 0) leaves the fp64 loop entirely: the loader's waves read 64 bins of one profile
+// at a time, so ONE ballot gives that row's zero mask, and the bins where BOTH profiles are zero are popcount(mask_i & mask_j),
+// two v_bcnt per pair and stage, accumulated by thread (i, j) of the 16 x 16 super-tile.
+//   Accuracy: r is within 1 ulp of 1 / (x + 1) (rcp_counts), so a term's error is at most 2^-52 (r_x + r_y) against a term
+// of at least r_x r_y (x != y: |x - y| >= 1): relative 2^-52 (x + y + 2) -- below 2.9e-11 while both counts are below 2^16
+// (kRdiffMaxCount; at 2^20 the bound would be 4.7e-10, half the contract with nothing left for the accumulation),
+// and every term being non-negative that bounds the relative error of the sum as well; the contract for fp64 results is
+// 1e-9 (typical: 1e-15; the cancellation-dominated worst case -- all counts just below the limit, differing by 1 -- is
+// tests/test_gpu_vec.py::test_matrix_rdiff_worst_case).  A count >= 2^16 (or negative) anywhere raises *big and the caller
+// reruns the pair-of-counts kernel, cross_super_kernel.
+//   Reciprocals of counts below 512 come from a table in LDS (one ds_read_b64 instead of v_rcp_f64 + four fused
+// multiply-adds per staged value -- the loader would cost 60 % of the arithmetic otherwise); larger counts are computed.
+//
+// FORM 1: the 'sum' pairwise function, |x - y| / (x + y + 1): no difference form as for 'prod', but the denominator is a
+// small integer -- its reciprocal comes from a table in LDS, R[s] = 1 / (s + 1) for s = x + y < kRsumTable, and a term is
+// v_sad_u32 (|x - y|), v_add_lshl_u32 (the table offset), one ds_read_b64, a conversion and one fused multiply-add
+// (cross_super_kernel with PlainAcc<1>: the two conversions, the sum and a ~10-instruction division).  Profiles of one sample
+// have counts within a narrow range, so the 64 lanes of a table read touch a few dozen consecutive entries: few bank
+// conflicts.  The staged values are the counts themselves as 32-bit integers (16 KiB instead of 32).
+//   A count >= kRsumTable / 2 anywhere raises *big and the caller reruns cross_super_kernel (an inline second path for such
+// stages cost the kernel its occupancy: 200 registers).
+//   Accuracy: R within 1 ulp, |x - y| exact: a term within 1.5 ulp of the correctly rounded quotient the reference computes.
+//
+// Both: the same loader, zero masks and popcounts for the term counts, and partial layout.  The partials must be zeroed
+// before the launch (.s and .m of a slot come from different threads).
 template <int FORM>
 __global__ __launch_bounds__(256) void cross_recip_kernel(const CrossSets c, uint32_t nsuper, int superR, Partial *__restrict__ partials,
                                                           uint32_t *__restrict__ big)
@@ -218,11 +316,10 @@ __global__ __launch_bounds__(256) void cross_recip_kernel(const CrossSets c, uin
     __shared__ unsigned long long zmask[2][32];
     __shared__ double rtable[kTable];
     for (int i = threadIdx.x; i < kTable; i += 256) rtable[i] = rcp_counts((double)i + 1.0);
-    const CrossBlock blk = cross_block(nsuper, superR);
+    const CrossBlock blk = cross_block(c, nsuper, superR);
     const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
-    const int ti = blk.si * 4 + (g >> 2), tj = blk.sj * 4 + (g & 3);
-    const int sideQ = (c.Q + TILE - 1) / TILE, sideR = (c.R + TILE - 1) / TILE;
-    const bool mine = ti < sideQ && tj < sideR;
+    const CrossGroup grp = cross_group(c, blk, g);
+    const bool mine = grp.mine;
     double s[TILE][TILE];
 #pragma unroll
     for (int a = 0; a < TILE; ++a)
@@ -230,6 +327,9 @@ __global__ __launch_bounds__(256) void cross_recip_kernel(const CrossSets c, uin
         for (int b = 0; b < TILE; ++b) s[a][b] = 0.0;
     uint32_t both_zero = 0;                            // pair (row threadIdx.x >> 4, column threadIdx.x & 15) of the super-tile
     bool saw_big = false;
+    // loader: values 2 q', 2 q' + 1 of thread t are the bins 2 (t & 31), 2 (t & 31) + 1 of staged row 8 q' + (t >> 5): a wave reads
+    // two 512-byte runs with 16-byte loads (as 8-byte loads the 43 GB of staged reads moved at 0.6 of the rate: MI355X_MICROARCH.md).
+    // The row addresses of a wave's two halves are scalar; a lane selects its half's.
     const int lrow = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lhalf = (threadIdx.x >> 5) & 1, lcol = threadIdx.x & 31;
     const int64_t *src[4][2];
 #pragma unroll
@@ -273,7 +373,8 @@ __global__ __launch_bounds__(256) void cross_recip_kernel(const CrossSets c, uin
         both_zero += (uint32_t)__popcll(zmask[cur][threadIdx.x >> 4] & zmask[cur][16 + (threadIdx.x & 15)]);
         if (!mine) return;
         if constexpr (FORM == 0) {
-            // lane l takes the bin pairs (2l, 2l+1) and (32 + 2l, 32 + 2l + 1): 16-byte LDS reads
+            // lane l takes the bin pairs (2l, 2l+1) and (32 + 2l, 32 + 2l + 1): 16-byte LDS reads (ds_read_b128 moves 256 B/clk per
+            // CU; the ds_read2_b64 the 8-byte form compiled to, half of that -- and the LDS, not the fp64 pipe, set the pace)
 #pragma unroll
             for (int u = 0; u < kSuperBins / 32; ++u) {
                 double2 rx[TILE], ry[TILE];
@@ -303,7 +404,9 @@ __global__ __launch_bounds__(256) void cross_recip_kernel(const CrossSets c, uin
             for (int a = 0; a < TILE; ++a)
 #pragma unroll
                 for (int b = 0; b < TILE; ++b) {
-                    // one pair (four terms) at a time keeps the register count at four waves per SIMD (matrix_rsum_kernel)
+                    // one pair (four terms) at a time: everything a term needs before its table read depends only on the staged counts,
+                    // and with the offsets and differences of all 64 terms computed up front the kernel needed 190 registers (two
+                    // waves per SIMD); the other three waves of the SIMD cover the latency of the four reads
                     asm volatile("" : "+v"(cy[b].x), "+v"(cy[b].y), "+v"(cy[b].z), "+v"(cy[b].w));
                     const uint32_t x[4] = {cx[a].x, cx[a].y, cx[a].z, cx[a].w}, y[4] = {cy[b].x, cy[b].y, cy[b].z, cy[b].w};
 #pragma unroll
@@ -316,6 +419,14 @@ __global__ __launch_bounds__(256) void cross_recip_kernel(const CrossSets c, uin
                 }
         }
     };
+    // the values of the next stage are requested before this stage's arithmetic and staged after it.  (Requesting TWO stages
+    // ahead -- a stage's arithmetic takes ~0.3 us, a load 1-2 us -- needs 16 more registers than four waves per SIMD leave:
+    // the compiler parked the prefetched values in scratch memory and the kernel was slower.  Round 4 tried the register-free
+    // way to that depth: the raw counts by LDS-DMA (global_load_lds_dwordx4, inline assembly so that hipcc does not drain it
+    // before every LDS read) into a three-slot ring, converted to reciprocals in place one iteration later, one raw s_barrier
+    // per stage, 52 KiB of LDS = three workgroups per CU -- correct, and 8.4 ms against this kernel's 6.0: the DMA pieces cost
+    // 100-185 cycles of issue each (MI355X_MICROARCH.md) -- four per wave and stage, as much as the stage's 136 fp64
+    // instructions -- and the in-place pass adds a third to the LDS traffic, which already runs level with the fp64 pipe.)
     longlong2 next[4];
     uint64_t ch = blk.group;
     uint64_t stages = 0;
@@ -349,12 +460,14 @@ __global__ __launch_bounds__(256) void cross_recip_kernel(const CrossSets c, uin
 #pragma unroll
             for (int d = 8; d >= 1; d >>= 1) ps += __shfl_down(ps, d, 16);
             if (mine && l == 0)
-                partials[(((uint64_t)ti * sideR + tj) * TILE * TILE + a * TILE + b) * blk.ngroups + blk.group].s = ps;
+                partials[((uint64_t)cross_tile_number(grp.ti, grp.tj, grp.sideR, c.tri != 0) * 16u + (uint64_t)(a * TILE + b)) * blk.ngroups + blk.group].s = ps;
         }
     // term counts: thread (i, j) of the super-tile writes .m = bins seen - bins where both are zero
     {
         const int i = blk.si * 16 + (int)(threadIdx.x >> 4), j = blk.sj * 16 + (int)(threadIdx.x & 15);
-        if ((i >> 2) < sideQ && (j >> 2) < sideR) partials[cross_slot(sideR, i, j) * blk.ngroups + blk.group].m = stages * kSuperBins - both_zero;
+        const int sideQ = (c.Q + 3) / 4;
+        if ((i >> 2) < sideQ && (j >> 2) < grp.sideR && (!c.tri || (j >> 2) <= (i >> 2)))
+            partials[cross_slot(c, grp.sideR, i, j) * blk.ngroups + blk.group].m = stages * kSuperBins - both_zero;
     }
 }
 

@@ -7,7 +7,7 @@
 // sums are integers, v_mfma_f64_16x16x4_f64 rounds nothing that fits 53 bits.  That is checked a posteriori on
 // the diagonal (|sum of any subset of x_i y_i| <= max(G_ii, G_jj) by Cauchy-Schwarz, and a sum of squares
 // that ever reached 2^53 stays >= 2^53 under rounding); if a diagonal entry is >= 2^53 the caller falls back
-// to the wrapping-int64 kernel (matrix_super_kernel<2>), which is also the cross-check in the tests.
+// to the wrapping-int64 kernel (cross_super_kernel, euclidean), which is also the cross-check in the tests.
 //
 // Layout: profiles in blocks of 64; a workgroup (4 waves) takes one block pair (I >= J) and a stride of
 // 64-bin slabs.  A slab of 64 profiles x 64 bins is loaded with 512-byte runs per profile, converted to
@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "vec_kernels.hpp"
+#include "matrix_common.hpp"
 
 namespace kpal {
 

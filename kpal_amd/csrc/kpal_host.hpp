@@ -313,7 +313,9 @@ int profile_distance_pair(kpal_ctx *ctx, int k, const int64_t *dl, const int64_t
                           double *out);   // kpal_vec.hip: the option pipeline of one pair of 16-byte aligned device tables (balanced: do_balance is not applied again)
 int distance_matrix_core(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof, int metric, double *out_lower, bool allreduce,
                          int tiled = -1);   // kpal_vec.hip (tiled: -1 decided from n; 0 / 1 agreed between the ranks)
-namespace kpal { struct Partial; }   // vec_kernels.hpp
+namespace kpal { struct Partial; struct CrossSets; }   // matrix_common.hpp
+int reduce_partials(kpal_ctx *ctx, const Partial *partials, uint32_t nq, uint32_t nblocks, Partial *out);   // kpal_vec.hip: nq groups of nblocks device partials added in a fixed order
 int finish_partials(kpal_ctx *ctx, uint32_t nq, uint32_t nblocks, std::vector<Partial> &out, bool allreduce = false);   // kpal_vec.hip: reduce nq groups of nblocks partials, fetch them
+int cross_pairs(kpal_ctx *ctx, const CrossSets &c, int metric, bool staged, bool recip, bool allreduce, std::vector<Partial> &res);   // kpal_cross.hip: the plain pairs of a rectangle or a triangle, reduced
 double finish_value(int metric, const Partial &p, int64_t *aux);         // kpal_vec.hip: the distance of one reduced partial
 int comm_allreduce_partials(kpal_ctx *ctx, void *dev_partials, size_t count);   // kpal_multi.hip: {double sum, uint64 count} pairs added over the ranks, in place

@@ -409,7 +409,7 @@ KPAL_API int kpal_comm_merged_table(kpal_ctx *ctx, void **dev_table, uint64_t *n
 }
 
 // ---- distance matrix over bin-range shards --------------------------------------------------------------------
-// Partial of vec_kernels.hpp restated (that header's kernels belong to kpal_vec.hip): a double sum and a 64-bit count / wrapping dot
+// Partial of matrix_common.hpp restated (the kernels that fill it belong to kpal_vec.hip and kpal_cross.hip): a double sum and a 64-bit count / wrapping dot
 struct PartialPod {
     double s;
     unsigned long long m;

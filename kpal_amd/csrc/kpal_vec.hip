@@ -136,12 +136,18 @@ KPAL_API int kpal_split(kpal_ctx *ctx, int k, const int64_t *host_counts, int64_
     return KPAL_OK;
 }
 
+// out[q] = the `nblocks` partials of group q added in a fixed order, q < nq.
+int reduce_partials(kpal_ctx *ctx, const Partial *partials, uint32_t nq, uint32_t nblocks, Partial *out)
+{
+    LAUNCH(ctx, "reduce_partials", reduce_partials_kernel, dim3(nq), dim3(256), partials, nblocks, out);
+    return KPAL_OK;
+}
+
 // Reduce `nq` groups of `nblocks` partials and fetch them.
 int finish_partials(kpal_ctx *ctx, uint32_t nq, uint32_t nblocks, std::vector<Partial> &out, bool allreduce)
 {
     CHK(ensure(ctx, ctx->result, (size_t)nq * sizeof(Partial)));
-    LAUNCH(ctx, "reduce_partials", reduce_partials_kernel, dim3(nq), dim3(256), (const Partial *)ctx->partials.p,
-           nblocks, (Partial *)ctx->result.p);
+    CHK(reduce_partials(ctx, (const Partial *)ctx->partials.p, nq, nblocks, (Partial *)ctx->result.p));
     if (allreduce) CHK(comm_allreduce_partials(ctx, ctx->result.p, nq));   // bin-range shards: the sums and counts of all ranks
     out.resize(nq);
     HIPCHK(hipMemcpyAsync(out.data(), ctx->result.p, (size_t)nq * sizeof(Partial), hipMemcpyDeviceToHost, ctx->stream));
@@ -378,10 +384,7 @@ int distance_matrix_core(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof, 
     }
     constexpr int TILE = 4;
     const int side = (P + TILE - 1) / TILE;
-    std::vector<int2> tiles;
-    for (int ti = 0; ti < side; ++ti)
-        for (int tj = 0; tj <= ti; ++tj) tiles.push_back(make_int2(ti, tj));
-    const uint32_t ntiles = (uint32_t)tiles.size();
+    const uint32_t ntiles = (uint32_t)side * (uint32_t)(side + 1) / 2;   // tile (ti, tj), tj <= ti, has number ti (ti + 1) / 2 + tj
     // LDS-staged 16 x 16 super-tiles when there are enough profiles and bins to share; KPAL_MATRIX_SUPER=0 forces
     // the register-tile kernel (A/B timing, cross-check)
     static const bool allow_super = [] { const char *e = getenv("KPAL_MATRIX_SUPER"); return !e || atoi(e) != 0; }();
@@ -389,10 +392,10 @@ int distance_matrix_core(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof, 
     // multiset 'prod' of 17..64 profiles: every profile staged once per bin range (matrix_all_kernels.hpp; KPAL_MATRIX_ALL=0
     // forces the super-tile kernels)
     static const bool allow_all = [] { const char *e = getenv("KPAL_MATRIX_ALL"); return !e || atoi(e) != 0; }();
-    static const bool allow_rdiff_all = [] { const char *e = getenv("KPAL_MATRIX_RDIFF"); return !e || atoi(e) != 0; }();
-    unsigned gx;
+    static const bool allow_rdiff = [] { const char *e = getenv("KPAL_MATRIX_RDIFF"); return !e || atoi(e) != 0; }();
+    unsigned gx = 0;
     bool all_done = false;
-    if (super && allow_all && allow_rdiff_all && metric <= 1 && P > 16 && P <= 64) {
+    if (super && allow_all && allow_rdiff && metric <= 1 && P > 16 && P <= 64) {
         const bool wide = P > 32;
         gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n / 128, (uint64_t)ctx->num_cu * (wide ? 1 : 4)));
         CHK(ensure(ctx, ctx->scratch[3], 32));
@@ -420,62 +423,15 @@ int distance_matrix_core(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof, 
         }
 #endif
     }
-    if (all_done) {
-    } else if (super) {
-        const int sside = (P + 15) / 16;
-        std::vector<int2> supers;
-        for (int si = 0; si < sside; ++si)
-            for (int sj = 0; sj <= si; ++sj) supers.push_back(make_int2(si, sj));
-        const uint32_t nsuper = (uint32_t)supers.size();
-        gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n / kSuperBins, std::max<uint64_t>(1, (uint64_t)ctx->num_cu * 8 / nsuper)));
-        gx = std::max(8u, gx / 8u * 8u);   // (matrix_rdiff_kernel deals bin-groups to the 8 XCDs; n / 64 >= 64 for k >= 6)
-        CHK(ensure(ctx, ctx->scratch[3], (size_t)nsuper * sizeof(int2) + 16));
-        HIPCHK(hipMemcpyAsync(ctx->scratch[3].p, supers.data(), (size_t)nsuper * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
-        CHK(ensure(ctx, ctx->partials, (size_t)ntiles * TILE * TILE * gx * sizeof(Partial)));
-        Partial *pp = (Partial *)ctx->partials.p;
-        const int2 *dt = (const int2 *)ctx->scratch[3].p;
-        // multiset 'prod' as a difference of reciprocals (matrix_rdiff_kernel; KPAL_MATRIX_RDIFF=0 forces the pair-of-counts
-        // kernel): valid while every count is below 2^16 -- the kernel says whether it saw a larger one
-        static const bool allow_rdiff = [] { const char *e = getenv("KPAL_MATRIX_RDIFF"); return !e || atoi(e) != 0; }();
-        bool rdiff_done = false;
-        if (metric == 0 && allow_rdiff) {
-            uint32_t *big = (uint32_t *)((int2 *)ctx->scratch[3].p + nsuper);
-            HIPCHK(hipMemsetAsync(big, 0, sizeof(uint32_t), ctx->stream));
-            HIPCHK(hipMemsetAsync(pp, 0, (size_t)ntiles * TILE * TILE * gx * sizeof(Partial), ctx->stream));   // (.s / .m of a slot come from different threads)
-            LAUNCH(ctx, "matrix_rdiff", matrix_rdiff_kernel, dim3(gx * nsuper), dim3(256), prof, P, n, dt, nsuper, pp, big);   // (gx: a multiple of 8)
-            uint32_t saw_big = 0;
-            HIPCHK(hipMemcpyAsync(&saw_big, big, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipStreamSynchronize(ctx->stream));   // (also: `supers` was read by the asynchronous copy above)
-            rdiff_done = saw_big == 0;
-        }
-        if (metric == 1 && allow_rdiff) {   // multiset 'sum' with the reciprocals of the denominators from a table (matrix_rsum_kernel)
-            uint32_t *big = (uint32_t *)((int2 *)ctx->scratch[3].p + nsuper);
-            HIPCHK(hipMemsetAsync(big, 0, sizeof(uint32_t), ctx->stream));
-            HIPCHK(hipMemsetAsync(pp, 0, (size_t)ntiles * TILE * TILE * gx * sizeof(Partial), ctx->stream));
-            LAUNCH(ctx, "matrix_rsum", matrix_rsum_kernel, dim3(gx * nsuper), dim3(256), prof, P, n, dt, nsuper, pp, big);
-            uint32_t saw_big = 0;
-            HIPCHK(hipMemcpyAsync(&saw_big, big, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            rdiff_done = saw_big == 0;
-        }
-        if (rdiff_done) {
-        } else if (metric == 0) LAUNCH(ctx, "matrix_super", (matrix_super_kernel<0>), dim3(gx, nsuper), dim3(256), prof, P, n, dt, pp);
-        else if (metric == 1) LAUNCH(ctx, "matrix_super", (matrix_super_kernel<1>), dim3(gx, nsuper), dim3(256), prof, P, n, dt, pp);
-        else LAUNCH(ctx, "matrix_super", (matrix_super_kernel<2>), dim3(gx, nsuper), dim3(256), prof, P, n, dt, pp);
-        HIPCHK(hipStreamSynchronize(ctx->stream));   // `supers` is read by the asynchronous copy above
-    } else {
-        gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, std::max<uint64_t>(1, (uint64_t)ctx->num_cu * 16 / ntiles)));
-        CHK(ensure(ctx, ctx->scratch[3], (size_t)ntiles * sizeof(int2)));
-        HIPCHK(hipMemcpyAsync(ctx->scratch[3].p, tiles.data(), (size_t)ntiles * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
-        CHK(ensure(ctx, ctx->partials, (size_t)ntiles * TILE * TILE * gx * sizeof(Partial)));
-        Partial *pp = (Partial *)ctx->partials.p;
-        const int2 *dt = (const int2 *)ctx->scratch[3].p;
-        if (metric == 0) LAUNCH(ctx, "matrix_tile", (matrix_tile_kernel<0, TILE>), dim3(gx, ntiles), dim3(256), prof, P, n, dt, pp);
-        else if (metric == 1) LAUNCH(ctx, "matrix_tile", (matrix_tile_kernel<1, TILE>), dim3(gx, ntiles), dim3(256), prof, P, n, dt, pp);
-        else LAUNCH(ctx, "matrix_tile", (matrix_tile_kernel<2, TILE>), dim3(gx, ntiles), dim3(256), prof, P, n, dt, pp);
-    }
     std::vector<Partial> res;
-    CHK(finish_partials(ctx, ntiles * TILE * TILE, gx, res, allreduce));
+    if (all_done) {
+        CHK(finish_partials(ctx, ntiles * TILE * TILE, gx, res, allreduce));
+    } else {
+        // the triangle is the set crossed with itself (cross_kernels.hpp): LDS-staged super-tiles, 'prod' / 'sum' in their
+        // reciprocal forms first (KPAL_MATRIX_RDIFF=0 forces the pair-of-counts kernel), or 4 x 4 register tiles
+        const CrossSets c = {prof, prof, P, P, n, 1};
+        CHK(cross_pairs(ctx, c, metric, super, allow_rdiff, allreduce, res));
+    }
     for (int i = 1; i < P; ++i)
         for (int j = 0; j < i; ++j) {
             const int ti = i / TILE, tj = j / TILE;

@@ -2,7 +2,7 @@
 // metrics.py:101-123; pairwise prod / sum, metrics.py:159-162) for up to 64 profiles with EVERY profile staged ONCE per
 // bin range (gfx950).
 //
-// The super-tile kernels of vec_kernels.hpp (matrix_rdiff / matrix_rsum) give a workgroup one 16 x 16 block of pairs, so a
+// The super-tile kernels of cross_kernels.hpp (cross_recip_kernel: matrix_rdiff / matrix_rsum) give a workgroup one 16 x 16 block of pairs, so a
 // profile is loaded, converted and written to LDS by every super-tile of its block row and column: 5 x at 64 profiles
 // (43 GB of loads for 8.6 GB of profiles at k = 12), and that loader, not the arithmetic, set their time.  Here ONE
 // workgroup stages 64 bins of ALL 4 S rows (S = 16: 64 profiles, 32 KiB of reciprocals per buffer) and its 4 S^2 threads
@@ -17,7 +17,7 @@
 // 128-byte pieces in the order u ^ ((q >> 1) & 1), which puts the four pieces on four different quarters of the 64 banks
 // whatever the rows are (same row and piece: a broadcast).  Conflict-free, 4 cycles per wave-instruction.
 #pragma once
-#include "vec_kernels.hpp"
+#include "matrix_common.hpp"
 
 namespace kpal {
 
@@ -86,7 +86,7 @@ __device__ __forceinline__ void matrix_all_terms(double (&s)[4][4], const double
     }
 }
 
-// Multiset 'prod' as | 1/(y+1) - 1/(x+1) | (see matrix_rdiff_kernel for the identity and its accuracy bound); the staged
+// Multiset 'prod' as | 1/(y+1) - 1/(x+1) | (see cross_recip_kernel for the identity and its accuracy bound); the staged
 // values are the reciprocals.  A count >= kRdiffMaxCount (or negative) raises *big: the caller reruns the pair-of-counts kernel.
 // B bins per stage; U slots per thread (thread slot q works through the slots q, q + S^2 / (2 U), ...: U = 2 halves the
 // waves and doubles their registers -- room to have the LDS reads of the next step in flight during the arithmetic of this one).
@@ -321,10 +321,10 @@ __global__ __launch_bounds__((MatrixAllGeometry<S, B, U>::kThreads), S == 16 ? 4
     }
 }
 
-// Multiset 'sum', |x - y| / (x + y + 1), with the reciprocal of the denominator from a table in LDS (see matrix_rsum_kernel:
+// Multiset 'sum', |x - y| / (x + y + 1), with the reciprocal of the denominator from a table in LDS (see cross_recip_kernel:
 // v_sad_u32, the table offset, one ds_read_b64, a conversion and one fused multiply-add per term) over the same slots; the
 // staged values are the counts as 32-bit integers, a lane takes 4 bins of a row per step (one ds_read_b128).  A count >=
-// kRsumTable / 2 anywhere raises *big and the caller reruns matrix_super_kernel<1>.
+// kRsumTable / 2 anywhere raises *big and the caller reruns cross_super_kernel with the 'sum' accumulator.
 template <int S, int B>
 __global__ __launch_bounds__((MatrixAllGeometry<S, B, 1>::kThreads), 4) void matrix_rsum_all_kernel(const int64_t *__restrict__ prof, int P, uint64_t n,
                                                                                                   Partial *__restrict__ partials, uint32_t *__restrict__ big)

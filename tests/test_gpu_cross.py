@@ -189,6 +189,42 @@ def test_paths_and_launch_counts(ctx):
     assert 'cross_super' not in names and names.get('cross_rdiff') == 1, names
 
 
+def _triangle_case(shape):
+    kind, k, P = shape
+    return matrix_cases.build(kind, k, max(8, P)).profiles[:P]
+
+
+# k = 5, 7 profiles: the tile form with one masked row.  k = 6, 13 profiles: one super-tile with a masked row and a group above
+# the diagonal (plain: matrix_rdiff / matrix_rsum against cross_rdiff / cross_rsum; max_65536: both sides hand over to the
+# super kernel).  k = 6, 70 profiles: five super rows, idle groups above the diagonal in every diagonal super-tile.
+TRIANGLE_SHAPES = [('plain', 5, 7), ('plain', 6, 13), ('max_65536', 6, 13), ('plain', 6, 70)]
+
+
+@pytest.mark.parametrize('shape', TRIANGLE_SHAPES, ids=['%s-k%d-P%d' % s for s in TRIANGLE_SHAPES])
+def test_triangle_is_the_set_crossed_with_itself(ctx, shape):
+    """The lower triangle from distance_matrix_device equals, bit for bit, the entries below the diagonal of
+    cross_distance_device of the set against itself: one set of kernels serves both, the triangle leaving out the tiles
+    above the diagonal.  The bits can agree because the partial grouping does: at k = 6 both sides get gx = 64 workgroups
+    per super-tile (n / 64 = 64 chunks clamps it: 256 CUs * 8 / 15 or 25 super-tiles of the triangle, / 16 or 25 of the
+    square, are all above 64), so bin-group g adds the chunks g, g + 64, ... on either side and the fixed-order reduction adds
+    the same 64 partials; at k = 5 the tile form's slices are clamped by ceil(n / 256) = 4 likewise.  Euclidean runs on the
+    set whose norms reach 2^53 (same shapes): both sides leave the Gram form for the exact int64 kernel."""
+    kind, k, P = shape
+    table = 8 * 4 ** k
+    lower = [(i, j) for i in range(1, P) for j in range(i)]
+    for metric in METRICS:
+        prof = _triangle_case(('norm_2p53', k, P) if metric == 'euclidean' else shape)
+        dev = ctx.alloc(P * table)
+        try:
+            ctx.h2d(dev, prof)
+            tri = ctx.distance_matrix_device(P, k, dev, METRICS.index(metric))
+            square = ctx.cross_distance_device(k, P, dev, P, dev, METRICS.index(metric))
+        finally:
+            ctx.free(dev)
+        below = np.array([square[i, j] for i, j in lower])
+        assert np.array_equal(tri, below), (shape, metric, [lower[t] for t in np.flatnonzero(tri != below)[:8]])
+
+
 FASTA_RECORDS = 12
 
 

@@ -273,7 +273,7 @@ def test_matrix_all_staged_once(ctx):
 
 
 def test_matrix_rdiff_worst_case(ctx):
-    """The accuracy bound of multiset 'prod' as a difference of reciprocals (matrix_rdiff_kernel) where it is tightest: EVERY
+    """The accuracy bound of multiset 'prod' as a difference of reciprocals (cross_recip_kernel<0>, launched as matrix_rdiff) where it is tightest: EVERY
     count just below the kernel's limit of 2^16 and neighbours differing by 1 or 2 -- each term 1/(y+1) - 1/(x+1) cancels all
     but the last ~16 bits of its operands.  Against the oracle (IEEE divisions of the integer formulation), 1e-9 relative; and
     one count AT the limit must take the pair-of-counts kernel (same answer)."""

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Developer harness for BASELINE config 5: P profiles at k, counted from synthetic reads
 (seed 100+p), kdistlib.distance_matrix values on the GPU; cross-checks a few pairs against kpal_pair_distance.
-    python tools/mbench.py [--P 64] [--k 12] [--reads 2000000] [--metric prod] [--balance]"""
+    python tools/mbench.py [--P 64] [--k 12] [--reads 2000000] [--metric prod] [--balance] [--reps 1]
+--reps N times the call N more times with the profiler off (host clock around a synchronised call) and prints min / median / max."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -14,6 +15,7 @@ ap.add_argument('--reads', type=int, default=2_000_000)
 ap.add_argument('--metric', default='prod')
 ap.add_argument('--balance', action='store_true')
 ap.add_argument('--check', type=int, default=3)
+ap.add_argument('--reps', type=int, default=1)
 a = ap.parse_args()
 ctx = _native.Context(0)
 n = 4 ** a.k
@@ -39,6 +41,16 @@ vals = ctx.distance_matrix_device(a.P, a.k, dprof, metric, a.balance)
 wall = time.perf_counter() - t0
 for name, (ms, cnt) in sorted(ctx.prof_get().items()):
     print('   %-18s %9.3f ms (%d launches)' % (name, ms, cnt))
+ctx.prof_enable(False)
+if a.reps > 1:
+    times = []
+    for _ in range(a.reps):
+        ctx.sync()
+        t0 = time.perf_counter()
+        ctx.distance_matrix_device(a.P, a.k, dprof, metric, a.balance)
+        times.append((time.perf_counter() - t0) * 1e3)
+    print('repeats P=%d k=%d metric=%s: min %.3f median %.3f max %.3f ms (%d calls)' % (
+        a.P, a.k, a.metric, min(times), float(np.median(times)), max(times), a.reps))
 pairs = a.P * (a.P - 1) // 2
 print('matrix P=%d k=%d metric=%s balance=%s: %.1f ms wall, %d pairs, %.1f Gterms/s, profiles read %.2f GB' % (
     a.P, a.k, a.metric, a.balance, wall * 1e3, pairs, pairs * n / wall / 1e9, a.P * n * 8 / 1e9))
