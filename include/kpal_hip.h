@@ -176,6 +176,18 @@ int kpal_fasta_records_file_open(kpal_ctx *ctx, const char *path, uint64_t begin
 int kpal_fasta_records_file_next(kpal_ctx *ctx, uint64_t *n_records, uint64_t *flat_bytes, uint64_t *text_offset, int *done);
 int kpal_fasta_records_file_tell(kpal_ctx *ctx, uint64_t *offset);   /* file offset of the first byte no piece has covered yet: where a closed scan is opened again */
 int kpal_fasta_records_file_close(kpal_ctx *ctx);
+/* One profile per sliding window of each record (beyond the reference), over the records indexed by the last
+ * kpal_fasta_records_begin / kpal_fasta_records_file_next.  Coordinates are bases of the flattened record; for a record of L
+ * bases window j covers bases [j * step, min(j * step + window, L)): none for L = 0, one for L <= window, else
+ * ceil((L - window) / step) + 1, the last one possibly truncated; windows never span records and are numbered record-major.
+ * Each window restates Profile.from_sequences, klib.py:135-170, on those bases: exactly the k-mers lying wholly inside it.
+ * Accepted: 1 <= step <= window, window % step == 0, k <= window; anything else is KPAL_E_INVALID.
+ * kpal_fasta_windows_layout: *n_windows of the piece and, unless NULL, first_window[r] = number of record r's first window
+ * (n_records + 1 values, the last = *n_windows).  kpal_fasta_windows_count counts windows [first, first + n) into host_out,
+ * n tables of 4^k int64; the range may begin and end inside a record.  The cost per base does not grow with window / step. */
+int kpal_fasta_windows_layout(kpal_ctx *ctx, uint64_t window, uint64_t step, uint64_t *n_windows, uint64_t *first_window);
+int kpal_fasta_windows_count(kpal_ctx *ctx, int k, uint64_t window, uint64_t step, uint64_t first, uint64_t n, int64_t *host_out);
+int kpal_fasta_windows_count_device(kpal_ctx *ctx, int k, uint64_t window, uint64_t step, uint64_t first, uint64_t n, int64_t *dev_out);   /* the same into the caller's device memory (kpal_dev_alloc) */
 int kpal_count_finish(kpal_ctx *ctx, int64_t *host_out /* 4^k, or NULL to keep the result on the device */); /* klib.py:170 */
 /* Profile.balance (klib.py:285-298) on the count table in place, on the device: count + balance is the unit the
  * north-star metric is quoted on.  Call after the last feed, before kpal_count_finish (which then returns the balanced

@@ -89,6 +89,9 @@ SIGNATURES = {
     'kpal_fasta_records_file_tell': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
     'kpal_fasta_records_file_close': (ctypes.c_int, [_vp]),
     'kpal_fasta_records_count': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp]),
+    'kpal_fasta_windows_layout': (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), _vp]),
+    'kpal_fasta_windows_count': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp]),
+    'kpal_fasta_windows_count_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp]),
     'kpal_count_finish': (ctypes.c_int, [_vp, _vp]),
     'kpal_count_table': (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint64)]),
     'kpal_count_balance': (ctypes.c_int, [_vp]),
@@ -525,6 +528,23 @@ class Context(object):
         """Tables of records [first, first + n) of the indexed text into n * 4**k int64 of device memory at ``dev_out``."""
         if n > 0:
             _check(self._L.kpal_fasta_records_count_device(self._h, int(k), int(first), int(n), _vp(dev_out)))
+
+    def fasta_windows_layout(self, window, step):
+        """Sliding windows of the indexed records -> (n_windows, number of every record's first window [n_records + 1])."""
+        first = np.empty(getattr(self, '_records', 0) + 1, dtype=np.uint64)
+        n = ctypes.c_uint64(0)
+        _check(self._L.kpal_fasta_windows_layout(self._h, int(window), int(step), ctypes.byref(n), first.ctypes.data))
+        return n.value, first
+
+    def fasta_windows_count(self, k, window, step, first, n):
+        """Tables of windows [first, first + n) of the indexed records -> int64[n, 4**k]."""
+        out = np.empty((max(n, 0), 4 ** k), dtype=np.int64)
+        _check(self._L.kpal_fasta_windows_count(self._h, int(k), int(window), int(step), int(first), int(n), out.ctypes.data))
+        return out
+
+    def fasta_windows_count_device(self, k, window, step, first, n, dev_out):
+        """Tables of windows [first, first + n) of the indexed records into n * 4**k int64 of device memory at ``dev_out``."""
+        _check(self._L.kpal_fasta_windows_count_device(self._h, int(k), int(window), int(step), int(first), int(n), _vp(dev_out)))
 
     def count_bytes(self, k, buf, strategy='auto'):
         """Count one flat host byte stream -> int64[4**k]."""

@@ -9,6 +9,7 @@
 #include "fasta_kernels.hpp"
 #include "fasta_host.hpp"
 #include "fastq_kernels.hpp"
+#include "window_kernels.hpp"
 
 #include <cerrno>
 #include <fcntl.h>
@@ -1102,6 +1103,7 @@ static int fasta_records_index_text(kpal_ctx *ctx, const uint8_t *host_text, siz
 {
     *n_records = *flat_bytes = 0;
     ctx->rec_n = ctx->rec_nf = 0;
+    ctx->win_window = ctx->win_step = 0;
     ctx->rec_starts_host.clear();
     ctx->rec_hdr_host.clear();
     const size_t first = nbytes ? fasta_first_header(host_text, nbytes, true) : 0;   // text before the first header is no record (klib.py:131: SeqIO)
@@ -1354,6 +1356,145 @@ KPAL_API int kpal_fasta_records_count_device(kpal_ctx *ctx, int k, uint64_t firs
     if (n == 0) return KPAL_OK;
     if (!dev_out) return set_err(KPAL_E_INVALID, "dev_out is NULL");
     CHK(fasta_records_count_into(ctx, k, first, n, (unsigned long long *)dev_out));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // (the index may be overwritten by the caller's next piece)
+    return KPAL_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
+// Profile.from_fasta_by_window: one profile per sliding window of every indexed record (window_kernels.hpp; the layout
+// arithmetic is window_index.hpp).  Tile tables, running sum along the tiles, trim of the windows that end inside their
+// record: three launches per call (two when window == step), whatever window / step is.
+// ----------------------------------------------------------------------------------------------
+constexpr size_t kWinTileBytes = (size_t)2 << 30;   // tile tables of one pass (a longer range of windows is counted in several)
+
+// first window / first tile of every indexed record for (window, step), on the host and on the device
+static int fasta_windows_prepare(kpal_ctx *ctx, uint64_t W, uint64_t S)
+{
+    if (S < 1 || S > W || W % S != 0)
+        return set_err(KPAL_E_INVALID, "window=%llu step=%llu: need 1 <= step <= window and window %% step == 0", (unsigned long long)W, (unsigned long long)S);
+    if (W > (1ULL << 62)) return set_err(KPAL_E_INVALID, "window=%llu is too large", (unsigned long long)W);
+    if (ctx->rec_n == 0) return set_err(KPAL_E_STATE, "kpal_fasta_windows_* without records (kpal_fasta_records_begin)");
+    if (ctx->win_window == W && ctx->win_step == S) return KPAL_OK;
+    const size_t R = (size_t)ctx->rec_n;
+    ctx->win_window = ctx->win_step = 0;
+    ctx->win_first_host.resize(R + 1);
+    ctx->win_tile_host.resize(R + 1);
+    win_layout(ctx->rec_starts_host.data(), R, W, S, ctx->win_first_host.data(), ctx->win_tile_host.data());
+    CHK(ensure(ctx, ctx->win_index, 2 * (R + 1) * sizeof(uint64_t)));
+    HIPCHK(hipMemcpyAsync(ctx->win_index.p, ctx->win_first_host.data(), (R + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync((uint64_t *)ctx->win_index.p + R + 1, ctx->win_tile_host.data(), (R + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->win_window = W;
+    ctx->win_step = S;
+    return KPAL_OK;
+}
+
+// windows [first, first + n) -- made from the tiles and bytes of `rg` -- into n x 4^k int64 of device memory
+static int fasta_windows_pass(kpal_ctx *ctx, int k, uint64_t W, uint64_t S, uint64_t first, uint64_t n, const WinRange &rg, unsigned long long *dev_out)
+{
+    const uint64_t bins = 1ULL << (2 * k), m = W / S;
+    const uint64_t R = ctx->rec_n, ntiles = rg.tile1 - rg.tile0;
+    const uint64_t *index = (const uint64_t *)ctx->win_index.p;
+    const WinGeom g = {(const uint64_t *)ctx->rec_starts.p, index, index + R + 1, R, W, S, first, n, rg.tile0, rg.tile1};
+    const uint8_t *flat = (const uint8_t *)ctx->rec_flat.p + kpal_ctx::kStagePad;
+    unsigned long long *tiles = dev_out;   // window == step: the tiles are the windows
+    if (m > 1) {
+        CHK(ensure(ctx, ctx->win_tiles, (size_t)ntiles * bins * sizeof(int64_t)));
+        tiles = (unsigned long long *)ctx->win_tiles.p;
+    }
+    if (k <= 7 && S < (1ULL << 32)) {   // histograms in LDS (u32 bins: a tile holds fewer than 2^32 k-mers)
+        const Span s = make_span(flat, (size_t)ctx->rec_nf, 0);
+        if (S <= 2048) {
+            DISPATCH_K_1_7(k, {
+                constexpr int TPW = WinTileCfg<K>::kSmallTpw;
+                const unsigned grid = (unsigned)std::min<uint64_t>((ntiles + TPW - 1) / TPW, (uint64_t)ctx->num_cu * 8);
+                LAUNCH(ctx, "window_tiles", (window_tiles_lds_kernel<K, TPW, 4>), dim3(grid), dim3(256), s, g, tiles);
+            });
+        } else {
+            const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, (uint64_t)ctx->num_cu * 4);
+            DISPATCH_K_1_7(k, LAUNCH(ctx, "window_tiles", (window_tiles_lds_kernel<K, 1, 8>), dim3(grid), dim3(512), s, g, tiles));
+        }
+    } else {
+        HIPCHK(hipMemsetAsync(tiles, 0, (size_t)ntiles * bins * sizeof(int64_t), ctx->stream));
+        const Span s = make_span(flat + rg.byte0, (size_t)(rg.byte1 - rg.byte0), 0);
+        const uint64_t steps = (s.nchunks + 63) / 64;
+        const uint64_t max_waves = (uint64_t)ctx->num_cu * 8 * 4;
+        const uint64_t spw = std::max<uint64_t>(1, (steps + max_waves - 1) / max_waves);
+        const uint64_t waves = (steps + spw - 1) / spw;
+        const unsigned grid = (unsigned)((waves + 3) / 4);
+        DISPATCH_K_1_16(k, LAUNCH(ctx, "window_tiles_atomic", (window_tiles_atomic_kernel<K>), dim3(grid), dim3(256), s, spw, rg.byte0, g, tiles));
+    }
+    if (m > 1) {
+        // segments of at least m windows (the m loads of a segment's first sum then cost no more than one per window),
+        // longer ones once the device is full
+        const uint64_t threads = (uint64_t)ctx->num_cu * 2048;
+        const uint64_t segment = std::max<uint64_t>(m, (n * bins + threads - 1) / threads);
+        const uint64_t n_segments = (n + segment - 1) / segment;
+        const uint64_t blocks = bins < (uint64_t)kWinSlideThreads ? (n_segments + kWinSlideThreads / bins - 1) / (kWinSlideThreads / bins)
+                                                                   : n_segments * (bins / kWinSlideThreads);
+        if (blocks > 0x7FFFFFFFull) return set_err(KPAL_E_INVALID, "too many windows in one batch");
+        LAUNCH(ctx, "window_slide", window_slide_kernel, dim3((unsigned)blocks), dim3(kWinSlideThreads), g, bins, segment, n_segments,
+               (const unsigned long long *)tiles, dev_out);
+    }
+    LAUNCH(ctx, "window_trim", window_trim_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), g, k, flat, dev_out);
+    return KPAL_OK;
+}
+
+static int fasta_windows_count_into(kpal_ctx *ctx, int k, uint64_t W, uint64_t S, uint64_t first, uint64_t n, unsigned long long *dev_out)
+{
+    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range 1..%d", k, KPAL_MAX_K);
+    CHK(fasta_windows_prepare(ctx, W, S));
+    if ((uint64_t)k > W) return set_err(KPAL_E_INVALID, "k=%d is longer than the window (%llu)", k, (unsigned long long)W);
+    const uint64_t R = ctx->rec_n, total = ctx->win_first_host[(size_t)R];
+    if (first > total || n > total - first) return set_err(KPAL_E_INVALID, "windows %llu..%llu of %llu", (unsigned long long)first,
+                                                           (unsigned long long)(first + n), (unsigned long long)total);
+    if (n >= 0x7FFFFFFFull * 256) return set_err(KPAL_E_INVALID, "too many windows in one batch");
+    const uint64_t bins = 1ULL << (2 * k);
+    const uint64_t cap = std::max<uint64_t>(1, kWinTileBytes / (bins * sizeof(int64_t)));
+    const uint64_t *starts = ctx->rec_starts_host.data(), *fw = ctx->win_first_host.data(), *ft = ctx->win_tile_host.data();
+    for (uint64_t done = 0; done < n;) {
+        uint64_t c = n - done;
+        WinRange rg = win_range(starts, fw, ft, R, k, W, S, first + done, c);
+        while (W != S && rg.tile1 - rg.tile0 > cap && c > 1) {   // (the tile tables of a pass stay within kWinTileBytes)
+            c = (c + 1) / 2;
+            rg = win_range(starts, fw, ft, R, k, W, S, first + done, c);
+        }
+        CHK(fasta_windows_pass(ctx, k, W, S, first + done, c, rg, dev_out + done * bins));
+        done += c;
+    }
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_fasta_windows_layout(kpal_ctx *ctx, uint64_t window, uint64_t step, uint64_t *n_windows, uint64_t *first_window)
+{
+    CTX_ENTER(ctx);
+    if (!n_windows) return set_err(KPAL_E_INVALID, "NULL pointer");
+    *n_windows = 0;
+    CHK(fasta_windows_prepare(ctx, window, step));
+    *n_windows = ctx->win_first_host[(size_t)ctx->rec_n];
+    if (first_window) memcpy(first_window, ctx->win_first_host.data(), (size_t)(ctx->rec_n + 1) * 8);
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_fasta_windows_count(kpal_ctx *ctx, int k, uint64_t window, uint64_t step, uint64_t first, uint64_t n, int64_t *host_out)
+{
+    CTX_ENTER(ctx);
+    if (n && !host_out) return set_err(KPAL_E_INVALID, "host_out is NULL");
+    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range 1..%d", k, KPAL_MAX_K);
+    const size_t out_bytes = (size_t)n * ((size_t)1 << (2 * k)) * sizeof(int64_t);
+    if (n) CHK(ensure(ctx, ctx->scratch[0], out_bytes));
+    CHK(fasta_windows_count_into(ctx, k, window, step, first, n, (unsigned long long *)ctx->scratch[0].p));
+    if (n == 0) return KPAL_OK;
+    HIPCHK(hipMemcpyAsync(host_out, ctx->scratch[0].p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_fasta_windows_count_device(kpal_ctx *ctx, int k, uint64_t window, uint64_t step, uint64_t first, uint64_t n, int64_t *dev_out)
+{
+    CTX_ENTER(ctx);
+    if (n && !dev_out) return set_err(KPAL_E_INVALID, "dev_out is NULL");
+    CHK(fasta_windows_count_into(ctx, k, window, step, first, n, (unsigned long long *)dev_out));
     HIPCHK(hipStreamSynchronize(ctx->stream));   // (the index may be overwritten by the caller's next piece)
     return KPAL_OK;
 }

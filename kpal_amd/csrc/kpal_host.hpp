@@ -132,6 +132,12 @@ struct kpal_ctx {
     int rec_fd = -1;
     uint64_t rec_pos = 0, rec_end = 0, rec_piece_at = 0;
     std::vector<uint8_t> rec_carry;
+    // ... cut into sliding windows (kpal_fasta_windows_*): first window and first tile of every record (R + 1 values each; on
+    // the device one behind the other) for the (window, step) last asked for -- a new record index clears them -- and the
+    // tile tables of the call in flight
+    DevBuf win_index, win_tiles;
+    std::vector<uint64_t> win_first_host, win_tile_host;
+    uint64_t win_window = 0, win_step = 0;
     uint64_t *fa_nflat_host = nullptr;
     // FASTQ ingest (kpal_count.hip): raw text (carried rest of the chunk before + the chunk) and flattened stream of two chunks,
     // scan metadata and newline positions of the chunk being tokenised, its status words on the device and in pinned host memory

@@ -212,6 +212,104 @@ def _whole_record_chunks(handle):
         yield bytes(pending), (''.join(pending_str) if keep_str else None), encoding
 
 
+def _indexed_pieces(ctx, handle, prefix, who):
+    """The records of a FASTA handle, piece by piece of whole records, each piece tokenised and indexed ON THE DEVICE
+    (``kpal_fasta_records_begin`` / ``kpal_fasta_records_file_next``): yields ``(names, bases, indexed)`` -- the records'
+    names (``prefix`` + the first word of the title, or the 1-based index of an untitled record, kpal/klib.py:132), their
+    lengths in bases, and a callable that makes sure the context still holds THIS piece's index.
+
+    The reference's generators are independent of each other (zip() of two, nesting, one abandoned half-way), and the
+    callers of this one yield with a piece indexed on the process-wide context.  So they call ``indexed()`` before every
+    batch: when another scan has used the context since, the piece is indexed again."""
+    index = 0                                  # records seen so far
+    plain = _plain_file(handle)
+    if plain is not None and os.path.getsize(plain[0]) > plain[1]:
+        # an ordinary file: the library reads it itself (parallel preads into pinned memory, pieces of whole records);
+        # the names are read from the header lines through a read-only mapping of the file
+        import mmap
+        encoding = handle.encoding if isinstance(handle, io.TextIOWrapper) else 'ascii'
+        # Nothing of the scan lives in the context across a yield: the scan is opened at `resume`, asked for ONE piece and
+        # closed again; a piece that has to be indexed again is bytes [at, resume).
+        def index_piece(begin, end):
+            ctx.fasta_records_file_open(plain[0], begin, end)
+            try:
+                piece = ctx.fasta_records_file_next()
+                return piece, (ctx.fasta_records_file_tell() if piece is not None else end)
+            finally:
+                ctx.fasta_records_file_close()
+
+        with open(plain[0], 'rb') as raw, mmap.mmap(raw.fileno(), 0, access=mmap.ACCESS_READ) as text:
+            resume = plain[1]
+            while True:
+                piece, resume = index_piece(resume, 0)
+                if piece is None:
+                    break
+                n_records, _, at = piece
+                if n_records == 0:
+                    continue
+                scan = [ctx._records_scan]
+                header_off, flat_start = ctx.fasta_records_index()
+                names = []
+                for h in (header_off + np.uint64(at)).tolist():
+                    words = text[h + 1:_line_end(text, h)].decode(encoding, 'replace').split(None, 1)
+                    index += 1
+                    names.append(prefix + (words[0] if words else str(index)))
+
+                def indexed(at=at, resume=resume, n_records=n_records, scan=scan):
+                    if ctx._records_scan != scan[0]:
+                        again, _ = index_piece(at, resume)
+                        if again is None or again[0] != n_records:
+                            raise RuntimeError('%s: bytes %d..%d of %s changed under the scan' % (who, at, resume, plain[0]))
+                        scan[0] = ctx._records_scan
+
+                yield names, np.diff(flat_start) - np.uint64(1), indexed
+        handle.seek(0, os.SEEK_END)          # the handle has been consumed, as by the reference's SeqIO.parse loop
+        return
+    for text, text_str, encoding in _whole_record_chunks(handle):
+        n_records, _ = ctx.fasta_records_begin(text)
+        if n_records == 0:
+            continue
+        header_off, flat_start = ctx.fasta_records_index()
+        names = []
+        for h in header_off.tolist():
+            end = _line_end(text, h)
+            title = text_str[h + 1:end] if text_str is not None else text[h + 1:end].decode(encoding, 'replace')
+            words = title.split(None, 1)
+            index += 1
+            names.append(prefix + (words[0] if words else str(index)))
+        scan = [ctx._records_scan]
+
+        def indexed(text=text, scan=scan):
+            if ctx._records_scan != scan[0]:     # another scan used the context since the last batch: this text again
+                ctx.fasta_records_begin(text)
+                scan[0] = ctx._records_scan
+
+        yield names, np.diff(flat_start) - np.uint64(1), indexed
+
+
+def _window_count(bases, window, step):
+    """Sliding windows of a record of ``bases`` bases (csrc/window_index.hpp: win_count)."""
+    if bases <= window:
+        return 1 if bases else 0
+    return -(-(bases - window) // step) + 1
+
+
+def _window_arguments(length, window, step):
+    """``(length, window, step)`` as integers (``step`` defaults to ``window``); ValueError unless ``1 <= length <= window``,
+    ``1 <= step <= window`` and ``step`` divides ``window``."""
+    length, window = int(length), int(window)
+    step = window if step is None else int(step)
+    if length < 1 or length > _native.KPAL_MAX_K:
+        raise ValueError('k-mer length must be in 1..%d (got %d)' % (_native.KPAL_MAX_K, length))
+    if window < length:
+        raise ValueError('the window (%d) must be at least as long as the k-mers (%d)' % (window, length))
+    if step < 1 or step > window or window % step:
+        raise ValueError('the step (%d) must be in 1..window and divide the window (%d)' % (step, window))
+    if window > 1 << 62:
+        raise ValueError('the window (%d) is too long' % window)
+    return length, window, step
+
+
 def _join_block(block):
     """One flat byte string for a block of sequences, ``\\n`` between them: C-speed joins for the
     homogeneous cases (all ``str`` / all ``bytes``), per-item encoding otherwise."""
@@ -464,71 +562,52 @@ class Profile(object):
                 yield cls.from_sequences([seq], length, name=prefix + (record_name or str(i + 1)))
             return
         ctx = _native.context()
-        index = 0                                  # records seen so far (kpal/klib.py:132: the 1-based index names an untitled record)
-        plain = _plain_file(handle)
-        if plain is not None and os.path.getsize(plain[0]) > plain[1]:
-            # an ordinary file: the library reads it itself (parallel preads into pinned memory, pieces of whole records);
-            # the names are read from the header lines through a read-only mapping of the file
-            import mmap
-            encoding = handle.encoding if isinstance(handle, io.TextIOWrapper) else 'ascii'
-            # The reference's generators are independent of each other (zip() of two, nesting, one abandoned half-way), and
-            # this one yields with a piece indexed on the process-wide context.  So nothing of the scan lives in the context
-            # across a yield: the scan is opened at `resume`, asked for ONE piece and closed again; and when another scan has
-            # used the context between two batches of a piece, the piece -- bytes [at, resume) -- is indexed again.
-            def index_piece(begin, end):
-                ctx.fasta_records_file_open(plain[0], begin, end)
-                try:
-                    piece = ctx.fasta_records_file_next()
-                    return piece, (ctx.fasta_records_file_tell() if piece is not None else end)
-                finally:
-                    ctx.fasta_records_file_close()
-
-            with open(plain[0], 'rb') as raw, mmap.mmap(raw.fileno(), 0, access=mmap.ACCESS_READ) as text:
-                resume = plain[1]
-                while True:
-                    piece, resume = index_piece(resume, 0)
-                    if piece is None:
-                        break
-                    n_records, _, at = piece
-                    if n_records == 0:
-                        continue
-                    scan = ctx._records_scan
-                    header_off, _ = ctx.fasta_records_index()
-                    names = []
-                    for h in (header_off + np.uint64(at)).tolist():
-                        words = text[h + 1:_line_end(text, h)].decode(encoding, 'replace').split(None, 1)
-                        index += 1
-                        names.append(prefix + (words[0] if words else str(index)))
-                    for first in range(0, n_records, per_batch):
-                        if ctx._records_scan != scan:
-                            again, _ = index_piece(at, resume)
-                            if again is None or again[0] != n_records:
-                                raise RuntimeError('from_fasta_by_record: bytes %d..%d of %s changed under the scan' % (at, resume, plain[0]))
-                            scan = ctx._records_scan
-                        n = min(per_batch, n_records - first)
-                        for profile in cls._record_batch(ctx, length, first, n, names):
-                            yield profile
-            handle.seek(0, os.SEEK_END)          # the handle has been consumed, as by the reference's SeqIO.parse loop
-            return
-        for text, text_str, encoding in _whole_record_chunks(handle):
-            n_records, _ = ctx.fasta_records_begin(text)
-            if n_records == 0:
-                continue
-            header_off, _ = ctx.fasta_records_index()
-            names = []
-            for h in header_off.tolist():
-                end = _line_end(text, h)
-                title = text_str[h + 1:end] if text_str is not None else text[h + 1:end].decode(encoding, 'replace')
-                words = title.split(None, 1)
-                index += 1
-                names.append(prefix + (words[0] if words else str(index)))
-            scan = ctx._records_scan
-            for first in range(0, n_records, per_batch):
-                if ctx._records_scan != scan:        # another by-record scan used the context since the last batch: this text again
-                    ctx.fasta_records_begin(text)
-                    scan = ctx._records_scan
-                n = min(per_batch, n_records - first)
+        for names, _, indexed in _indexed_pieces(ctx, handle, prefix, 'from_fasta_by_record'):
+            for first in range(0, len(names), per_batch):
+                indexed()
+                n = min(per_batch, len(names) - first)
                 for profile in cls._record_batch(ctx, length, first, n, names):
+                    yield profile
+
+    @classmethod
+    def from_fasta_by_window(cls, handle, length, window, step=None, prefix=None):
+        """One profile per sliding window of every FASTA record (beyond the reference: a compositional scan).
+
+        Coordinates are bases of the record as the device tokeniser flattens it (line ends and spaces dropped).  For a
+        record of L bases window j covers bases ``[j * step, min(j * step + window, L))``: none for an empty record, one for
+        ``L <= window``, else ``ceil((L - window) / step) + 1`` -- only the last one of a record can be truncated, and no
+        window spans two records.  Its profile holds the k-mers lying wholly inside it: what
+        ``from_sequences([seq[j * step:j * step + window]], length)`` counts, bit for bit.  ``step`` defaults to ``window``
+        and must divide it; ``length <= window``.  Profiles come record-major, named ``<record name>:<start + 1>-<end>``
+        (1-based, inclusive), the record name being the one ``from_fasta_by_record`` gives.
+
+        The records are indexed as for ``from_fasta_by_record`` and counted by ``kpal_fasta_windows_count``: every base is
+        tokenised and counted once, whatever ``window / step`` is, and the tables stay in HBM under the same budgets.  A k
+        whose table alone exceeds the batch budget falls back to ``from_sequences`` per window."""
+        length, window, step = _window_arguments(length, window, step)
+        prefix = prefix + '_' if prefix else ''
+        table_bytes = 8 * 4 ** length
+        per_batch = _RECORD_BATCH_BYTES // table_bytes
+        if per_batch < 2:
+            for i, (record_name, seq) in enumerate(_fasta_records(handle)):
+                record_name = prefix + (record_name or str(i + 1))
+                for start in range(0, _window_count(len(seq), window, step) * step, step):
+                    end = min(start + window, len(seq))
+                    yield cls.from_sequences([seq[start:end]], length, name='%s:%d-%d' % (record_name, start + 1, end))
+            return
+        ctx = _native.context()
+        for names, bases, indexed in _indexed_pieces(ctx, handle, prefix, 'from_fasta_by_window'):
+            n_windows, first_window = ctx.fasta_windows_layout(window, step)
+            for first in range(0, n_windows, per_batch):
+                indexed()
+                n = min(per_batch, n_windows - first)
+                # names of windows [first, first + n): their records, their numbers inside them
+                numbers = np.arange(first, first + n, dtype=np.uint64)
+                records = np.searchsorted(first_window, numbers, side='right') - 1
+                starts = (numbers - first_window[records]) * np.uint64(step)
+                ends = np.minimum(starts + np.uint64(window), bases[records])
+                window_names = ['%s:%d-%d' % (names[r], a + 1, b) for r, a, b in zip(records.tolist(), starts.tolist(), ends.tolist())]
+                for profile in cls._window_batch(ctx, length, window, step, first, n, window_names):
                     yield profile
 
     @classmethod
@@ -558,6 +637,18 @@ class Profile(object):
             return [cls._from_device(batch, j, length, names[first + j]) for j in range(n)]
         tables = ctx.fasta_records_count(length, first, n)
         return [cls(tables[j], name=names[first + j]) for j in range(n)]
+
+    @classmethod
+    def _window_batch(cls, ctx, length, window, step, first, n, names):
+        """The profiles of windows [first, first + n) of the records the context has indexed (``names``: theirs), kept in
+        HBM or downloaded at once as ``_record_batch`` does."""
+        nbytes = n * 8 * 4 ** length
+        if _DEVICE_PROFILE_BYTES and _DeviceBatch.live_bytes + nbytes <= _DEVICE_PROFILE_BYTES:
+            batch = _DeviceBatch(ctx, nbytes, n)
+            ctx.fasta_windows_count_device(length, window, step, first, n, batch.ptr)
+            return [cls._from_device(batch, j, length, names[j]) for j in range(n)]
+        tables = ctx.fasta_windows_count(length, window, step, first, n)
+        return [cls(tables[j], name=names[j]) for j in range(n)]
 
     @classmethod
     def from_sequences(cls, sequences, length, name=None):

@@ -86,13 +86,24 @@ def cat(input_handles, output_handle, names=None, prefixes=None):
             profile.save(output_handle, name=prefix + name)
 
 
-def count(input_handles, output_handle, size, names=None, by_record=False, fastq=False, min_quality=None, phred64=False):
+def count(input_handles, output_handle, size, names=None, by_record=False, fastq=False, min_quality=None, phred64=False,
+          by_window=None, step=None):
     """k-mer profiles of FASTA files (kpal/kmer.py:112-146): one profile per file, or per record
     with ``by_record`` (record names, prefixed by the file's name when several files are given).
     With ``fastq`` the inputs are four-line FASTQ files, one profile per file (beyond the reference); ``min_quality`` masks
-    bases of a lower Phred quality, read with offset 64 instead of 33 under ``phred64``."""
+    bases of a lower Phred quality, read with offset 64 instead of 33 under ``phred64``.
+    With ``by_window`` = W (beyond the reference) there is one profile per sliding window of W bases of every record, ``step``
+    bases apart (default W; it must divide W), named ``<record>:<start>-<end>`` and prefixed like the records' profiles."""
     if fastq and by_record:
         raise ValueError('--by-record does not apply to FASTQ input (one profile per read is not supported)')
+    if by_window is not None and by_record:
+        raise ValueError('--by-window and --by-record exclude each other (a window profile is named after its record already)')
+    if by_window is not None and fastq:
+        raise ValueError('--by-window does not apply to FASTQ input (windows are cut from FASTA records)')
+    if step is not None and by_window is None:
+        raise ValueError('--step applies to --by-window only')
+    if by_window is not None:
+        klib._window_arguments(size, by_window, step)
     if not fastq and (min_quality is not None or phred64):
         raise ValueError('--min-quality and --phred64 apply to FASTQ input only (add --fastq)')
     names = names or [_name_from_handle(handle) for handle in input_handles]
@@ -105,6 +116,8 @@ def count(input_handles, output_handle, size, names=None, by_record=False, fastq
                                                 quality_offset=64 if phred64 else 33)]
         elif by_record:
             profiles = klib.Profile.from_fasta_by_record(handle, size, prefix=name if several else None)
+        elif by_window is not None:
+            profiles = klib.Profile.from_fasta_by_window(handle, size, by_window, step=step, prefix=name if several else None)
         else:
             profiles = [klib.Profile.from_fasta(handle, size, name=name)]
         for profile in profiles:
@@ -478,6 +491,11 @@ def build_parser():
     sub.add_argument('--by-record', '-r', dest='by_record', action='store_true',
                      help='make a k-mer profile per FASTA record instead of a k-mer profile per FASTA file (profiles are '
                      'named by the record names and prefixed according to --profiles if more than one INPUT is given)')
+    sub.add_argument('--by-window', dest='by_window', metavar='W', type=int, default=None,
+                     help='make a k-mer profile per sliding window of W bases of every FASTA record (profiles are named '
+                     'RECORD:START-END, 1-based and inclusive, and prefixed like those of --by-record)')
+    sub.add_argument('--step', dest='step', metavar='S', type=int, default=None,
+                     help='with --by-window: bases between the starts of two windows (a divisor of W; default: W)')
     sub.add_argument('--fastq', dest='fastq', action='store_true',
                      help='the INPUTs are four-line FASTQ files of reads (one k-mer profile per file)')
     sub.add_argument('--min-quality', dest='min_quality', metavar='Q', type=int, default=None,
