@@ -141,7 +141,7 @@ __global__ __launch_bounds__(512) void count_lds_direct_kernel(Span s, uint64_t 
 // ------------------------------------------------------------------------------------------
 // Synthetic reads.  One thread per 16 output bytes.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void synth_reads_kernel(uint64_t seed, uint64_t first_read, uint64_t n_reads,
+static __global__ __launch_bounds__(256) void synth_reads_kernel(uint64_t seed, uint64_t first_read, uint64_t n_reads,
                                                           uint32_t read_len, int noisy, uint8_t *__restrict__ out)
 {
     const uint64_t total = n_reads * (uint64_t)(read_len + 1);

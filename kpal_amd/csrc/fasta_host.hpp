@@ -2,7 +2,7 @@
 // from (a byte range of a file read by the pool's threads, or host memory, optionally preceded by a short prefix), how it is read
 // into two staging buffers -- StagedReader reads chunk i + 1 into one while the caller handles chunk i in the other; fa_read
 // reads one range synchronously -- and how FaChunker cuts FASTA text into the chunks the flattening kernels of fasta_kernels.hpp
-// take.  kpal_count.hip drives both with its pinned staging buffers and queues the copies and kernels per chunk;
+// take.  kpal_text.hip drives both with its pinned staging buffers and queues the copies and kernels per chunk;
 // tests/native/fasta_host_check.cpp drives the same classes with malloc'ed buffers under AddressSanitizer / ThreadSanitizer and
 // compares the chunks with the source, and the FASTA chunks, flattened by a restatement of the kernels' rules, with the text
 // flattened in one piece.

@@ -71,7 +71,7 @@ __device__ __forceinline__ long long fa_block_exclusive_max(long long v, long lo
 }
 
 // K1: index of the last end-of-line byte in each block (-1 if none).
-__global__ __launch_bounds__(kFaThreads) void fa_last_eol_kernel(const uint8_t *__restrict__ in, uint64_t n,
+static __global__ __launch_bounds__(kFaThreads) void fa_last_eol_kernel(const uint8_t *__restrict__ in, uint64_t n,
                                                                  long long *__restrict__ last_eol)
 {
     __shared__ long long sh[4];
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kFaThreads) void fa_last_eol_kernel(const uint8_t *
 }
 
 // K2: carry[b] = last EOL index in blocks < b (-1 if none).  One workgroup, serial over chunks.
-__global__ __launch_bounds__(256) void fa_carry_kernel(const long long *__restrict__ last_eol, uint32_t nblocks,
+static __global__ __launch_bounds__(256) void fa_carry_kernel(const long long *__restrict__ last_eol, uint32_t nblocks,
                                                        long long *__restrict__ carry)
 {
     __shared__ long long sh[4];
@@ -141,7 +141,7 @@ __device__ __forceinline__ void fa_classify(const uint8_t *__restrict__ in, uint
 }
 
 // K3: kept bytes per block.
-__global__ __launch_bounds__(kFaThreads) void fa_count_kernel(const uint8_t *__restrict__ in, uint64_t n,
+static __global__ __launch_bounds__(kFaThreads) void fa_count_kernel(const uint8_t *__restrict__ in, uint64_t n,
                                                               const long long *__restrict__ carry, int start_state, int tail_trailing,
                                                               uint32_t *__restrict__ kept)
 {
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(kFaThreads) void fa_count_kernel(const uint8_t *__r
 }
 
 // K4: exclusive scan of the per-block counts -> 64-bit offsets; offs[nblocks] = total.
-__global__ __launch_bounds__(256) void fa_offset_kernel(const uint32_t *__restrict__ kept, uint32_t nblocks,
+static __global__ __launch_bounds__(256) void fa_offset_kernel(const uint32_t *__restrict__ kept, uint32_t nblocks,
                                                         uint64_t *__restrict__ offs)
 {
     __shared__ uint64_t sh[4];
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(256) void fa_offset_kernel(const uint32_t *__restri
 }
 
 // K5: write the kept bytes of each block contiguously at offs[block].
-__global__ __launch_bounds__(kFaThreads) void fa_scatter_kernel(const uint8_t *__restrict__ in, uint64_t n,
+static __global__ __launch_bounds__(kFaThreads) void fa_scatter_kernel(const uint8_t *__restrict__ in, uint64_t n,
                                                                 const long long *__restrict__ carry, int start_state, int tail_trailing,
                                                                 const uint64_t *__restrict__ offs,
                                                                 uint8_t *__restrict__ flat)
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(kFaThreads) void fa_mark_scatter_kernel(const uint8
 }
 
 // starts of a batch of records relative to the batch's first byte (count_records_kernel takes them so)
-__global__ __launch_bounds__(256) void fa_rebase_kernel(const uint64_t *__restrict__ starts, uint64_t n, uint64_t base, uint64_t *__restrict__ out)
+static __global__ __launch_bounds__(256) void fa_rebase_kernel(const uint64_t *__restrict__ starts, uint64_t n, uint64_t base, uint64_t *__restrict__ out)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = starts[i] - base;

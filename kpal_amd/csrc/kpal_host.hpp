@@ -1,7 +1,8 @@
 // kpal_host.hpp -- host side shared by the translation units of libkpal_hip.so: errors, the context,
 // workspace buffers, per-kernel HIP-event timing, the launch / dispatch macros and the few host functions
 // one unit calls in another.  (kpal_ctx.hip: context + profiling API; kpal_count.hip: counting front end and the
-// round-1 pipelines; kpal_quads.hip / kpal_quads2.hip: the quad record pipelines; kpal_vec.hip: balance, split,
+// round-1 pipelines; kpal_text.hip: FASTA and FASTQ ingest; kpal_records.hip: one profile per record / per sliding window;
+// kpal_quads.hip / kpal_quads2.hip: the quad record pipelines; kpal_vec.hip: balance, split,
 // distances, matrices, options, summaries; kpal_cross.hip: the rectangle of distances between two sets; kpal_multi.hip: multi-GPU entry points over RCCL.)
 #pragma once
 #include "../../include/kpal_hip.h"
@@ -120,7 +121,7 @@ struct kpal_ctx {
     uint32_t chunk_meta_y = 0;               // coarse-bucket count the meta layout was cleared for
     uint32_t *chunk_error_word = nullptr;
     DevBuf residuals, cnt1, offs1, start1;  // two-level path (k = 13..16)
-    // FASTA ingest (kpal_count.hip): raw text and flattened stream of two chunks in flight, scan metadata, the flattened tail of
+    // FASTA ingest (kpal_text.hip): raw text and flattened stream of two chunks in flight, scan metadata, the flattened tail of
     // the previous chunk (the k-1 bytes the next one's first windows begin in), the chunks' flattened sizes in pinned host memory
     DevBuf fa_raw[2], fa_flat[2], fa_meta[2], fa_tail;
     // record index of the text of the last kpal_fasta_records_begin (from_fasta_by_record): raw text, flattened stream, scan metadata,
@@ -139,7 +140,7 @@ struct kpal_ctx {
     std::vector<uint64_t> win_first_host, win_tile_host;
     uint64_t win_window = 0, win_step = 0;
     uint64_t *fa_nflat_host = nullptr;
-    // FASTQ ingest (kpal_count.hip): raw text (carried rest of the chunk before + the chunk) and flattened stream of two chunks,
+    // FASTQ ingest (kpal_text.hip): raw text (carried rest of the chunk before + the chunk) and flattened stream of two chunks,
     // scan metadata and newline positions of the chunk being tokenised, its status words on the device and in pinned host memory
     DevBuf fq_raw[2], fq_flat[2], fq_meta, fq_pos, fq_status;
     unsigned long long *fq_status_host = nullptr;
@@ -311,7 +312,18 @@ double quad_expected_backlog(const std::vector<double> &mu, int slots);   // kpa
 constexpr double kQuadBacklogMax = 1500.0;   // quad_choose_steps: expected steady-state backlog a tile size may bring (list: 2048)
 int quad2_finalize(kpal_ctx *ctx, bool balance);                          // kpal_quads2.hip: no-op unless a finalisation is pending
 int quad2_resolve_fresh(kpal_ctx *ctx);                                   // kpal_quads2.hip: a FRESH piece whose lists overflowed is counted again (the fed buffer is read)
-int count_end_text(kpal_ctx *ctx);                                        // kpal_count.hip: an open FASTQ text is ended (its carried record counted, or the count abandoned)
+namespace kpal { struct FaSource; }   // fasta_host.hpp
+Span make_span(const uint8_t *addr, size_t n, size_t halo);               // kpal_count.hip: the k-mers ending in [addr, addr + n), `halo` readable bytes of the same feed left of addr
+int count_device_range(kpal_ctx *ctx, const uint8_t *addr, size_t n, size_t halo, int strategy = -1, size_t batch_bytes = 0);   // kpal_count.hip: a device range into the running count (strategy / batch_bytes: its own re-counts only)
+int ensure_pinned(kpal_ctx *ctx);                                         // kpal_count.hip: the two pinned staging buffers exist
+int pinned_wait(kpal_ctx *ctx, int slot);                                 // kpal_count.hip: before ctx->pinned[slot] is written
+int pinned_h2d(kpal_ctx *ctx, int slot, void *dst, const void *src, size_t n);   // kpal_count.hip: the DMA out of ctx->pinned[slot]
+void staged_memcpy(void *dst, const void *src, size_t n);                 // kpal_count.hip: host copy into a staging buffer on several cores
+int fa_flatten(kpal_ctx *ctx, const uint8_t *raw, uint64_t m, int state, int tail, uint8_t *flat, void *meta, uint64_t **offs_out,
+               void **rest = nullptr);                                    // kpal_text.hip: the FASTA flattening of raw[0, m) into flat
+int open_text_range(const char *path, uint64_t begin, uint64_t end, FaSource &src);   // kpal_text.hip: a byte range of a regular file, opened for sequential reading
+void fq_reset(kpal_ctx *ctx);                                             // kpal_text.hip: the unfinished FASTQ record of a count is dropped
+int count_end_text(kpal_ctx *ctx);                                        // kpal_text.hip: an open FASTQ text is ended (its carried record counted, or the count abandoned)
 int table_ready(kpal_ctx *ctx);                                           // kpal_quads2.hip: zeros materialised, pending finalisation done: the table is the table
 int launch_balance(kpal_ctx *ctx, int k, const int64_t *in, int64_t *out);   // kpal_vec.hip
 int check_options(const kpal_distance_options *opt);                       // kpal_vec.hip

@@ -1,0 +1,445 @@
+// kpal_records.hip -- one profile per record or per sliding window of a FASTA text: kpal_count_records, the record index over
+// memory and over a file the library reads itself (kpal_fasta_records_*), the sliding windows (kpal_fasta_windows_*).
+#include "kpal_host.hpp"
+
+#include "count_kernels.hpp"
+#include "count_plan.hpp"
+#include "fasta_kernels.hpp"
+#include "fasta_host.hpp"
+#include "window_kernels.hpp"
+
+#include <unistd.h>
+
+// one table per record: the k-mers of `s` into out[r], r the record (of the n that begin at starts[0 .. n]) their last byte lies in
+static int launch_count_records(kpal_ctx *ctx, int k, const Span &s, const uint64_t *starts, uint32_t n, unsigned long long *out)
+{
+    const WaveGrid w = wave_grid((s.nchunks + 63) / 64, ctx->num_cu, 8, 4);
+    DISPATCH_K_1_16(k, LAUNCH(ctx, "count_records", (count_records_kernel<K>), dim3(w.grid), dim3(256), s, w.spw, starts, n, out));
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_count_records(kpal_ctx *ctx, int k, const uint8_t *host_flat, size_t nbytes, const uint64_t *host_starts,
+                                size_t n_records, int64_t *host_out)
+{
+    CTX_ENTER(ctx);
+    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range 1..%d", k, KPAL_MAX_K);
+    if (n_records == 0) return KPAL_OK;
+    if (!host_starts || !host_out || (nbytes && !host_flat)) return set_err(KPAL_E_INVALID, "NULL pointer");
+    if (n_records >= 0xFFFFFFFFull) return set_err(KPAL_E_INVALID, "too many records in one batch");
+    if (host_starts[0] != 0 || host_starts[n_records] != nbytes) return set_err(KPAL_E_INVALID, "starts must run from 0 to nbytes");
+    for (size_t r = 0; r < n_records; ++r)
+        if (host_starts[r] > host_starts[r + 1]) return set_err(KPAL_E_INVALID, "starts must be ascending");
+    const uint64_t bins = 1ULL << (2 * k);
+    const size_t out_bytes = n_records * bins * sizeof(int64_t);
+    CHK(ensure(ctx, ctx->scratch[0], out_bytes));
+    CHK(ensure(ctx, ctx->scratch[1], nbytes + 64));
+    CHK(ensure(ctx, ctx->scratch[2], (n_records + 1) * sizeof(uint64_t)));
+    HIPCHK(hipMemsetAsync(ctx->scratch[0].p, 0, out_bytes, ctx->stream));
+    if (nbytes) {
+        HIPCHK(hipMemcpyAsync(ctx->scratch[1].p, host_flat, nbytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->scratch[2].p, host_starts, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        const Span s = make_span((const uint8_t *)ctx->scratch[1].p, nbytes, 0);
+        CHK(launch_count_records(ctx, k, s, (const uint64_t *)ctx->scratch[2].p, (uint32_t)n_records, (unsigned long long *)ctx->scratch[0].p));
+    }
+    HIPCHK(hipMemcpyAsync(host_out, ctx->scratch[0].p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return KPAL_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
+// Profile.from_fasta_by_record (kpal/klib.py:114-133) with the records tokenised on the device: the text (whole records; the
+// caller cuts at record boundaries) is flattened by the kernels of the FASTA ingest, and two compactions list where every record
+// starts in the flattened stream and where its header line starts in the text -- the host reads the header lines only (names).
+// kpal_fasta_records_count then counts batches of records into one table each (count_records_kernel), as many as the caller has
+// room for.
+// ----------------------------------------------------------------------------------------------
+// in_pinned0: host_text lies in ctx->pinned[0] (the file reader put it there): the DMA engine reads it in place
+static int fasta_records_index_text(kpal_ctx *ctx, const uint8_t *host_text, size_t nbytes, bool in_pinned0, uint64_t *n_records, uint64_t *flat_bytes)
+{
+    *n_records = *flat_bytes = 0;
+    ctx->rec_n = ctx->rec_nf = 0;
+    ctx->win_window = ctx->win_step = 0;
+    ctx->rec_starts_host.clear();
+    ctx->rec_hdr_host.clear();
+    const size_t first = nbytes ? fasta_first_header(host_text, nbytes, true) : 0;   // text before the first header is no record (klib.py:131: SeqIO)
+    if (first >= nbytes) return KPAL_OK;
+    const uint8_t *text = host_text + first;
+    const size_t m = nbytes - first;
+    const size_t pad = kpal_ctx::kStagePad;
+    const uint32_t nblocks = (uint32_t)((m + kFaBlockBytes - 1) / kFaBlockBytes);
+    CHK(ensure(ctx, ctx->rec_raw, m + 64));
+    CHK(ensure(ctx, ctx->rec_flat, m + pad + 64));
+    CHK(ensure(ctx, ctx->rec_meta, (size_t)nblocks * (8 + 8 + 4 + 4) + 2 * (size_t)(nblocks + 1) * 8 + 128));
+    uint8_t *raw = (uint8_t *)ctx->rec_raw.p;
+    uint8_t *flat = (uint8_t *)ctx->rec_flat.p + pad;
+    // text -> device through the pinned staging buffers (host threads copy piece i + 1 while the DMA takes piece i)
+    CHK(ensure_pinned(ctx));
+    if (in_pinned0) {
+        CHK(pinned_wait(ctx, 0));   // (an earlier DMA out of the buffer: long done, the caller has refilled it)
+        CHK(pinned_h2d(ctx, 0, raw, text, m));
+    } else {
+        const size_t stage = kpal_ctx::kStage;
+        int slot = 0;
+        for (size_t off = 0; off < m; off += stage, slot ^= 1) {
+            const size_t len = std::min(stage, m - off);
+            CHK(pinned_wait(ctx, slot));
+            staged_memcpy(ctx->pinned[slot], text + off, len);
+            CHK(pinned_h2d(ctx, slot, raw + off, ctx->pinned[slot], len));
+        }
+    }
+    // the flattening; behind its scratch the header lines' offsets (offs2) and the marks of both compactions
+    uint64_t *offs, *offs2;
+    CHK(fa_flatten(ctx, raw, m, 0, 1, flat, ctx->rec_meta.p, &offs, (void **)&offs2));
+    uint32_t *marks = (uint32_t *)(offs2 + nblocks + 1);
+    // header lines of the text
+    LAUNCH(ctx, "fa_mark_count", (fa_mark_count_kernel<1>), dim3(nblocks), dim3(kFaThreads), (const uint8_t *)raw, (uint64_t)m, marks);
+    LAUNCH(ctx, "fa_offset", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)marks, nblocks, offs2);
+    uint64_t sizes[2] = {0, 0};   // flattened bytes, records
+    HIPCHK(hipMemcpyAsync(&sizes[0], offs + nblocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&sizes[1], offs2 + nblocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const uint64_t nf = sizes[0], R = sizes[1];
+    if (R == 0 || nf < R) return set_err(KPAL_E_HIP, "record index: %llu records in %llu flattened bytes", (unsigned long long)R, (unsigned long long)nf);
+    CHK(ensure(ctx, ctx->rec_hdr, (size_t)R * 8));
+    CHK(ensure(ctx, ctx->rec_starts, (size_t)(R + 1) * 8));
+    LAUNCH(ctx, "fa_mark_scatter", (fa_mark_scatter_kernel<1>), dim3(nblocks), dim3(kFaThreads), (const uint8_t *)raw, (uint64_t)m, (const uint64_t *)offs2,
+           (uint64_t *)ctx->rec_hdr.p);
+    // record starts of the flattened stream: its '\n' bytes (offs / marks are free again: the flattening is done)
+    const uint32_t fblocks = (uint32_t)((nf + kFaBlockBytes - 1) / kFaBlockBytes);   // <= nblocks
+    LAUNCH(ctx, "fa_mark_count", (fa_mark_count_kernel<0>), dim3(fblocks), dim3(kFaThreads), (const uint8_t *)flat, nf, marks);
+    LAUNCH(ctx, "fa_offset", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)marks, fblocks, offs);
+    LAUNCH(ctx, "fa_mark_scatter", (fa_mark_scatter_kernel<0>), dim3(fblocks), dim3(kFaThreads), (const uint8_t *)flat, nf, (const uint64_t *)offs,
+           (uint64_t *)ctx->rec_starts.p);
+    uint64_t seps = 0;
+    HIPCHK(hipMemcpyAsync(&seps, offs + fblocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync((uint64_t *)ctx->rec_starts.p + R, &nf, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    ctx->rec_hdr_host.resize((size_t)R);
+    ctx->rec_starts_host.resize((size_t)R + 1);
+    HIPCHK(hipMemcpyAsync(ctx->rec_hdr_host.data(), ctx->rec_hdr.p, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->rec_starts_host.data(), ctx->rec_starts.p, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (seps != R) return set_err(KPAL_E_HIP, "record index: %llu header lines but %llu separators", (unsigned long long)R, (unsigned long long)seps);
+    ctx->rec_starts_host[(size_t)R] = nf;
+    for (uint64_t &h : ctx->rec_hdr_host) h += first;
+    ctx->rec_n = R;
+    ctx->rec_nf = nf;
+    *n_records = R;
+    *flat_bytes = nf;
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_fasta_records_begin(kpal_ctx *ctx, const uint8_t *host_text, size_t nbytes, uint64_t *n_records, uint64_t *flat_bytes)
+{
+    CTX_ENTER(ctx);
+    if (!n_records || !flat_bytes || (nbytes && !host_text)) return set_err(KPAL_E_INVALID, "NULL pointer");
+    return fasta_records_index_text(ctx, host_text, nbytes, false, n_records, flat_bytes);
+}
+
+// ---- the same over a FILE the library reads itself (fa_read: the pool's threads pread into the pinned staging buffer; no byte of the text
+// passes through Python): every kpal_fasta_records_file_next indexes the next piece of WHOLE records -- up to the end of line
+// before the last header line of what fits the 64 MiB staging buffer; the unfinished record behind it is carried to the next
+// piece; a record longer than the buffer is gathered in pageable memory first.
+static void fasta_records_file_reset(kpal_ctx *ctx)
+{
+    if (ctx->rec_fd >= 0) close(ctx->rec_fd);
+    ctx->rec_fd = -1;
+    ctx->rec_pos = ctx->rec_end = ctx->rec_piece_at = 0;
+    ctx->rec_carry.clear();
+    ctx->rec_carry.shrink_to_fit();
+}
+
+KPAL_API int kpal_fasta_records_file_open(kpal_ctx *ctx, const char *path, uint64_t begin, uint64_t end)
+{
+    CTX_ENTER(ctx);
+    if (!path) return set_err(KPAL_E_INVALID, "path is NULL");
+    fasta_records_file_reset(ctx);
+    FaSource src;
+    CHK(open_text_range(path, begin, end, src));
+    ctx->rec_fd = src.fd;
+    ctx->rec_pos = ctx->rec_piece_at = src.pos;
+    ctx->rec_end = src.end;
+    return KPAL_OK;
+}
+
+// index of the end-of-line byte before the LAST header line of buf[0, n) that begins at or after `from` (a '>' behind an
+// end of line), or n when there is none
+static size_t fasta_last_boundary(const uint8_t *buf, size_t n, size_t from)
+{
+    size_t i = n;
+    while (i > from + 1) {
+        const void *p = memrchr(buf + from + 1, '>', i - from - 1);
+        if (!p) break;
+        const size_t at = (size_t)((const uint8_t *)p - buf);
+        if (fa_host_is_eol(buf[at - 1])) return at - 1;
+        i = at;
+    }
+    return n;
+}
+
+KPAL_API int kpal_fasta_records_file_next(kpal_ctx *ctx, uint64_t *n_records, uint64_t *flat_bytes, uint64_t *text_offset, int *done)
+{
+    CTX_ENTER(ctx);
+    if (!n_records || !flat_bytes || !text_offset || !done) return set_err(KPAL_E_INVALID, "NULL pointer");
+    *n_records = *flat_bytes = *text_offset = 0;
+    *done = 1;
+    if (ctx->rec_fd < 0) return set_err(KPAL_E_STATE, "kpal_fasta_records_file_next without kpal_fasta_records_file_open");
+    CHK(ensure_pinned(ctx));
+    const size_t stage = std::min<size_t>(kpal_ctx::kStage, ctx->fa_chunk);   // (KPAL_FASTA_CHUNK: tests put the seams everywhere)
+    FaSource src;
+    src.fd = ctx->rec_fd;
+    for (;;) {
+        if (ctx->rec_carry.empty() && ctx->rec_pos >= ctx->rec_end) {   // the end
+            fasta_records_file_reset(ctx);
+            *n_records = *flat_bytes = *text_offset = 0;
+            *done = 1;
+            return KPAL_OK;
+        }
+        const size_t c = ctx->rec_carry.size();
+        const bool fits = c < stage;
+        const size_t want = (size_t)std::min<uint64_t>(fits ? stage - c : stage, ctx->rec_end - ctx->rec_pos);
+        uint8_t *buf;
+        if (fits) {   // the carried tail + the next bytes of the file into the pinned buffer
+            CHK(pinned_wait(ctx, 0));
+            buf = (uint8_t *)ctx->pinned[0];
+            if (c) memcpy(buf, ctx->rec_carry.data(), c);
+        } else {      // a record longer than the staging buffer: gathered in pageable memory, 64 MiB at a time
+            ctx->rec_carry.resize(c + want);
+            buf = ctx->rec_carry.data();
+        }
+        if (want) {
+            if (int e = fa_read(src, buf + c, ctx->rec_pos, want)) return set_err(KPAL_E_IO, "reading the FASTA input failed: %s", strerror(e));
+            ctx->rec_pos += want;
+        }
+        const size_t n = c + want;
+        const bool at_end = ctx->rec_pos >= ctx->rec_end;
+        // whole records: up to the end of line before the last header line (searched in the new bytes only; a boundary is two bytes)
+        const size_t cut = at_end ? n : fasta_last_boundary(buf, n, c ? c - 1 : 0);
+        if (cut >= n && !at_end) {   // no record ends in this piece: keep gathering
+            if (fits) ctx->rec_carry.assign(buf, buf + n);
+            continue;
+        }
+        const size_t piece = at_end ? n : cut + 1;
+        const uint64_t at = ctx->rec_piece_at;
+        const int rc = fasta_records_index_text(ctx, buf, piece, fits, n_records, flat_bytes);
+        if (rc != KPAL_OK) return rc;
+        // the unfinished record behind the piece is carried (the DMA out of the pinned buffer has been waited for: the index is complete)
+        std::vector<uint8_t> tail(buf + piece, buf + n);
+        ctx->rec_carry.swap(tail);
+        ctx->rec_piece_at = at + piece;
+        *text_offset = at;
+        *done = 0;
+        if (*n_records == 0 && !(ctx->rec_carry.empty() && at_end)) continue;   // (text before the first header only: next piece)
+        return KPAL_OK;
+    }
+}
+
+// Where the scan stands: the file offset of the first byte that no piece has covered yet (the start of the carried,
+// unfinished record).  A caller that lets other work use the context between two pieces keeps THIS, closes the scan and
+// opens it again there: the scan state of the context -- descriptor, position, carried bytes -- then never outlives a call.
+KPAL_API int kpal_fasta_records_file_tell(kpal_ctx *ctx, uint64_t *offset)
+{
+    CTX_ENTER(ctx);
+    if (!offset) return set_err(KPAL_E_INVALID, "NULL pointer");
+    if (ctx->rec_fd < 0) return set_err(KPAL_E_STATE, "kpal_fasta_records_file_tell without an open scan");
+    *offset = ctx->rec_piece_at;
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_fasta_records_file_close(kpal_ctx *ctx)
+{
+    CTX_ENTER(ctx);
+    fasta_records_file_reset(ctx);
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_fasta_records_index(kpal_ctx *ctx, uint64_t *header_off, uint64_t *flat_start)
+{
+    CTX_ENTER(ctx);
+    if (ctx->rec_n == 0) return set_err(KPAL_E_STATE, "kpal_fasta_records_index without records (kpal_fasta_records_begin)");
+    if (header_off) memcpy(header_off, ctx->rec_hdr_host.data(), (size_t)ctx->rec_n * 8);
+    if (flat_start) memcpy(flat_start, ctx->rec_starts_host.data(), (size_t)(ctx->rec_n + 1) * 8);
+    return KPAL_OK;
+}
+
+// the tables of records [first, first + n) of the indexed text into n x 4^k int64 of DEVICE memory (queued on the context's stream)
+static int fasta_records_count_into(kpal_ctx *ctx, int k, uint64_t first, uint64_t n, unsigned long long *dev_out)
+{
+    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range 1..%d", k, KPAL_MAX_K);
+    if (first > ctx->rec_n || n > ctx->rec_n - first) return set_err(KPAL_E_INVALID, "records %llu..%llu of %llu", (unsigned long long)first,
+                                                                      (unsigned long long)(first + n), (unsigned long long)ctx->rec_n);
+    if (n >= 0xFFFFFFFFull) return set_err(KPAL_E_INVALID, "too many records in one batch");
+    const uint64_t bins = 1ULL << (2 * k);
+    const size_t out_bytes = (size_t)n * bins * sizeof(int64_t);
+    const uint64_t b0 = ctx->rec_starts_host[(size_t)first], b1 = ctx->rec_starts_host[(size_t)(first + n)];
+    CHK(ensure(ctx, ctx->scratch[2], (size_t)(n + 1) * sizeof(uint64_t)));
+    HIPCHK(hipMemsetAsync(dev_out, 0, out_bytes, ctx->stream));
+    if (b1 > b0) {
+        LAUNCH(ctx, "fa_rebase", fa_rebase_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), (const uint64_t *)ctx->rec_starts.p + first, n + 1, b0,
+               (uint64_t *)ctx->scratch[2].p);
+        const Span s = make_span((const uint8_t *)ctx->rec_flat.p + kpal_ctx::kStagePad + b0, (size_t)(b1 - b0), 0);
+        CHK(launch_count_records(ctx, k, s, (const uint64_t *)ctx->scratch[2].p, (uint32_t)n, dev_out));
+    }
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_fasta_records_count(kpal_ctx *ctx, int k, uint64_t first, uint64_t n, int64_t *host_out)
+{
+    CTX_ENTER(ctx);
+    if (n == 0) return KPAL_OK;
+    if (!host_out) return set_err(KPAL_E_INVALID, "host_out is NULL");
+    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range 1..%d", k, KPAL_MAX_K);
+    const size_t out_bytes = (size_t)n * ((size_t)1 << (2 * k)) * sizeof(int64_t);
+    CHK(ensure(ctx, ctx->scratch[0], out_bytes));
+    CHK(fasta_records_count_into(ctx, k, first, n, (unsigned long long *)ctx->scratch[0].p));
+    HIPCHK(hipMemcpyAsync(host_out, ctx->scratch[0].p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return KPAL_OK;
+}
+
+// ... into the CALLER's device memory (kpal_dev_alloc): the profiles of a by-record scan that stay in HBM until something on the
+// host asks for their counts (kpal_amd/klib.py: Profile.counts is materialised lazily; distances and matrices of such profiles
+// read the device copies)
+KPAL_API int kpal_fasta_records_count_device(kpal_ctx *ctx, int k, uint64_t first, uint64_t n, int64_t *dev_out)
+{
+    CTX_ENTER(ctx);
+    if (n == 0) return KPAL_OK;
+    if (!dev_out) return set_err(KPAL_E_INVALID, "dev_out is NULL");
+    CHK(fasta_records_count_into(ctx, k, first, n, (unsigned long long *)dev_out));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // (the index may be overwritten by the caller's next piece)
+    return KPAL_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
+// Profile.from_fasta_by_window: one profile per sliding window of every indexed record (window_kernels.hpp; the layout
+// arithmetic is window_index.hpp).  Tile tables, running sum along the tiles, trim of the windows that end inside their
+// record: three launches per call (two when window == step), whatever window / step is.
+// ----------------------------------------------------------------------------------------------
+constexpr size_t kWinTileBytes = (size_t)2 << 30;   // tile tables of one pass (a longer range of windows is counted in several)
+
+// first window / first tile of every indexed record for (window, step), on the host and on the device
+static int fasta_windows_prepare(kpal_ctx *ctx, uint64_t W, uint64_t S)
+{
+    if (S < 1 || S > W || W % S != 0)
+        return set_err(KPAL_E_INVALID, "window=%llu step=%llu: need 1 <= step <= window and window %% step == 0", (unsigned long long)W, (unsigned long long)S);
+    if (W > (1ULL << 62)) return set_err(KPAL_E_INVALID, "window=%llu is too large", (unsigned long long)W);
+    if (ctx->rec_n == 0) return set_err(KPAL_E_STATE, "kpal_fasta_windows_* without records (kpal_fasta_records_begin)");
+    if (ctx->win_window == W && ctx->win_step == S) return KPAL_OK;
+    const size_t R = (size_t)ctx->rec_n;
+    ctx->win_window = ctx->win_step = 0;
+    ctx->win_first_host.resize(R + 1);
+    ctx->win_tile_host.resize(R + 1);
+    win_layout(ctx->rec_starts_host.data(), R, W, S, ctx->win_first_host.data(), ctx->win_tile_host.data());
+    CHK(ensure(ctx, ctx->win_index, 2 * (R + 1) * sizeof(uint64_t)));
+    HIPCHK(hipMemcpyAsync(ctx->win_index.p, ctx->win_first_host.data(), (R + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync((uint64_t *)ctx->win_index.p + R + 1, ctx->win_tile_host.data(), (R + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->win_window = W;
+    ctx->win_step = S;
+    return KPAL_OK;
+}
+
+// windows [first, first + n) -- made from the tiles and bytes of `rg` -- into n x 4^k int64 of device memory
+static int fasta_windows_pass(kpal_ctx *ctx, int k, uint64_t W, uint64_t S, uint64_t first, uint64_t n, const WinRange &rg, unsigned long long *dev_out)
+{
+    const uint64_t bins = 1ULL << (2 * k), m = W / S;
+    const uint64_t R = ctx->rec_n, ntiles = rg.tile1 - rg.tile0;
+    const uint64_t *index = (const uint64_t *)ctx->win_index.p;
+    const WinGeom g = {(const uint64_t *)ctx->rec_starts.p, index, index + R + 1, R, W, S, first, n, rg.tile0, rg.tile1};
+    const uint8_t *flat = (const uint8_t *)ctx->rec_flat.p + kpal_ctx::kStagePad;
+    unsigned long long *tiles = dev_out;   // window == step: the tiles are the windows
+    if (m > 1) {
+        CHK(ensure(ctx, ctx->win_tiles, (size_t)ntiles * bins * sizeof(int64_t)));
+        tiles = (unsigned long long *)ctx->win_tiles.p;
+    }
+    if (k <= 7 && S < (1ULL << 32)) {   // histograms in LDS (u32 bins: a tile holds fewer than 2^32 k-mers)
+        const Span s = make_span(flat, (size_t)ctx->rec_nf, 0);
+        if (S <= 2048) {
+            DISPATCH_K_1_7(k, {
+                constexpr int TPW = WinTileCfg<K>::kSmallTpw;
+                const unsigned grid = (unsigned)std::min<uint64_t>((ntiles + TPW - 1) / TPW, (uint64_t)ctx->num_cu * 8);
+                LAUNCH(ctx, "window_tiles", (window_tiles_lds_kernel<K, TPW, 4>), dim3(grid), dim3(256), s, g, tiles);
+            });
+        } else {
+            const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, (uint64_t)ctx->num_cu * 4);
+            DISPATCH_K_1_7(k, LAUNCH(ctx, "window_tiles", (window_tiles_lds_kernel<K, 1, 8>), dim3(grid), dim3(512), s, g, tiles));
+        }
+    } else {
+        HIPCHK(hipMemsetAsync(tiles, 0, (size_t)ntiles * bins * sizeof(int64_t), ctx->stream));
+        const Span s = make_span(flat + rg.byte0, (size_t)(rg.byte1 - rg.byte0), 0);
+        const WaveGrid w = wave_grid((s.nchunks + 63) / 64, ctx->num_cu, 8, 4);
+        DISPATCH_K_1_16(k, LAUNCH(ctx, "window_tiles_atomic", (window_tiles_atomic_kernel<K>), dim3(w.grid), dim3(256), s, w.spw, rg.byte0, g, tiles));
+    }
+    if (m > 1) {
+        // segments of at least m windows (the m loads of a segment's first sum then cost no more than one per window),
+        // longer ones once the device is full
+        const uint64_t threads = (uint64_t)ctx->num_cu * 2048;
+        const uint64_t segment = std::max<uint64_t>(m, (n * bins + threads - 1) / threads);
+        const uint64_t n_segments = (n + segment - 1) / segment;
+        const uint64_t blocks = bins < (uint64_t)kWinSlideThreads ? (n_segments + kWinSlideThreads / bins - 1) / (kWinSlideThreads / bins)
+                                                                   : n_segments * (bins / kWinSlideThreads);
+        if (blocks > 0x7FFFFFFFull) return set_err(KPAL_E_INVALID, "too many windows in one batch");
+        LAUNCH(ctx, "window_slide", window_slide_kernel, dim3((unsigned)blocks), dim3(kWinSlideThreads), g, bins, segment, n_segments,
+               (const unsigned long long *)tiles, dev_out);
+    }
+    LAUNCH(ctx, "window_trim", window_trim_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), g, k, flat, dev_out);
+    return KPAL_OK;
+}
+
+static int fasta_windows_count_into(kpal_ctx *ctx, int k, uint64_t W, uint64_t S, uint64_t first, uint64_t n, unsigned long long *dev_out)
+{
+    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range 1..%d", k, KPAL_MAX_K);
+    CHK(fasta_windows_prepare(ctx, W, S));
+    if ((uint64_t)k > W) return set_err(KPAL_E_INVALID, "k=%d is longer than the window (%llu)", k, (unsigned long long)W);
+    const uint64_t R = ctx->rec_n, total = ctx->win_first_host[(size_t)R];
+    if (first > total || n > total - first) return set_err(KPAL_E_INVALID, "windows %llu..%llu of %llu", (unsigned long long)first,
+                                                           (unsigned long long)(first + n), (unsigned long long)total);
+    if (n >= 0x7FFFFFFFull * 256) return set_err(KPAL_E_INVALID, "too many windows in one batch");
+    const uint64_t bins = 1ULL << (2 * k);
+    const uint64_t cap = std::max<uint64_t>(1, kWinTileBytes / (bins * sizeof(int64_t)));
+    const uint64_t *starts = ctx->rec_starts_host.data(), *fw = ctx->win_first_host.data(), *ft = ctx->win_tile_host.data();
+    for (uint64_t done = 0; done < n;) {
+        uint64_t c = n - done;
+        WinRange rg = win_range(starts, fw, ft, R, k, W, S, first + done, c);
+        while (W != S && rg.tile1 - rg.tile0 > cap && c > 1) {   // (the tile tables of a pass stay within kWinTileBytes)
+            c = (c + 1) / 2;
+            rg = win_range(starts, fw, ft, R, k, W, S, first + done, c);
+        }
+        CHK(fasta_windows_pass(ctx, k, W, S, first + done, c, rg, dev_out + done * bins));
+        done += c;
+    }
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_fasta_windows_layout(kpal_ctx *ctx, uint64_t window, uint64_t step, uint64_t *n_windows, uint64_t *first_window)
+{
+    CTX_ENTER(ctx);
+    if (!n_windows) return set_err(KPAL_E_INVALID, "NULL pointer");
+    *n_windows = 0;
+    CHK(fasta_windows_prepare(ctx, window, step));
+    *n_windows = ctx->win_first_host[(size_t)ctx->rec_n];
+    if (first_window) memcpy(first_window, ctx->win_first_host.data(), (size_t)(ctx->rec_n + 1) * 8);
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_fasta_windows_count(kpal_ctx *ctx, int k, uint64_t window, uint64_t step, uint64_t first, uint64_t n, int64_t *host_out)
+{
+    CTX_ENTER(ctx);
+    if (n && !host_out) return set_err(KPAL_E_INVALID, "host_out is NULL");
+    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range 1..%d", k, KPAL_MAX_K);
+    const size_t out_bytes = (size_t)n * ((size_t)1 << (2 * k)) * sizeof(int64_t);
+    if (n) CHK(ensure(ctx, ctx->scratch[0], out_bytes));
+    CHK(fasta_windows_count_into(ctx, k, window, step, first, n, (unsigned long long *)ctx->scratch[0].p));
+    if (n == 0) return KPAL_OK;
+    HIPCHK(hipMemcpyAsync(host_out, ctx->scratch[0].p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_fasta_windows_count_device(kpal_ctx *ctx, int k, uint64_t window, uint64_t step, uint64_t first, uint64_t n, int64_t *dev_out)
+{
+    CTX_ENTER(ctx);
+    if (n && !dev_out) return set_err(KPAL_E_INVALID, "dev_out is NULL");
+    CHK(fasta_windows_count_into(ctx, k, window, step, first, n, (unsigned long long *)dev_out));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // (the index may be overwritten by the caller's next piece)
+    return KPAL_OK;
+}

@@ -992,7 +992,7 @@ def test_k12_staged_forms_and_fused_balance():
 
 @pytest.mark.gpu
 def test_auto_two_level_choice_fresh_and_later_pieces(ctx):
-    """AUTO at k >= 13 (kpal_count.hip: count_device_range): the FIRST piece of a count that is a whole device buffer of at least
+    """AUTO at k >= 13 (count_plan.hpp: plan_strategy / kpal_count.hip: count_device_range): the FIRST piece of a count that is a whole device buffer of at least
     64 MiB and an eighth of a byte per table entry goes through the two-level quad pipeline (FRESH table, fused balance); a later
     piece only once it holds three bytes per entry -- below that the round-1 two-level pipeline adds into the finished table.
     Both orders, with and without the balance, against the oracle run on the whole input."""
