@@ -34,14 +34,12 @@ KPAL_API int kpal_count_begin(kpal_ctx *ctx, int k)
     // table in its finalisation and never needs it (kpal_quads2.hip, FRESH); whatever else touches the table first zeroes it (table_ready)
     static const bool allow_fresh = [] { const char *e = getenv("KPAL_FRESH"); return !e || atoi(e) != 0; }();
     ctx->table_zero_pending = allow_fresh && k >= 13 && (ctx->strategy == KPAL_STRATEGY_AUTO || ctx->strategy == KPAL_STRATEGY_PARTITION2_QUADS);
-    ctx->finalize_fresh = false;
     if (!ctx->table_zero_pending) HIPCHK(hipMemsetAsync(ctx->table.p, 0, ctx->bins * sizeof(int64_t), ctx->stream));
     if (ctx->chunk_error_word) HIPCHK(hipMemsetAsync(ctx->chunk_error_word, 0, sizeof(uint32_t), ctx->stream));
     if (ctx->quad_error_word) HIPCHK(hipMemsetAsync(ctx->quad_error_word, 0, sizeof(uint32_t), ctx->stream));
     ctx->chunk_error_armed = false;
-    ctx->finalize_pending = false;          // (staged forms of an abandoned count)
-    ctx->cached_steps1 = ctx->cached_steps2 = 0;
-    ctx->sample_hot_rows = false;           // (the verdict of a sample of THIS count only: kpal_quads2.hip reads it for cached tile sizes)
+    ctx->fin.clear();                       // (staged forms of an abandoned count)
+    ctx->tiles.clear();                     // (tile sizes and verdict of a sample of THIS count only)
     ctx->plan_strategy = ctx->plan_steps1 = ctx->plan_steps2 = 0;
     fq_reset(ctx);                          // (the unfinished FASTQ record of an abandoned count)
     ctx->counting = true;
@@ -601,7 +599,7 @@ KPAL_API int kpal_count_balance(kpal_ctx *ctx)
     if (!ctx->counting) return set_err(KPAL_E_STATE, "kpal_count_balance before kpal_count_begin");
     CHK(count_end_text(ctx));   // (a FASTQ record still carried belongs to the table that is balanced)
     // two-level quad pipeline: the pending finalisation of the table balances it in the same pass
-    if (ctx->finalize_pending) return quad2_finalize(ctx, true);
+    if (ctx->fin.pending) return quad2_finalize(ctx, true);
     CHK(table_ready(ctx));
     return launch_balance(ctx, ctx->k, (const int64_t *)ctx->table.p, (int64_t *)ctx->table.p);
 }

@@ -2,7 +2,7 @@
 // workspace buffers, per-kernel HIP-event timing, the launch / dispatch macros and the few host functions
 // one unit calls in another.  (kpal_ctx.hip: context + profiling API; kpal_count.hip: counting front end and the
 // round-1 pipelines; kpal_text.hip: FASTA and FASTQ ingest; kpal_records.hip: one profile per record / per sliding window;
-// kpal_quads.hip / kpal_quads2.hip: the quad record pipelines; kpal_vec.hip: balance, split,
+// kpal_quads.hip / kpal_quads2.hip: the quad record pipelines, planned by quad_plan.hpp; kpal_vec.hip: balance, split,
 // distances, matrices, options, summaries; kpal_cross.hip: the rectangle of distances between two sets; kpal_multi.hip: multi-GPU entry points over RCCL.)
 #pragma once
 #include "../../include/kpal_hip.h"
@@ -22,6 +22,7 @@
 
 #include "kpal_device.hpp"
 #include "host_pool.hpp"
+#include "quad_plan.hpp"
 
 #define KPAL_API extern "C" __attribute__((visibility("default")))
 
@@ -60,6 +61,47 @@ struct ProfRec {
     hipEvent_t a, b;
 };
 
+// The staged forms of the last quad piece that have not been added to the table yet (quad2_finalize; armed by
+// launch_partition_quads at k = 12 and by launch_partition2_quads).  FRESH (kpal_quads2.hip): kpal_count_begin leaves the table
+// of a k >= 13 count UNZEROED (kpal_ctx::table_zero_pending) -- the first piece, if it is a whole device feed on the two-level
+// quad pipeline, lets its finalisation WRITE the table instead of adding to it, and keeps the few counts that bypass the
+// records in lists until then.  Every other consumer of the table materialises the zeros first (table_ready).
+//   idle --arm--> pending [fresh: --resolve--> resolved (lists fit) | --clear--> idle, the piece armed again classically]
+//   pending --take--> idle (the finalisation is launched);  kpal_count_begin: clear (staged forms of an abandoned count)
+struct QuadFinalize {
+    bool pending = false;
+    const void *stage = nullptr;
+    bool fresh = false;
+    bool resolved = false;        // the overflow word of the pending FRESH piece has been read (quad2_resolve_fresh)
+    Span span = {};               // the piece of a FRESH finalisation (re-run classically if a list overflowed)
+    uint32_t nseg = 0;            // list segments of that piece
+    uint32_t seg = 16384;         // ... entries of each (sixteen times kpal_ctx::direct_seg for a feed with hot rows)
+    uint32_t seg_hist = 16384;    // ... and of the last one (histogram stage, shared)
+
+    void arm(const void *stage_, bool fresh_ = false, const Span &span_ = {}, uint32_t nseg_ = 0, uint32_t seg_ = 0, uint32_t seg_hist_ = 0)
+    {
+        pending = true;
+        stage = stage_;
+        fresh = fresh_;
+        resolved = false;
+        if (fresh_) {
+            span = span_;
+            nseg = nseg_;
+            seg = seg_;
+            seg_hist = seg_hist_;
+        }
+    }
+    bool needs_resolve() const { return pending && fresh && !resolved; }
+    void resolve() { resolved = true; }
+    bool take()   // -> whether the finalisation that is launched now is a FRESH one
+    {
+        const bool was_fresh = fresh;
+        pending = fresh = false;
+        return was_fresh;
+    }
+    void clear() { pending = fresh = false; }
+};
+
 struct kpal_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -86,35 +128,18 @@ struct kpal_ctx {
     int quad_steps_forced = 0, quad_steps2_forced = 0;   // KPAL_QUAD_STEPS / KPAL_QUAD_STEPS2 at context creation (tests, A/B): tile sizes of the quad scatters
     bool quad_verbose = false;               // KPAL_QUAD_VERBOSE
     int quad_repeat_forced = -1;             // KPAL_QUAD_REPEAT=0 / 1: the scatter instantiation without / with the repeat lanes' shortcut (-1: by the sample)
-    bool sample_hot_rows = false;            // the last row-load sample showed hot rows (quad_choose_steps)
     // what the last piece of the last feed took (kpal_count_last_plan): strategy, wave-steps per wave and tile of level 1 / level 2
     int plan_strategy = 0, plan_steps1 = 0, plan_steps2 = 0;
     // kpal_count_stats: pieces by pipeline and the FRESH pieces / re-runs, since the context was created
     uint64_t stat_fresh_pieces = 0, stat_fresh_reruns = 0, stat_quad_pieces = 0, stat_chunked_pieces = 0, stat_split_pieces = 0, stat_repeat_pieces = 0;
-    // tile sizes chosen from the sample of an earlier feed of this count (kpal_count_begin clears them): a file streamed in
-    // many feeds is sampled once per 16 feeds, not once per feed (the sample costs a D2H copy + a host synchronisation)
-    int cached_steps1 = 0, cached_steps2 = 0;
-    uint32_t cached_uses = 0;
-    size_t cached_bytes = 0;
-    // two-level quad pipeline: the staged forms of the last piece have not been added to the table yet (quad2_finalize)
-    bool finalize_pending = false;
-    const void *finalize_stage = nullptr;
-    // FRESH mode of that pipeline (kpal_quads2.hip): kpal_count_begin leaves the table of a k >= 13 count UNZEROED
-    // (table_zero_pending) -- the first piece, if it is a whole device feed on the two-level quad pipeline, lets its
-    // finalisation WRITE the table instead of adding to it, and keeps the few counts that bypass the records in lists until
-    // then (finalize_fresh).  Every other consumer of the table materialises the zeros first (table_ready).
-    bool table_zero_pending = false;
-    bool finalize_fresh = false;
-    bool fresh_resolved = false;             // the overflow word of the pending FRESH piece has been read (quad2_resolve_fresh)
+    QuadTileCache tiles;                     // tile sizes and verdict of the last sample of this count (kpal_count_begin clears them)
+    QuadFinalize fin;                        // the pending finalisation of the last quad piece
+    bool table_zero_pending = false;         // the table of this k >= 13 count has not been zeroed yet (FRESH: QuadFinalize)
     bool fresh_feed = false;                 // set by kpal_count_feed_device around count_device_range: a whole device feed
-    Span fresh_span = {};                    // the piece of a FRESH finalisation (re-run classically if a list overflowed)
     DevBuf direct_list, direct_meta;         // TableSink segments ((index << 32) | count entries); per-segment counts + overflow word
     uint32_t direct_seg = 16384;             // entries per segment (KPAL_DIRECT_SEG: tests force the overflow path)
-    uint32_t direct_seg_used = 16384;        // ... of the current lists (sixteen times that for a feed with hot rows)
-    bool quad_hist_unpacked = false;         // KPAL_HIST_PACKED=0: the 128 KiB histogram at every k (A/B, tests)
     bool direct_seg_forced = false;          // ... then the histogram stage's segment is as small
-    uint32_t direct_seg_hist = 16384;        // entries of the last segment (histogram stage, shared) of the current lists
-    uint32_t direct_nseg = 0;                // segments in use by the pending finalisation
+    bool quad_hist_unpacked = false;         // KPAL_HIST_PACKED=0: the 128 KiB histogram at every k (A/B, tests)
     int level2_mode = 2;                     // level 2 of the two-level path (KPAL_LEVEL2): 0 count + exact offsets, 1 chunked per-tile runs, 2 chunked aligned lines (default)
     alignas(16) unsigned char chunk_pool_sent[96] = {};   // (ChunkPool) what the device copy of the pool descriptor holds
     void *chunk_pool_dev = nullptr;
@@ -306,10 +331,14 @@ constexpr int kQuadsUseChunked = 2;   // launch_partition*_quads (AUTO): the sam
 constexpr int kSplitBatch = 1;        // launch_partition2 / launch_partition*_quads: the caller halves the piece
 int launch_partition_quads(kpal_ctx *ctx, const Span &s);                 // kpal_quads.hip
 int launch_partition2_quads(kpal_ctx *ctx, const Span &s, bool fresh = false);   // kpal_quads2.hip
-int quad_choose_steps(kpal_ctx *ctx, const Span &s, uint32_t *load, int buckets, int slots, int waves, const int *candidates,
-                      size_t n_candidates, int *steps_out, std::vector<double> *fine_per_step = nullptr);   // kpal_quads.hip
-double quad_expected_backlog(const std::vector<double> &mu, int slots);   // kpal_quads.hip
-constexpr double kQuadBacklogMax = 1500.0;   // quad_choose_steps: expected steady-state backlog a tile size may bring (list: 2048)
+struct QuadMeta {   // kpal_ctx::quad_meta
+    uint32_t *nrounds;   // rounds per (level-1) scatter workgroup
+    uint32_t *error;     // the error word and the three statistics words behind it
+    uint32_t *load;      // the counters of the row-load sample
+};
+int quad_meta(kpal_ctx *ctx, QuadMeta *out);                              // kpal_quads.hip: that buffer exists, the error word is armed
+int quad_choose_steps(kpal_ctx *ctx, const Span &s, uint32_t *load, int buckets, int slots, const int *candidates, size_t n_candidates,
+                      int *steps_out, std::vector<double> *fine = nullptr);   // kpal_quads.hip: sample a piece; ctx->tiles.hot_rows and the level-1 size (or kQuadsUseChunked)
 int quad2_finalize(kpal_ctx *ctx, bool balance);                          // kpal_quads2.hip: no-op unless a finalisation is pending
 int quad2_resolve_fresh(kpal_ctx *ctx);                                   // kpal_quads2.hip: a FRESH piece whose lists overflowed is counted again (the fed buffer is read)
 namespace kpal { struct FaSource; }   // fasta_host.hpp

@@ -20,7 +20,7 @@
 //     -- no cursors, no chunk allocation, no tables: the histogram stage reads pool[bucket] as one stream.
 //   * A row that overflows (Poisson tail, 1-3 % of the items) spills into a small LDS list whose
 //     entries are placed again at the start of the next round; the host sizes the tile so that the
-//     steady-state backlog of that list stays small (kpal_hip.hip: quad_expected_backlog).  Items that do
+//     steady-state backlog of that list stays small (quad_plan.hpp: quad_expected_backlog).  Items that do
 //     not fit even then, or that the list cannot hold (a row that is over-full every round: homopolymers,
 //     satellite repeats), are counted on the spot: ballot-aggregated per wave into a 256-entry (row, item)
 //     hash table in LDS that is added to the count table once per workgroup.  No round is ever abandoned,
@@ -37,11 +37,11 @@
 
 #include "kpal_device.hpp"
 #include "quad2_index.hpp"
+#include "quad_plan.hpp"   // kQuadRowWords (128 KiB of rows), kQuadPackedRecordBytes
 
 namespace kpal {
 
 constexpr int kQuadSpillCap = 2048;           // spilled items a round may carry over (16 KiB of LDS)
-constexpr int kQuadRowWords = 32768;          // 128 KiB of rows
 constexpr int kQuadDummyWords = 4;            // words behind the rows that lanes without a slot write to
 
 template <int K>
@@ -170,7 +170,6 @@ __device__ __forceinline__ uint4 quad_unpack3(uint32_t a, uint32_t b, uint32_t c
     v.w = (c >> 5) & 0x7FFFFFu;
     return v;
 }
-constexpr int kQuadPackedRecordBytes = 192;   // 64 items
 
 struct QuadSpill {
     uint32_t row, item;

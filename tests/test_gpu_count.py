@@ -249,6 +249,35 @@ def test_quad_tile_sizes_against_oracle(steps):
     c2.close()
 
 
+def test_quad_tile_sizes_are_sampled_once_per_16_feeds():
+    """A count streamed in feeds of about one size samples its row loads for the first feed and keeps the tile sizes for the
+    next 16 (quad_plan.hpp: QuadTileCache); the 18th feed samples again, and so does a feed of more than twice the kept size.
+    Seen in the launches of quad_sample, one- and two-level; the table is the sum of the feeds."""
+    from kpal_amd import _native
+    c2 = _native.Context(_native.default_device())
+    c2.prof_enable(True)
+    small = oracle.synth_reads(67, 0, 13889, 150)[:2 << 20]
+    large = oracle.synth_reads(68, 0, 41666, 150)[:6 << 20]
+
+    def samples():
+        c2.sync()
+        return c2.prof_get().get('quad_sample', (0.0, 0))[1]
+    for k, strategy in ((10, 'partition_quads'), (12, 'partition_quads'), (13, 'partition2_quads')):
+        c2.prof_reset()
+        c2.count_begin(k, strategy)
+        for _ in range(17):
+            c2.count_feed(small)
+        assert samples() == 1, k
+        c2.count_feed(small)
+        assert samples() == 2, k
+        c2.count_feed(large)
+        assert samples() == 3, k
+        assert c2.count_last_plan()[0] == strategy
+        want = 18 * oracle.count_flat(small, k, threads=8) + oracle.count_flat(large, k, threads=8)
+        assert np.array_equal(c2.count_finish(), want), k
+    c2.close()
+
+
 def test_quad_pipelines_halve_an_oversized_piece():
     """A piece whose record pool would pass the limit of the quad scatters' 32-bit record offsets is counted as two
     halves, recursively (forced here by lowering the limit to 4 MiB); halo across the seams of the halves."""
