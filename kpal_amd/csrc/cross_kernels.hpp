@@ -47,16 +47,7 @@ __device__ __forceinline__ void cross_tile(uint32_t t, int side, bool tri, int &
     tj = (int)(t - i * (i + 1u) / 2u);
 }
 
-__device__ __forceinline__ uint32_t cross_tile_number(int ti, int tj, int side, bool tri)
-{
-    return tri ? (uint32_t)ti * ((uint32_t)ti + 1u) / 2u + (uint32_t)tj : (uint32_t)ti * (uint32_t)side + (uint32_t)tj;
-}
-
-// Slot of pair (i, j) among the 16 * tiles of one accumulator.
-__device__ __forceinline__ uint64_t cross_slot(const CrossSets &c, int sideR, int i, int j)
-{
-    return (uint64_t)cross_tile_number(i >> 2, j >> 2, sideR, c.tri != 0) * 16u + (uint64_t)((i & 3) * 4 + (j & 3));
-}
+// (the other way, cross_tile_number, and cross_slot, the slot of a pair: matrix_plan.hpp -- the host finds the pairs with them)
 
 // Staged row r of super-tile (si, sj): rows 0..15 are left profiles, 16..31 right ones.
 __device__ __forceinline__ const int64_t *cross_row(const CrossSets &c, int si, int sj, int r)

@@ -24,7 +24,6 @@
 
 namespace kpal {
 
-constexpr int kGramBins = 64;
 constexpr int kGramRow = 66;
 typedef double gram_v4f64 __attribute__((ext_vector_type(4)));
 

@@ -1,78 +1,154 @@
-// kpal_cross.hip -- kpal_cross_distance[_device]: the Q x R rectangle of distances between a left and a right set of
-// profiles in separate allocations (cross_kernels.hpp); cross_pairs also runs the lower triangle of kpal_vec.hip's matrices.  One call is a fixed number of launches whatever Q and R are:
-// the balance of each profile (do_balance), one rectangle kernel (two when a fast form gives up on the values), one
-// fixed-order reduction of the per-workgroup partials.
-// kpal_cross_profile_distance[_device] / kpal_profile_distance_matrix_device: the same rectangle, and the lower triangle of one
-// set, for a ProfileDistance with options (cross_option_kernels.hpp) -- a totals pass or a masked-totals rectangle pass more when
-// the profiles are scaled; dynamic smoothing alone stays one pair pipeline per pair, on tables balanced once.
+// kpal_cross.hip -- everything of the C-ABI that works on SETS of profiles: the lower triangle of one set
+// (kpal_distance_matrix[_device], kdistlib.distance_matrix) and the Q x R rectangle between a left and a right set in separate
+// allocations (kpal_cross_distance[_device]), plain and -- kpal_profile_distance_matrix[_device],
+// kpal_cross_profile_distance[_device] -- for a ProfileDistance with options.  What is decided before a launch (which kernels,
+// the grids, where a pair's partial lies) is matrix_plan.hpp.
+//   plain: one call is a fixed number of launches whatever P, Q and R are -- the balance of each profile (do_balance), one
+// kernel over all pairs (cross_kernels.hpp: the triangle is the set crossed with itself; two kernels when a fast form gives up
+// on the values; matrix_all_kernels.hpp for a multiset triangle of 17..64 profiles; the fp64 Gram matrix on the matrix cores
+// for euclidean), one fixed-order reduction of the per-workgroup partials.
+//   with options (cross_option_kernels.hpp): a totals pass or a masked-totals rectangle pass more when the profiles are scaled;
+// dynamic smoothing alone stays one pair pipeline (kpal_pair.hip) per pair, on tables balanced once.
 #include "kpal_host.hpp"
 
 #include "cross_kernels.hpp"
 #include "cross_option_kernels.hpp"
+#include "matrix_all_kernels.hpp"
 
-// Euclidean from the fp64 dot products of cross_gram_kernel and the norms of cross_norm_kernel.  *exact = false (and
-// `out` untouched) when some |x|^2 >= 2^53 -- gram_euclidean's rule: the caller then takes the wrapping-int64 kernel.
+static const MatrixSwitches &matrix_switches()
+{
+    static const MatrixSwitches sw = [] {
+        auto on = [](const char *name) { const char *e = getenv(name); return !e || atoi(e) != 0; };
+        return MatrixSwitches{on("KPAL_MATRIX_MFMA"), on("KPAL_MATRIX_SUPER"), on("KPAL_MATRIX_ALL"), on("KPAL_MATRIX_RDIFF")};
+    }();
+    return sw;
+}
+
+// `count` host profiles of n bins, one behind the other at dst; what: "profile", "left profile", "right profile".
+static int upload_set(kpal_ctx *ctx, int64_t *dst, int count, uint64_t n, const int64_t *const *host, const char *what)
+{
+    for (int p = 0; p < count; ++p) {
+        if (!host[p]) return set_err(KPAL_E_INVALID, "%s %d is NULL", what, p);
+        HIPCHK(hipMemcpyAsync(dst + (uint64_t)p * n, host[p], n * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return KPAL_OK;
+}
+
+// The left and the right set of a rectangle, one behind the other in scratch[0].
+static int upload_rectangle(kpal_ctx *ctx, uint64_t n, int Q, const int64_t *const *host_left, int R, const int64_t *const *host_right,
+                            int64_t **dl, int64_t **dr)
+{
+    CHK(ensure(ctx, ctx->scratch[0], ((size_t)Q + (size_t)R) * n * 8));
+    *dl = (int64_t *)ctx->scratch[0].p;
+    *dr = *dl + (uint64_t)Q * n;
+    CHK(upload_set(ctx, *dl, Q, n, host_left, "left profile"));
+    return upload_set(ctx, *dr, R, n, host_right, "right profile");
+}
+
+// Balanced copies of `count` consecutive tables at `dst` (one launch_balance per profile).
+static int balance_set(kpal_ctx *ctx, int k, int count, const int64_t *src, int64_t *dst)
+{
+    const uint64_t n = 1ULL << (2 * k);
+    for (int p = 0; p < count; ++p) CHK(launch_balance(ctx, k, src + (uint64_t)p * n, dst + (uint64_t)p * n));
+    return KPAL_OK;
+}
+
+// Balanced copies of the sets of c (a triangle: of its one set) in scratch[2]; c names them from here on.  Balanced once per
+// profile: identical to the reference balancing copies per pair (kdistlib.py:136-141).
+static int balance_sets(kpal_ctx *ctx, int k, CrossSets &c)
+{
+    CHK(ensure(ctx, ctx->scratch[2], ((size_t)c.Q + (c.tri ? 0 : (size_t)c.R)) * c.n * 8));
+    int64_t *bl = (int64_t *)ctx->scratch[2].p, *br = c.tri ? bl : bl + (uint64_t)c.Q * c.n;
+    CHK(balance_set(ctx, k, c.Q, c.left, bl));
+    if (!c.tri) CHK(balance_set(ctx, k, c.R, c.right, br));
+    c.left = bl;
+    c.right = br;
+    return KPAL_OK;
+}
+
+// A reciprocal form (cross_recip_kernel, matrix_r*_all_kernel) over the `count` cleared partials at pp: `launch` runs it, and
+// *done says whether it saw no count it is not valid for -- the word `big`, of which big_bytes are cleared before, stayed 0.
+template <class Launch>
+static int try_recip(kpal_ctx *ctx, uint32_t *big, size_t big_bytes, Partial *pp, size_t count, Launch launch, bool *done)
+{
+    HIPCHK(hipMemsetAsync(big, 0, big_bytes, ctx->stream));
+    HIPCHK(hipMemsetAsync(pp, 0, count * sizeof(Partial), ctx->stream));   // (.s / .m of a slot come from different threads)
+    CHK(launch());
+    uint32_t saw_big = 0;
+    HIPCHK(hipMemcpyAsync(&saw_big, big, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *done = saw_big == 0;
+    return KPAL_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
+// plain metrics
+// ----------------------------------------------------------------------------------------------
+// Euclidean distances of all pairs of a triangle from the fp64 Gram matrix (gram_kernels.hpp).  *exact = false (and
+// out_lower untouched) when some |x|^2 >= 2^53: the caller then takes the wrapping-int64 path.
+static int gram_euclidean(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof, double *out_lower, bool *exact, bool allreduce)
+{
+    static_assert(sizeof(GramBlock) == sizeof(int2), "gram_mfma_kernel reads the block list as int2");
+    const GramPlan g = gram_plan(ctx->num_cu, P, n);
+    const uint32_t nd = g.nd, no = g.no;
+    CHK(ensure(ctx, ctx->scratch[3], g.blocks.size() * sizeof(GramBlock)));
+    HIPCHK(hipMemcpyAsync(ctx->scratch[3].p, g.blocks.data(), g.blocks.size() * sizeof(GramBlock), hipMemcpyHostToDevice, ctx->stream));
+    const size_t part_d = (size_t)nd * 4096 * g.gx_d, part_o = (size_t)no * 4096 * g.gx_o;
+    CHK(ensure(ctx, ctx->partials, (part_d + part_o) * sizeof(Partial)));
+    CHK(ensure(ctx, ctx->result, (size_t)(nd + no) * 4096 * sizeof(Partial)));
+    Partial *pp = (Partial *)ctx->partials.p;
+    Partial *res_d = (Partial *)ctx->result.p;
+    const int2 *dt = (const int2 *)ctx->scratch[3].p;
+    // a diagonal block writes only its 10 tiles with gj <= gi; the reduction below runs over all 16: the other six read zeros
+    HIPCHK(hipMemsetAsync(pp, 0, part_d * sizeof(Partial), ctx->stream));
+    LAUNCH(ctx, "gram_mfma", (gram_mfma_kernel<true>), dim3(g.gx_d, nd), dim3(256), prof, P, n, dt, pp);
+    CHK(reduce_partials(ctx, pp, nd * 4096, g.gx_d, res_d));
+    if (no) {
+        LAUNCH(ctx, "gram_mfma", (gram_mfma_kernel<false>), dim3(g.gx_o, no), dim3(256), prof, P, n, dt + nd, pp + part_d);
+        CHK(reduce_partials(ctx, pp + part_d, no * 4096, g.gx_o, res_d + (size_t)nd * 4096));
+    }
+    if (allreduce) CHK(comm_allreduce_partials(ctx, res_d, (size_t)(nd + no) * 4096));   // (sums of exact integers: exact in any order below 2^53)
+    std::vector<Partial> res((size_t)(nd + no) * 4096);
+    HIPCHK(hipMemcpyAsync(res.data(), res_d, res.size() * sizeof(Partial), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // also: `g.blocks` was read by the asynchronous copy above
+    std::vector<double> norm(P);
+    for (int i = 0; i < P; ++i) {
+        norm[i] = res[gram_index(g, i, i)].s;
+        if (!gram_exact(norm[i])) {
+            *exact = false;
+            return KPAL_OK;
+        }
+    }
+    for (int i = 1; i < P; ++i)
+        for (int j = 0; j < i; ++j) out_lower[triangle_index(i, j)] = gram_distance(norm[i], norm[j], res[gram_index(g, i, j)].s, exact);
+    *exact = true;
+    return KPAL_OK;
+}
+
+// ... of a rectangle, from the fp64 dot products of cross_gram_kernel and the norms of cross_norm_kernel: the same rule.
 static int cross_gram_euclidean(kpal_ctx *ctx, const CrossSets &c, double *out, bool *exact)
 {
     const int blocksQ = (c.Q + 63) / 64, blocksR = (c.R + 63) / 64;
     const uint32_t nblocks = (uint32_t)blocksQ * (uint32_t)blocksR, nprof = (uint32_t)c.Q + (uint32_t)c.R;
-    const uint64_t slabs = c.n / kGramBins;
-    // one 132 KiB workgroup per CU
-    const uint32_t gx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(slabs, (uint64_t)ctx->num_cu / nblocks));
+    const uint32_t gx = cross_gram_gx(ctx->num_cu, nblocks, c.n);
     const size_t dots = (size_t)nblocks * 4096, groups = dots + nprof;
-    if (groups > 0x7fffffffu / gx) return set_err(KPAL_E_INVALID, "cross distance: %d x %d profiles are too many for one call", c.Q, c.R);
+    if (partials_too_many(groups, gx)) return set_err(KPAL_E_INVALID, "cross distance: %d x %d profiles are too many for one call", c.Q, c.R);
     CHK(ensure(ctx, ctx->partials, groups * gx * sizeof(Partial)));
     Partial *pp = (Partial *)ctx->partials.p;
     LAUNCH(ctx, "cross_gram", cross_gram_kernel, dim3(nblocks * gx), dim3(256), c, gx, blocksR, pp);
     LAUNCH(ctx, "cross_norm", cross_norm_kernel, dim3(nprof * gx), dim3(256), c, gx, pp + dots * gx);
     std::vector<Partial> res;
     CHK(finish_partials(ctx, (uint32_t)groups, gx, res));
-    const double limit = 9007199254740992.0;     // 2^53
     for (uint32_t p = 0; p < nprof; ++p)
-        if (!(res[dots + p].s < limit)) {
+        if (!gram_exact(res[dots + p].s)) {
             *exact = false;
             return KPAL_OK;
         }
     for (int q = 0; q < c.Q; ++q)
-        for (int r = 0; r < c.R; ++r) {
-            const size_t block = (size_t)(q / 64) * blocksR + (size_t)(r / 64);
-            const size_t tile = (size_t)((q % 64) / 16) * 4 + (size_t)((r % 64) / 16);
-            const double dot = res[(block * 16 + tile) * 256 + (size_t)((q % 16) * 16 + (r % 16))].s;
-            // exact integers below 2^53 each: the int64 expression is the reference's sum of squared differences
-            const int64_t d2 = (int64_t)res[dots + q].s + (int64_t)res[dots + c.Q + r].s - 2 * (int64_t)dot;
-            out[(size_t)q * c.R + r] = std::sqrt((double)d2);   // metrics.py:46: np.sqrt(np.dot(v, v))
-        }
+        for (int r = 0; r < c.R; ++r)
+            out[(size_t)q * c.R + r] = gram_distance(res[dots + q].s, res[dots + c.Q + r].s, res[cross_gram_index(blocksR, q, r)].s, exact);
     *exact = true;
     return KPAL_OK;
-}
-
-// Tiles, slots and the grid of one pass of cross_tile_kernel / cross_super_kernel (or cross_recip_kernel) over c.
-struct CrossGrid {
-    int sideR, superR;
-    uint32_t units;   // what the grid counts: super-tiles (staged) or 4 x 4 tiles
-    uint32_t gx;      // workgroups per unit = partials per slot
-    uint64_t slots;   // 16 * tiles
-};
-static CrossGrid cross_grid(kpal_ctx *ctx, const CrossSets &c, bool staged)
-{
-    const int sideQ = (c.Q + 3) / 4, sideR = (c.R + 3) / 4, superQ = (c.Q + 15) / 16, superR = (c.R + 15) / 16;
-    const uint64_t ntiles = c.tri ? (uint64_t)sideQ * (sideQ + 1) / 2 : (uint64_t)sideQ * sideR;
-    const uint64_t nsuper = c.tri ? (uint64_t)superQ * (superQ + 1) / 2 : (uint64_t)superQ * superR;
-    uint32_t gx;
-    if (staged) {
-        gx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(c.n / kSuperBins, std::max<uint64_t>(1, (uint64_t)ctx->num_cu * 8 / nsuper)));
-        gx = std::max(8u, gx / 8u * 8u);   // (cross_block deals bin-groups to the 8 XCDs; n / 64 >= 64 for k >= 6)
-    } else {
-        gx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((c.n + 255) / 256, std::max<uint64_t>(1, (uint64_t)ctx->num_cu * 16 / ntiles)));
-    }
-    return CrossGrid{sideR, superR, (uint32_t)(staged ? nsuper : ntiles), gx, ntiles * 16};
-}
-
-// cross_slot on the host: where the reduced partial of pair (i, j) lies
-static size_t cross_slot_host(const CrossSets &c, int sideR, int i, int j)
-{
-    const size_t tile = c.tri ? (size_t)(i / 4) * (size_t)(i / 4 + 1) / 2 + (size_t)(j / 4) : (size_t)(i / 4) * sideR + (size_t)(j / 4);
-    return tile * 16 + (size_t)((i % 4) * 4 + j % 4);
 }
 
 template <class Acc>
@@ -86,12 +162,11 @@ static int launch_cross(kpal_ctx *ctx, const char *name, bool staged, const Cros
 // Every pair of c for a plain metric: the register-tile kernel, or (staged: c.n is a multiple of 64) the LDS-staged ones --
 // with `recip` the reciprocal form of 'prod' / 'sum' first, valid while every count is below 2^16 ('prod') or fits the table
 // ('sum'): the kernel says whether it saw a larger one, and the pair-of-counts kernel then runs after all.  res: the reduced
-// partial of pair (i, j) at tile number * 16 + (i % 4) * 4 + j % 4 (cross_kernels.hpp); the triangle's launches keep the
-// names they always had.
-int cross_pairs(kpal_ctx *ctx, const CrossSets &c, int metric, bool staged, bool recip, bool allreduce, std::vector<Partial> &res)
+// partial of pair (i, j) at cross_slot(i, j); the triangle's launches keep the names they always had.
+static int cross_pairs(kpal_ctx *ctx, const CrossSets &c, int metric, bool staged, bool recip, bool allreduce, std::vector<Partial> &res)
 {
-    const CrossGrid g = cross_grid(ctx, c, staged);
-    if (g.slots > 0x7fffffffu / g.gx) return set_err(KPAL_E_INVALID, "%d x %d profiles are too many for one call", c.Q, c.R);
+    const CrossGrid g = cross_grid(ctx->num_cu, c, staged);
+    if (partials_too_many(g.slots, g.gx)) return set_err(KPAL_E_INVALID, "%d x %d profiles are too many for one call", c.Q, c.R);
     CHK(ensure(ctx, ctx->partials, g.slots * g.gx * sizeof(Partial)));
     Partial *pp = (Partial *)ctx->partials.p;
     const CrossOpt o = {c, 0, nullptr, 0u, (uint32_t)g.slots};
@@ -99,15 +174,12 @@ int cross_pairs(kpal_ctx *ctx, const CrossSets &c, int metric, bool staged, bool
     if (staged && recip && metric != KPAL_EUCLIDEAN) {
         CHK(ensure(ctx, ctx->scratch[3], 16));
         uint32_t *big = (uint32_t *)ctx->scratch[3].p;
-        HIPCHK(hipMemsetAsync(big, 0, sizeof(uint32_t), ctx->stream));
-        HIPCHK(hipMemsetAsync(pp, 0, g.slots * g.gx * sizeof(Partial), ctx->stream));   // (.s / .m of a slot come from different threads)
-        const dim3 grid(g.gx * g.units);   // (gx: a multiple of 8)
-        if (metric == KPAL_PAIRWISE_PROD) LAUNCH(ctx, c.tri ? "matrix_rdiff" : "cross_rdiff", (cross_recip_kernel<0>), grid, dim3(256), c, g.units, g.superR, pp, big);
-        else LAUNCH(ctx, c.tri ? "matrix_rsum" : "cross_rsum", (cross_recip_kernel<1>), grid, dim3(256), c, g.units, g.superR, pp, big);
-        uint32_t saw_big = 0;
-        HIPCHK(hipMemcpyAsync(&saw_big, big, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        done = saw_big == 0;
+        CHK(try_recip(ctx, big, sizeof(uint32_t), pp, g.slots * g.gx, [&]() -> int {
+            const dim3 grid(g.gx * g.units);   // (gx: a multiple of 8)
+            if (metric == KPAL_PAIRWISE_PROD) LAUNCH(ctx, c.tri ? "matrix_rdiff" : "cross_rdiff", (cross_recip_kernel<0>), grid, dim3(256), c, g.units, g.superR, pp, big);
+            else LAUNCH(ctx, c.tri ? "matrix_rsum" : "cross_rsum", (cross_recip_kernel<1>), grid, dim3(256), c, g.units, g.superR, pp, big);
+            return KPAL_OK;
+        }, &done));
     }
     if (!done) {
         const char *name = staged ? (c.tri ? "matrix_super" : "cross_super") : (c.tri ? "matrix_tile" : "cross_tile");
@@ -118,11 +190,57 @@ int cross_pairs(kpal_ctx *ctx, const CrossSets &c, int metric, bool staged, bool
     return finish_partials(ctx, (uint32_t)g.slots, g.gx, res, allreduce);
 }
 
+// The lower triangle over n bins per profile (profile p at prof + p * n).  allreduce: this rank holds a bin RANGE of every
+// profile -- the per-pair sums / term counts / dot products of all ranks are added (one all-reduce) before they are finished;
+// the ranks agreed on `tiled_agreed` (kpal_comm_distance_matrix_device): the Gram path and the others all-reduce different things.
+int distance_matrix_core(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof, int metric, double *out_lower, bool allreduce, int tiled_agreed)
+{
+    const MatrixRoute route = matrix_route(P, n, metric, tiled_agreed, matrix_switches());
+    if (route.gram) {
+        bool exact = false;
+        CHK(gram_euclidean(ctx, P, n, prof, out_lower, &exact, allreduce));
+        if (exact) return KPAL_OK;
+    }
+    const CrossSets c = {prof, prof, P, P, n, 1};   // the triangle is the set crossed with itself
+    const size_t slots = (size_t)cross_grid(ctx->num_cu, c, false).slots;   // (the *_all kernels write the slots of cross_kernels.hpp)
+    unsigned gx = 0;
+    bool all_done = false;
+    if (route.all) {
+        const bool wide = route.all_wide;
+        gx = matrix_all_gx(ctx->num_cu, n, wide);
+        CHK(ensure(ctx, ctx->scratch[3], 32));
+        CHK(ensure(ctx, ctx->partials, slots * gx * sizeof(Partial)));
+        Partial *pp = (Partial *)ctx->partials.p;
+        uint32_t *big = (uint32_t *)ctx->scratch[3].p;
+        CHK(try_recip(ctx, big, 32, pp, slots * gx, [&]() -> int {
+            if (metric == 0) {
+                if (wide) LAUNCH(ctx, "matrix_rdiff_all", (matrix_rdiff_all_kernel<16, kMatrixAllBins, kMatrixAllUnits>), dim3(gx), dim3(1024 / kMatrixAllUnits), prof, P, n, pp, big);
+                else LAUNCH(ctx, "matrix_rdiff_all", (matrix_rdiff_all_kernel<8, 64, 1>), dim3(gx), dim3(256), prof, P, n, pp, big);
+            } else {
+                if (wide) LAUNCH(ctx, "matrix_rsum_all", (matrix_rsum_all_kernel<16, 64>), dim3(gx), dim3(1024), prof, P, n, pp, big);
+                else LAUNCH(ctx, "matrix_rsum_all", (matrix_rsum_all_kernel<8, 64>), dim3(gx), dim3(256), prof, P, n, pp, big);
+            }
+            return KPAL_OK;
+        }, &all_done));
+#if defined(KPAL_MALL_CLOCK)
+        {
+            unsigned long long clk[4] = {0, 0, 0, 0};
+            HIPCHK(hipMemcpy(clk, big, sizeof(clk), hipMemcpyDeviceToHost));
+            fprintf(stderr, "matrix_all: %llu shader cycles in %.1f us = %.0f MHz\n", clk[1], (double)clk[2] / 100.0, 100.0 * (double)clk[1] / (double)clk[2]);
+        }
+#endif
+    }
+    std::vector<Partial> res;
+    if (all_done) CHK(finish_partials(ctx, (uint32_t)slots, gx, res, allreduce));
+    else CHK(cross_pairs(ctx, c, metric, route.staged, route.recip, allreduce, res));
+    for (int i = 1; i < P; ++i)
+        for (int j = 0; j < i; ++j) out_lower[triangle_index(i, j)] = finish_value(metric, res[cross_slot(c, 0, i, j)], nullptr);   // (a triangle's slots know no side)
+    return KPAL_OK;
+}
+
 static int cross_core(kpal_ctx *ctx, const CrossSets &c, int metric, double *out)
 {
-    // the LDS-staged kernels take 64 bins at a time (k >= 6) and pay when both sides fill more than one register tile; with
-    // at most four profiles on a side the register-tile kernel already reads the long side once
-    const bool staged = c.n >= 4096 && c.Q > 4 && c.R > 4;
+    const bool staged = cross_staged(c.Q, c.R, c.n);
     if (metric == KPAL_EUCLIDEAN && staged) {
         bool exact = false;
         CHK(cross_gram_euclidean(ctx, c, out, &exact));
@@ -132,8 +250,37 @@ static int cross_core(kpal_ctx *ctx, const CrossSets &c, int metric, double *out
     CHK(cross_pairs(ctx, c, metric, staged, true, false, res));
     const int sideR = (c.R + 3) / 4;
     for (int q = 0; q < c.Q; ++q)
-        for (int r = 0; r < c.R; ++r) out[(size_t)q * c.R + r] = finish_value(metric, res[cross_slot_host(c, sideR, q, r)], nullptr);
+        for (int r = 0; r < c.R; ++r) out[(size_t)q * c.R + r] = finish_value(metric, res[cross_slot(c, sideR, q, r)], nullptr);
     return KPAL_OK;
+}
+
+KPAL_API int kpal_distance_matrix_device(kpal_ctx *ctx, int P, int k, const int64_t *dev_profiles, int metric,
+                                         int do_balance, double *out_lower)
+{
+    CTX_ENTER(ctx);
+    if (P < 1) return set_err(KPAL_E_INVALID, "P must be >= 1");
+    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
+    if (metric < 0 || metric > 2) return set_err(KPAL_E_INVALID, "unknown metric %d", metric);
+    if (P == 1) return KPAL_OK;
+    if (!dev_profiles || !out_lower) return set_err(KPAL_E_INVALID, "NULL pointer");
+    const uint64_t n = 1ULL << (2 * k);
+    CrossSets c = {dev_profiles, dev_profiles, P, P, n, 1};
+    if (do_balance) CHK(balance_sets(ctx, k, c));
+    return distance_matrix_core(ctx, P, n, c.left, metric, out_lower, false);
+}
+
+KPAL_API int kpal_distance_matrix(kpal_ctx *ctx, int P, int k, const int64_t *const *host_profiles, int metric,
+                                  int do_balance, double *out_lower)
+{
+    CTX_ENTER(ctx);
+    if (P < 1) return set_err(KPAL_E_INVALID, "P must be >= 1");
+    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
+    if (P == 1) return KPAL_OK;
+    if (!host_profiles || !out_lower) return set_err(KPAL_E_INVALID, "NULL pointer");
+    const uint64_t n = 1ULL << (2 * k);
+    CHK(ensure(ctx, ctx->scratch[0], (size_t)P * n * 8));
+    CHK(upload_set(ctx, (int64_t *)ctx->scratch[0].p, P, n, host_profiles, "profile"));
+    return kpal_distance_matrix_device(ctx, P, k, (const int64_t *)ctx->scratch[0].p, metric, do_balance, out_lower);
 }
 
 static int cross_check(int k, int Q, int R, int metric, const void *left, const void *right, const double *out)
@@ -151,17 +298,8 @@ KPAL_API int kpal_cross_distance_device(kpal_ctx *ctx, int k, int Q, const int64
     CTX_ENTER(ctx);
     CHK(cross_check(k, Q, R, metric, dev_left, dev_right, out));
     if (((uintptr_t)dev_left & 15) || ((uintptr_t)dev_right & 15)) return set_err(KPAL_E_INVALID, "device tables must be 16-byte aligned");
-    const uint64_t n = 1ULL << (2 * k);
-    CrossSets c = {dev_left, dev_right, Q, R, n, 0};
-    if (do_balance) {
-        // balance once per profile: identical to the reference balancing copies per pair (kdistlib.py:136-141)
-        CHK(ensure(ctx, ctx->scratch[2], ((size_t)Q + (size_t)R) * n * 8));
-        int64_t *bl = (int64_t *)ctx->scratch[2].p, *br = bl + (uint64_t)Q * n;
-        for (int q = 0; q < Q; ++q) CHK(launch_balance(ctx, k, dev_left + (uint64_t)q * n, bl + (uint64_t)q * n));
-        for (int r = 0; r < R; ++r) CHK(launch_balance(ctx, k, dev_right + (uint64_t)r * n, br + (uint64_t)r * n));
-        c.left = bl;
-        c.right = br;
-    }
+    CrossSets c = {dev_left, dev_right, Q, R, 1ULL << (2 * k), 0};
+    if (do_balance) CHK(balance_sets(ctx, k, c));
     return cross_core(ctx, c, metric, out);
 }
 
@@ -170,25 +308,14 @@ KPAL_API int kpal_cross_distance(kpal_ctx *ctx, int k, int Q, const int64_t *con
 {
     CTX_ENTER(ctx);
     CHK(cross_check(k, Q, R, metric, host_left, host_right, out));
-    const uint64_t n = 1ULL << (2 * k);
-    CHK(ensure(ctx, ctx->scratch[0], ((size_t)Q + (size_t)R) * n * 8));
-    int64_t *dl = (int64_t *)ctx->scratch[0].p, *dr = dl + (uint64_t)Q * n;
-    for (int p = 0; p < Q + R; ++p) {
-        const int64_t *src = p < Q ? host_left[p] : host_right[p - Q];
-        if (!src) return set_err(KPAL_E_INVALID, "%s profile %d is NULL", p < Q ? "left" : "right", p < Q ? p : p - Q);
-        HIPCHK(hipMemcpyAsync(dl + (uint64_t)p * n, src, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
+    int64_t *dl = nullptr, *dr = nullptr;
+    CHK(upload_rectangle(ctx, 1ULL << (2 * k), Q, host_left, R, host_right, &dl, &dr));
     return kpal_cross_distance_device(ctx, k, Q, dl, R, dr, metric, do_balance, out);
 }
 
 // ----------------------------------------------------------------------------------------------
 // ProfileDistance with options over a rectangle / a lower triangle (cross_option_kernels.hpp)
 // ----------------------------------------------------------------------------------------------
-static bool plain_options(const kpal_distance_options *opt)
-{
-    return !opt->do_positive && !opt->do_smooth && !opt->do_scale && opt->metric <= KPAL_EUCLIDEAN;
-}
-
 template <int MODE>
 static int launch_cross_option_metric(kpal_ctx *ctx, const char *name, bool staged, bool scaled, bool positive, const CrossOpt &o,
                                       const CrossGrid &g, Partial *pp)
@@ -205,14 +332,14 @@ static int launch_cross_option_metric(kpal_ctx *ctx, const char *name, bool stag
 static int cross_option_core(kpal_ctx *ctx, const CrossSets &c, const kpal_distance_options *opt, double *out)
 {
     const bool scaled = opt->do_scale != 0, positive = opt->do_positive != 0, tri = c.tri != 0;
-    const bool staged = c.n >= 4096 && c.Q > 4 && c.R > 4;   // (cross_core's rule)
-    const CrossGrid g = cross_grid(ctx, c, staged);
+    const bool staged = cross_staged(c.Q, c.R, c.n);
+    const CrossGrid g = cross_grid(ctx->num_cu, c, staged);
     const uint64_t slots = g.slots;
     const uint32_t gx = g.gx;
-    const uint32_t nacc = opt->metric == KPAL_COSINE ? 3 : 1, nacc_max = std::max(nacc, scaled && positive ? 2u : 1u);
-    if (slots * nacc_max > 0x7fffffffu / gx) return set_err(KPAL_E_INVALID, "cross distance: %d x %d profiles are too many for one call", c.Q, c.R);
+    const uint32_t nacc = option_nacc(opt->metric), nacc_max = option_nacc_max(opt->metric, scaled, positive);
+    if (partials_too_many(slots * nacc_max, gx)) return set_err(KPAL_E_INVALID, "cross distance: %d x %d profiles are too many for one call", c.Q, c.R);
     const uint32_t nprof = tri ? (uint32_t)c.Q : (uint32_t)c.Q + (uint32_t)c.R;
-    const uint32_t gxt = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((c.n + 255) / 256, std::max<uint64_t>(1, (uint64_t)ctx->num_cu * 8 / nprof)));
+    const uint32_t gxt = option_totals_gx(ctx->num_cu, nprof, c.n);
     CHK(ensure(ctx, ctx->partials, std::max<size_t>((size_t)slots * nacc_max * gx, (size_t)nprof * gxt) * sizeof(Partial)));
     CHK(ensure(ctx, ctx->scratch[3], std::max<size_t>((size_t)slots * 2, nprof) * sizeof(Partial)));
     Partial *pp = (Partial *)ctx->partials.p, *totals = (Partial *)ctx->scratch[3].p;
@@ -235,30 +362,17 @@ static int cross_option_core(kpal_ctx *ctx, const CrossSets &c, const kpal_dista
     }
     std::vector<Partial> res;
     CHK(finish_partials(ctx, (uint32_t)(slots * nacc), gx, res));
-    auto value = [&](int i, int j) -> double {
-        const size_t slot = cross_slot_host(c, g.sideR, i, j);
-        const Partial &p0 = res[slot];
-        if (opt->metric <= KPAL_PAIRWISE_SUM) return p0.s / (double)(p0.m + 1ULL);   // metrics.py:123
-        if (opt->metric == KPAL_EUCLIDEAN) return scaled ? std::sqrt(p0.s) : std::sqrt((double)(int64_t)p0.m);   // metrics.py:135,46
-        const Partial &p1 = res[slots + slot], &p2 = res[2 * slots + slot];          // metrics.py:147: dot(l, r) / (|l| * |r|)
-        if (scaled) return p0.s / (std::sqrt(p1.s) * std::sqrt(p2.s));
-        return (double)(int64_t)p0.m / (std::sqrt((double)(int64_t)p1.m) * std::sqrt((double)(int64_t)p2.m));
+    auto value = [&](int i, int j) -> double {   // (accumulators 1 and 2 exist for the cosine only: p0 again, unread)
+        const size_t slot = cross_slot(c, g.sideR, i, j);
+        return finish_distance(opt->metric, scaled, res[slot], res[(nacc / 2) * slots + slot], res[(nacc - 1) * slots + slot]);
     };
     if (tri) {
         for (int i = 1; i < c.Q; ++i)
-            for (int j = 0; j < i; ++j) out[(size_t)i * (i - 1) / 2 + j] = value(i, j);
+            for (int j = 0; j < i; ++j) out[triangle_index(i, j)] = value(i, j);
     } else {
         for (int q = 0; q < c.Q; ++q)
             for (int r = 0; r < c.R; ++r) out[(size_t)q * c.R + r] = value(q, r);
     }
-    return KPAL_OK;
-}
-
-// Balanced copies of `count` consecutive tables at `dst` (one launch_balance per profile, as kpal_cross_distance_device).
-static int balance_set(kpal_ctx *ctx, int k, int count, const int64_t *src, int64_t *dst)
-{
-    const uint64_t n = 1ULL << (2 * k);
-    for (int p = 0; p < count; ++p) CHK(launch_balance(ctx, k, src + (uint64_t)p * n, dst + (uint64_t)p * n));
     return KPAL_OK;
 }
 
@@ -267,20 +381,12 @@ KPAL_API int kpal_cross_profile_distance_device(kpal_ctx *ctx, int k, int Q, con
 {
     CTX_ENTER(ctx);
     CHK(check_options(opt));
-    if (plain_options(opt)) return kpal_cross_distance_device(ctx, k, Q, dev_left, R, dev_right, opt->metric, opt->do_balance, out);
+    if (options_plain(opt)) return kpal_cross_distance_device(ctx, k, Q, dev_left, R, dev_right, opt->metric, opt->do_balance, out);
     CHK(cross_check(k, Q, R, 0, dev_left, dev_right, out));
     if (((uintptr_t)dev_left & 15) || ((uintptr_t)dev_right & 15)) return set_err(KPAL_E_INVALID, "device tables must be 16-byte aligned");
     const uint64_t n = 1ULL << (2 * k);
     CrossSets c = {dev_left, dev_right, Q, R, n, 0};
-    if (opt->do_balance) {
-        // balance once per profile: identical to the reference balancing copies per pair (kdistlib.py:136-141)
-        CHK(ensure(ctx, ctx->scratch[2], ((size_t)Q + (size_t)R) * n * 8));
-        int64_t *bl = (int64_t *)ctx->scratch[2].p, *br = bl + (uint64_t)Q * n;
-        CHK(balance_set(ctx, k, Q, dev_left, bl));
-        CHK(balance_set(ctx, k, R, dev_right, br));
-        c.left = bl;
-        c.right = br;
-    }
+    if (opt->do_balance) CHK(balance_sets(ctx, k, c));
     if (opt->do_smooth) {
         // smoothed tables exist per pair only (a node collapses by both partners' counts): the pair pipeline on the balanced tables
         for (int q = 0; q < Q; ++q)
@@ -297,14 +403,8 @@ KPAL_API int kpal_cross_profile_distance(kpal_ctx *ctx, int k, int Q, const int6
     CTX_ENTER(ctx);
     CHK(check_options(opt));
     CHK(cross_check(k, Q, R, 0, host_left, host_right, out));
-    const uint64_t n = 1ULL << (2 * k);
-    CHK(ensure(ctx, ctx->scratch[0], ((size_t)Q + (size_t)R) * n * 8));
-    int64_t *dl = (int64_t *)ctx->scratch[0].p, *dr = dl + (uint64_t)Q * n;
-    for (int p = 0; p < Q + R; ++p) {
-        const int64_t *src = p < Q ? host_left[p] : host_right[p - Q];
-        if (!src) return set_err(KPAL_E_INVALID, "%s profile %d is NULL", p < Q ? "left" : "right", p < Q ? p : p - Q);
-        HIPCHK(hipMemcpyAsync(dl + (uint64_t)p * n, src, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
+    int64_t *dl = nullptr, *dr = nullptr;
+    CHK(upload_rectangle(ctx, 1ULL << (2 * k), Q, host_left, R, host_right, &dl, &dr));
     return kpal_cross_profile_distance_device(ctx, k, Q, dl, R, dr, opt, out);
 }
 
@@ -317,21 +417,34 @@ KPAL_API int kpal_profile_distance_matrix_device(kpal_ctx *ctx, int P, int k, co
     CHK(check_options(opt));
     if (P == 1) return KPAL_OK;
     if (!dev_profiles || !out_lower) return set_err(KPAL_E_INVALID, "NULL pointer");
-    if (plain_options(opt)) return kpal_distance_matrix_device(ctx, P, k, dev_profiles, opt->metric, opt->do_balance, out_lower);
+    if (options_plain(opt)) return kpal_distance_matrix_device(ctx, P, k, dev_profiles, opt->metric, opt->do_balance, out_lower);
     if ((uintptr_t)dev_profiles & 15) return set_err(KPAL_E_INVALID, "device tables must be 16-byte aligned");
     const uint64_t n = 1ULL << (2 * k);
-    const int64_t *prof = dev_profiles;
-    if (opt->do_balance) {
-        CHK(ensure(ctx, ctx->scratch[2], (size_t)P * n * 8));
-        CHK(balance_set(ctx, k, P, dev_profiles, (int64_t *)ctx->scratch[2].p));
-        prof = (const int64_t *)ctx->scratch[2].p;
-    }
+    CrossSets c = {dev_profiles, dev_profiles, P, P, n, 1};
+    if (opt->do_balance) CHK(balance_sets(ctx, k, c));
     if (opt->do_smooth) {
         for (int i = 1; i < P; ++i)
             for (int j = 0; j < i; ++j)
-                CHK(profile_distance_pair(ctx, k, prof + (uint64_t)i * n, prof + (uint64_t)j * n, opt, true, &out_lower[(size_t)i * (i - 1) / 2 + j]));
+                CHK(profile_distance_pair(ctx, k, c.left + (uint64_t)i * n, c.left + (uint64_t)j * n, opt, true, &out_lower[triangle_index(i, j)]));
         return KPAL_OK;
     }
-    const CrossSets c = {prof, prof, P, P, n, 1};
     return cross_option_core(ctx, c, opt, out_lower);
+}
+
+KPAL_API int kpal_profile_distance_matrix(kpal_ctx *ctx, int P, int k, const int64_t *const *host_profiles,
+                                          const kpal_distance_options *opt, double *out_lower)
+{
+    CTX_ENTER(ctx);
+    if (P < 1) return set_err(KPAL_E_INVALID, "P must be >= 1");
+    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
+    CHK(check_options(opt));
+    if (P == 1) return KPAL_OK;
+    if (!host_profiles || !out_lower) return set_err(KPAL_E_INVALID, "NULL pointer");
+    if (options_plain(opt)) return kpal_distance_matrix(ctx, P, k, host_profiles, opt->metric, opt->do_balance, out_lower);
+    const uint64_t n = 1ULL << (2 * k);
+    CHK(ensure(ctx, ctx->opt_profiles, (size_t)P * n * 8));
+    int64_t *prof = (int64_t *)ctx->opt_profiles.p;
+    CHK(upload_set(ctx, prof, P, n, host_profiles, "profile"));
+    // uploaded once; balanced once per profile and every pair in a fixed number of launches
+    return kpal_profile_distance_matrix_device(ctx, P, k, prof, opt, out_lower);
 }

@@ -2,8 +2,9 @@
 // workspace buffers, per-kernel HIP-event timing, the launch / dispatch macros and the few host functions
 // one unit calls in another.  (kpal_ctx.hip: context + profiling API; kpal_count.hip: counting front end and the
 // round-1 pipelines; kpal_text.hip: FASTA and FASTQ ingest; kpal_records.hip: one profile per record / per sliding window;
-// kpal_quads.hip / kpal_quads2.hip: the quad record pipelines, planned by quad_plan.hpp; kpal_vec.hip: balance, split,
-// distances, matrices, options, summaries; kpal_cross.hip: the rectangle of distances between two sets; kpal_multi.hip: multi-GPU entry points over RCCL.)
+// kpal_quads.hip / kpal_quads2.hip: the quad record pipelines, planned by quad_plan.hpp; kpal_vec.hip: one vector -- balance,
+// split, summaries, merge, shrink; kpal_pair.hip: the distance of one pair, plain and with options; kpal_cross.hip: the distances
+// of sets of profiles, triangle and rectangle, planned by matrix_plan.hpp; kpal_multi.hip: multi-GPU entry points over RCCL.)
 #pragma once
 #include "../../include/kpal_hip.h"
 
@@ -23,6 +24,7 @@
 #include "kpal_device.hpp"
 #include "host_pool.hpp"
 #include "quad_plan.hpp"
+#include "matrix_plan.hpp"
 
 #define KPAL_API extern "C" __attribute__((visibility("default")))
 
@@ -355,14 +357,13 @@ void fq_reset(kpal_ctx *ctx);                                             // kpa
 int count_end_text(kpal_ctx *ctx);                                        // kpal_text.hip: an open FASTQ text is ended (its carried record counted, or the count abandoned)
 int table_ready(kpal_ctx *ctx);                                           // kpal_quads2.hip: zeros materialised, pending finalisation done: the table is the table
 int launch_balance(kpal_ctx *ctx, int k, const int64_t *in, int64_t *out);   // kpal_vec.hip
-int check_options(const kpal_distance_options *opt);                       // kpal_vec.hip
+int canon_tiles(kpal_ctx *ctx, int k, int per_cu, const uint32_t **list, uint32_t *count, unsigned *grid);   // kpal_vec.hip: the canonical tile pairs of the LDS-tiled balance family (k >= 6), the grid for per_cu workgroups on a CU
+int check_options(const kpal_distance_options *opt);                       // kpal_pair.hip
 int profile_distance_pair(kpal_ctx *ctx, int k, const int64_t *dl, const int64_t *dr, const kpal_distance_options *opt, bool balanced,
-                          double *out);   // kpal_vec.hip: the option pipeline of one pair of 16-byte aligned device tables (balanced: do_balance is not applied again)
+                          double *out);   // kpal_pair.hip: the option pipeline of one pair of 16-byte aligned device tables (balanced: do_balance is not applied again)
 int distance_matrix_core(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof, int metric, double *out_lower, bool allreduce,
-                         int tiled = -1);   // kpal_vec.hip (tiled: -1 decided from n; 0 / 1 agreed between the ranks)
-namespace kpal { struct Partial; struct CrossSets; }   // matrix_common.hpp
+                         int tiled = -1);   // kpal_cross.hip (tiled: -1 decided from n; 0 / 1 agreed between the ranks)
 int reduce_partials(kpal_ctx *ctx, const Partial *partials, uint32_t nq, uint32_t nblocks, Partial *out);   // kpal_vec.hip: nq groups of nblocks device partials added in a fixed order
 int finish_partials(kpal_ctx *ctx, uint32_t nq, uint32_t nblocks, std::vector<Partial> &out, bool allreduce = false);   // kpal_vec.hip: reduce nq groups of nblocks partials, fetch them
-int cross_pairs(kpal_ctx *ctx, const CrossSets &c, int metric, bool staged, bool recip, bool allreduce, std::vector<Partial> &res);   // kpal_cross.hip: the plain pairs of a rectangle or a triangle, reduced
-double finish_value(int metric, const Partial &p, int64_t *aux);         // kpal_vec.hip: the distance of one reduced partial
-int comm_allreduce_partials(kpal_ctx *ctx, void *dev_partials, size_t count);   // kpal_multi.hip: {double sum, uint64 count} pairs added over the ranks, in place
+double finish_value(int metric, const Partial &p, int64_t *aux);         // kpal_vec.hip: the distance of one reduced partial of a plain metric (aux: its count / wrapping dot)
+int comm_allreduce_partials(kpal_ctx *ctx, Partial *dev_partials, size_t count);   // kpal_multi.hip: partials added over the ranks, in place

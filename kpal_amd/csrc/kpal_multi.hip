@@ -409,13 +409,7 @@ KPAL_API int kpal_comm_merged_table(kpal_ctx *ctx, void **dev_table, uint64_t *n
 }
 
 // ---- distance matrix over bin-range shards --------------------------------------------------------------------
-// Partial of matrix_common.hpp restated (the kernels that fill it belong to kpal_vec.hip and kpal_cross.hip): a double sum and a 64-bit count / wrapping dot
-struct PartialPod {
-    double s;
-    unsigned long long m;
-};
-
-__global__ void partials_split_kernel(const PartialPod *__restrict__ p, size_t n, double *__restrict__ s, unsigned long long *__restrict__ m)
+__global__ void partials_split_kernel(const Partial *__restrict__ p, size_t n, double *__restrict__ s, unsigned long long *__restrict__ m)
 {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         s[i] = p[i].s;
@@ -423,12 +417,12 @@ __global__ void partials_split_kernel(const PartialPod *__restrict__ p, size_t n
     }
 }
 
-__global__ void partials_join_kernel(PartialPod *__restrict__ p, size_t n, const double *__restrict__ s, const unsigned long long *__restrict__ m)
+__global__ void partials_join_kernel(Partial *__restrict__ p, size_t n, const double *__restrict__ s, const unsigned long long *__restrict__ m)
 {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = PartialPod{s[i], m[i]};
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = Partial{s[i], m[i]};
 }
 
-int comm_allreduce_partials(kpal_ctx *ctx, void *dev_partials, size_t count)
+int comm_allreduce_partials(kpal_ctx *ctx, Partial *dev_partials, size_t count)
 {
     if (!ctx->comm) return set_err(KPAL_E_STATE, "no communicator (kpal_comm_init)");
     if (count == 0) return KPAL_OK;
@@ -436,13 +430,13 @@ int comm_allreduce_partials(kpal_ctx *ctx, void *dev_partials, size_t count)
     double *s = (double *)ctx->scratch[1].p;
     unsigned long long *m = (unsigned long long *)(s + count);
     const unsigned grid = (unsigned)std::min<size_t>((count + 255) / 256, 1024);
-    LAUNCH(ctx, "partials_split", partials_split_kernel, dim3(grid), dim3(256), (const PartialPod *)dev_partials, count, s, m);
+    LAUNCH(ctx, "partials_split", partials_split_kernel, dim3(grid), dim3(256), (const Partial *)dev_partials, count, s, m);
     {
         ProfScope ps_(ctx, "rccl_allreduce");
         NCCLCHK(g_rccl.AllReduce(s, s, count, ncclDouble, ncclSum, (ncclComm_t)ctx->comm, ctx->stream));
         NCCLCHK(g_rccl.AllReduce(m, m, count, ncclUint64, ncclSum, (ncclComm_t)ctx->comm, ctx->stream));
     }
-    LAUNCH(ctx, "partials_join", partials_join_kernel, dim3(grid), dim3(256), (PartialPod *)dev_partials, count, (const double *)s,
+    LAUNCH(ctx, "partials_join", partials_join_kernel, dim3(grid), dim3(256), dev_partials, count, (const double *)s,
            (const unsigned long long *)m);
     return KPAL_OK;
 }
@@ -461,7 +455,7 @@ KPAL_API int kpal_comm_distance_matrix_device(kpal_ctx *ctx, int P, uint64_t bin
     if (metric < 0 || metric > 2) return set_err(KPAL_E_INVALID, "unknown metric %d", metric);
     if (P == 1) return KPAL_OK;
     const bool valid = dev_slices && out_lower && bin_count != 0 && ((uintptr_t)dev_slices & 15) == 0;
-    int tiled = !valid ? -1 : ((bin_count >= 4096 && bin_count % 64 == 0) ? 1 : 0);
+    int tiled = !valid ? -1 : (matrix_tiled(bin_count) ? 1 : 0);
     CHK(ensure(ctx, ctx->result, 64));
     HIPCHK(hipMemcpyAsync(ctx->result.p, &tiled, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     NCCLCHK(g_rccl.AllReduce(ctx->result.p, ctx->result.p, 1, ncclInt32, ncclMin, (ncclComm_t)ctx->comm, ctx->stream));

@@ -5,19 +5,9 @@
 // triangle) and gram_kernels.hpp.  No kernel lives here.
 #pragma once
 #include "kpal_device.hpp"
+#include "matrix_plan.hpp"   // CrossSets, Partial, the index functions the host shares, kSuperBins
 
 namespace kpal {
-
-// Two sets of profiles whose pairs (left i, right j) are wanted (cross_kernels.hpp).  tri: a set against ITSELF -- left ==
-// right, Q == R -- and only the pairs on or below the diagonal: the lower triangle of kdistlib.distance_matrix.
-struct CrossSets {
-    const int64_t *left;    // Q x n
-    const int64_t *right;   // R x n
-    int Q, R;
-    uint64_t n;
-    int tri;
-};
-
 
 // ---- pairwise functions, kpal/metrics.py:159-162, int64 wrap-around like NumPy -------------
 __device__ __forceinline__ int64_t wrap_abs_diff(int64_t x, int64_t y)
@@ -37,11 +27,6 @@ __device__ __forceinline__ double pw_sum(int64_t x, int64_t y)
 }
 __device__ __forceinline__ double pw_prod(double x, double y) { return fabs(x - y) / ((x + 1.0) * (y + 1.0)); }
 __device__ __forceinline__ double pw_sum(double x, double y) { return fabs(x - y) / (x + y + 1.0); }
-
-struct Partial {
-    double s;            // sum of pairwise terms
-    unsigned long long m;  // multiset: bins with l!=0 or r!=0; euclidean: wrapping int64 dot
-};
 
 __device__ __forceinline__ Partial block_reduce(Partial p)
 {
@@ -225,8 +210,7 @@ __device__ __forceinline__ void matrix_accumulate_prod_rcp(const int64_t (&x)[TI
     if (++tb.bins == 255u) term_bytes_flush(tb, mf);   // wave-uniform
 }
 
-// Geometry of a staged super-tile (cross_super_kernel, cross_recip_kernel): 64 bins per stage, rows padded to 68 bins.
-constexpr int kSuperBins = 64;
+// Geometry of a staged super-tile (cross_super_kernel, cross_recip_kernel): kSuperBins = 64 bins per stage, rows padded to 68 bins.
 constexpr int kSuperRow = 68;
 
 // Wave priority by progress (quad_kernels.hpp: quad_tile_priority): the workgroups of the staged matrix kernels run a few thousand

@@ -9,6 +9,7 @@
 // fp64 sums are reduced in a FIXED order (per-thread serial, wave shuffle tree, block tree,
 // then a single-workgroup pass over the per-block partials) so results are run-to-run
 // reproducible; they agree with NumPy's pairwise summation to ~1e-15 relative.
+// Two units include this header (kpal_vec.hip; kpal_pair.hip for the pair kernels): the kernels that are no templates are static.
 #pragma once
 #include "matrix_common.hpp"
 
@@ -16,7 +17,7 @@ namespace kpal {
 
 // ---- balance ------------------------------------------------------------------------------
 // out[i] = in[i] + in[rc(i)] (i == rc(i) gives 2*in[i], klib.py:297-298).  Out of place.
-__global__ __launch_bounds__(256) void balance_oop_kernel(const int64_t *__restrict__ in, int64_t *__restrict__ out,
+static __global__ __launch_bounds__(256) void balance_oop_kernel(const int64_t *__restrict__ in, int64_t *__restrict__ out,
                                                           int k, uint64_t n)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
@@ -24,7 +25,7 @@ __global__ __launch_bounds__(256) void balance_oop_kernel(const int64_t *__restr
 }
 
 // In place: the thread owning i < rc(i) updates both ends of the pair (klib.py:290-296).
-__global__ __launch_bounds__(256) void balance_inplace_kernel(int64_t *__restrict__ c, int k, uint64_t n)
+static __global__ __launch_bounds__(256) void balance_inplace_kernel(int64_t *__restrict__ c, int k, uint64_t n)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t r = revcomp(i, k);
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256) void balance_inplace_kernel(int64_t *__restric
 // persistent workgroups take them round robin -- every workgroup gets the same number of pairs to within one.  (Striding through
 // M itself and skipping the non-canonical ones left the work badly spread: a workgroup's M share their low digits, and those
 // decide whether M <= rc(M) for nearly all of them -- a quarter of the workgroups had eight pairs, a quarter none.)
-__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void balance_tiled_kernel(const int64_t *in, int64_t *out, int k,
+static __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void balance_tiled_kernel(const int64_t *in, int64_t *out, int k,
                                                                                                      const uint32_t *__restrict__ canon, uint32_t ncanon)
 {
     constexpr int T = 3, S = 64;
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
 // segment; the host scans the (small) count array; pass 2 writes.
 constexpr int kSplitSeg = 4096;  // indices per block
 
-__global__ __launch_bounds__(256) void split_count_kernel(int k, uint64_t n, uint32_t *__restrict__ seg_count)
+static __global__ __launch_bounds__(256) void split_count_kernel(int k, uint64_t n, uint32_t *__restrict__ seg_count)
 {
     const uint64_t base = (uint64_t)blockIdx.x * kSplitSeg;
     uint32_t c = 0;
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(256) void split_count_kernel(int k, uint64_t n, uin
     if (threadIdx.x == 0) seg_count[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-__global__ __launch_bounds__(256) void split_write_kernel(const int64_t *__restrict__ c, int k, uint64_t n,
+static __global__ __launch_bounds__(256) void split_write_kernel(const int64_t *__restrict__ c, int k, uint64_t n,
                                                           const uint64_t *__restrict__ seg_offset,
                                                           int64_t *__restrict__ fwd, int64_t *__restrict__ rev)
 {
@@ -398,7 +399,7 @@ __global__ __launch_bounds__(1024) void strand_balance_tiled_kernel(const int64_
 }
 
 // Final fixed-order reduction of per-block partials: out[q] = sum over blocks of partials[q*nblocks + b].
-__global__ __launch_bounds__(256) void reduce_partials_kernel(const Partial *__restrict__ partials, uint32_t nblocks,
+static __global__ __launch_bounds__(256) void reduce_partials_kernel(const Partial *__restrict__ partials, uint32_t nblocks,
                                                               Partial *__restrict__ out)
 {
     const Partial *src = partials + (uint64_t)blockIdx.x * nblocks;

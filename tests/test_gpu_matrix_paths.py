@@ -1,4 +1,4 @@
-"""The distance-matrix dispatch table (distance_matrix_core, kpal_amd/csrc/kpal_vec.hip), row by row.
+"""The distance-matrix dispatch table (distance_matrix_core, kpal_amd/csrc/kpal_cross.hip; its decisions: matrix_plan.hpp), row by row.
 
 kpal_distance_matrix picks one of several kernels from the profile count P, the table size 4^k, the metric and the counts it
 meets; the staged kernels give up through their `big` flag and hand the work on.  Each row below names the kernels it must

@@ -17,7 +17,7 @@ import __graft_entry__ as g
 OUT = os.path.join(ROOT, 'build', 'variants')
 os.makedirs(OUT, exist_ok=True)
 UNITS = sorted(f[:-4] for f in os.listdir(g.CSRC) if f.endswith('.hip'))
-# only these units see the macros (default: the ones that include quad_kernels.hpp; --units=kpal_vec[,...] as the first
+# only these units see the macros (default: the ones that include quad_kernels.hpp; --units=kpal_cross[,...] as the first
 # argument names others); the rest are taken from the regular build
 QUAD_UNITS = ('kpal_quads', 'kpal_quads2')
 
