@@ -353,6 +353,20 @@ int kpal_cross_profile_distance(kpal_ctx *ctx, int k, int Q, const int64_t *cons
 int kpal_cross_profile_distance_device(kpal_ctx *ctx, int k, int Q, const int64_t *dev_left /* Q x 4^k */, int R,
                                        const int64_t *dev_right /* R x 4^k */, const kpal_distance_options *opt,
                                        double *out /* host, Q x R, row-major */);
+/* The two device entries above for an option set WITH dynamic smoothing in a number of launches that does not grow with the
+ * number of pairs.  The reference collapses a node iff min(f(left quarters), f(right quarters)) <= threshold (kdistlib.py:
+ * 99-100), that is iff f(left quarters) <= threshold OR f(right quarters) <= threshold: a flag per profile.  Every profile is
+ * balanced once and gets one pyramid of node sums and node codes (k + 1 launches for all profiles); a pair's distance is the
+ * option arithmetic over the bins and nodes that are live for that pair, two passes of the rectangle kernels and one
+ * reduction.  Same arguments, checks and values (1e-9; unscaled euclidean and cosine bit for bit) as those entries, to which
+ * an option set without do_smooth is handed.  With do_positive (the masks come first: node sums depend on the partner), or
+ * when the pyramids -- ten bytes per node, a third of the tables' bins -- exceed 32 GiB, the pair pipeline per pair of those
+ * entries runs instead.  Inputs are never modified; all workspace is the context's. */
+int kpal_cross_smooth_distance_device(kpal_ctx *ctx, int k, int Q, const int64_t *dev_left /* Q x 4^k */, int R,
+                                      const int64_t *dev_right /* R x 4^k */, const kpal_distance_options *opt,
+                                      double *out /* host, Q x R, row-major */);
+int kpal_smooth_distance_matrix_device(kpal_ctx *ctx, int P, int k, const int64_t *dev_profiles /* P x 4^k */,
+                                       const kpal_distance_options *opt, double *out_lower);
 
 /* ---- profile summaries, merge, shrink ---- */
 /* Profile.total / non_zero / mean / median / std (kpal/klib.py:193-225) of one int64 vector in two

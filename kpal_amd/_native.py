@@ -141,6 +141,9 @@ SIGNATURES = {
     'kpal_profile_distance_matrix': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp), _optp,
                                                     _f64p]),
     'kpal_profile_distance_matrix_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _optp, _f64p]),
+    'kpal_cross_smooth_distance_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, _optp,
+                                                         _f64p]),
+    'kpal_smooth_distance_matrix_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _optp, _f64p]),
     'kpal_stats': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _statp]),
     'kpal_stats_device': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _statp]),
     'kpal_merge': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, _vp]),
@@ -721,6 +724,14 @@ class Context(object):
                                                           ctypes.byref(options), out.ctypes.data_as(_f64p)))
         return out
 
+    def cross_smooth_distance_device(self, k, Q, dev_left, R, dev_right, options):
+        """cross_profile_distance_device with dynamic smoothing from one pyramid per profile: launches that do not grow with
+        Q * R (positive + smoothing, and pyramids past the library's budget, keep its pair pipeline per pair)."""
+        out = np.zeros((int(Q), int(R)), dtype=np.float64)
+        _check(self._L.kpal_cross_smooth_distance_device(self._h, int(k), int(Q), _vp(dev_left), int(R), _vp(dev_right),
+                                                         ctypes.byref(options), out.ctypes.data_as(_f64p)))
+        return out
+
     # -- ProfileDistance with options ------------------------------------------------------------
     def profile_distance(self, left, right, k, options):
         """ProfileDistance.distance for a DistanceOptions (kdistlib.py:126-161)."""
@@ -801,6 +812,13 @@ class Context(object):
         out = np.zeros(P * (P - 1) // 2, dtype=np.float64)
         _check(self._L.kpal_profile_distance_matrix_device(self._h, int(P), int(k), _vp(dev_profiles), ctypes.byref(options),
                                                            out.ctypes.data_as(_f64p)))
+        return out
+
+    def smooth_distance_matrix_device(self, P, k, dev_profiles, options):
+        """profile_distance_matrix_device with dynamic smoothing from one pyramid per profile (cross_smooth_distance_device)."""
+        out = np.zeros(P * (P - 1) // 2, dtype=np.float64)
+        _check(self._L.kpal_smooth_distance_matrix_device(self._h, int(P), int(k), _vp(dev_profiles), ctypes.byref(options),
+                                                          out.ctypes.data_as(_f64p)))
         return out
 
     # -- profiling ---------------------------------------------------------------------------

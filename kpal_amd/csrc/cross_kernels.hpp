@@ -31,6 +31,23 @@ struct CrossOpt {
     uint32_t roff;
     uint32_t slots;          // 16 * tiles: the stride between the accumulators of one pair
 };
+// ... of an accumulator with CODES (SmoothAcc, smooth_set_kernels.hpp): one code per node beside the values, profile p's at
+// codes + p * cstride.  cshift 0: the elements ARE the nodes; 2: the elements are bins, whose code follows from bottom node
+// (bin >> 2)'s.  An accumulator names what its kernels are launched with (Opt), so the others' arguments stay what they were.
+struct CrossCodeOpt : CrossOpt {
+    const uint8_t *lcodes, *rcodes;
+    uint64_t cstride;
+    int cshift;
+};
+
+// The code of element i of a profile whose node codes lie at `codes` (CrossCodeOpt::cshift).
+__device__ __forceinline__ uint8_t cross_code(const uint8_t *codes, uint64_t i, int shift)
+{
+    const uint8_t c = codes[i >> shift];
+    return shift ? (uint8_t)(c ? 2 : 1) : c;
+}
+
+constexpr int kCodeRow = 80;   // bytes of a staged row of codes: rows four apart lie 16 banks apart for the groups' 4-byte reads
 
 // Number t of a tile (or super-tile) -> (ti, tj): row-major over `side` columns, or the lower triangle's ti (ti + 1) / 2 + tj.
 __device__ __forceinline__ void cross_tile(uint32_t t, int side, bool tri, int &ti, int &tj)
@@ -88,11 +105,14 @@ __device__ __forceinline__ CrossGroup cross_group(const CrossSets &c, const Cros
 // The plain metrics (0 / 1: multiset prod / sum, metrics.py:121-123; 2: euclidean as a wrapping int64 dot, metrics.py:135,46)
 // as an accumulator of the two skeletons.  An accumulator says how many (s, m) pairs it writes per pair of profiles (NACC),
 // whether the staged skeleton should stage the reciprocals 1 / (x + 1) beside the values (RCP: 'prod' then takes
-// matrix_accumulate_prod_rcp), and what a pair's (s, m) is once the bins are through.
+// matrix_accumulate_prod_rcp), whether it takes a code per value as well (CODES: add(x, y, cx, cy)), and what a pair's
+// (s, m) is once the bins are through.
 template <int METRIC>
 struct PlainAcc {
     static constexpr int NACC = 1;
     static constexpr bool RCP = METRIC == 0;
+    static constexpr bool CODES = false;
+    using Opt = CrossOpt;
     double s[4][4];
     unsigned long long m[4][4];   // the euclidean dots
     uint32_t mf[4][4];            // multiset: number of terms (a thread sees fewer than 2^32 bins)
@@ -127,7 +147,7 @@ struct PlainAcc {
 // blockIdx.x = tile * gx + slice: tile (tq, tr) of 4 x 4 pairs, the slices stride over the bins.  Each thread streams one
 // bin at a time of the four row and four column profiles (coalesced 512-byte wave loads per profile).
 template <class Acc>
-__global__ __launch_bounds__(256) void cross_tile_kernel(const CrossOpt o, uint32_t gx, Partial *__restrict__ partials)
+__global__ __launch_bounds__(256) void cross_tile_kernel(const typename Acc::Opt o, uint32_t gx, Partial *__restrict__ partials)
 {
     const CrossSets &c = o.c;
     const int sideR = (c.R + 3) / 4;
@@ -143,6 +163,15 @@ __global__ __launch_bounds__(256) void cross_tile_kernel(const CrossOpt o, uint3
         rowp[a] = c.left + (uint64_t)min(tq * 4 + a, c.Q - 1) * c.n;
         colp[a] = c.right + (uint64_t)min(tr * 4 + a, c.R - 1) * c.n;
     }
+    const uint8_t *rowc[Acc::CODES ? 4 : 1];
+    const uint8_t *colc[Acc::CODES ? 4 : 1];
+    if constexpr (Acc::CODES) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            rowc[a] = o.lcodes + (uint64_t)min(tq * 4 + a, c.Q - 1) * o.cstride;
+            colc[a] = o.rcodes + (uint64_t)min(tr * 4 + a, c.R - 1) * o.cstride;
+        }
+    }
     for (uint64_t i = (uint64_t)slice * blockDim.x + threadIdx.x; i < c.n; i += (uint64_t)gx * blockDim.x) {
         int64_t x[4], y[4];
 #pragma unroll
@@ -150,7 +179,17 @@ __global__ __launch_bounds__(256) void cross_tile_kernel(const CrossOpt o, uint3
             x[a] = rowp[a][i];
             y[a] = colp[a][i];
         }
-        acc.add(x, y);
+        if constexpr (Acc::CODES) {
+            uint8_t cx[4], cy[4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                cx[a] = cross_code(rowc[a], i, o.cshift);
+                cy[a] = cross_code(colc[a], i, o.cshift);
+            }
+            acc.add(x, y, cx, cy);
+        } else {
+            acc.add(x, y);
+        }
     }
     acc.finish();
 #pragma unroll
@@ -171,7 +210,7 @@ __global__ __launch_bounds__(256) void cross_tile_kernel(const CrossOpt o, uint3
 // so that the column rows of the two groups of a half-wave (4 rows apart) sit 32 banks apart for ds_read_b64.  Grid:
 // cross_block; bin-group g takes the chunks g, g + ngroups, ...
 template <class Acc>
-__global__ __launch_bounds__(256) void cross_super_kernel(const CrossOpt o, uint32_t nsuper, int superR, Partial *__restrict__ partials)
+__global__ __launch_bounds__(256) void cross_super_kernel(const typename Acc::Opt o, uint32_t nsuper, int superR, Partial *__restrict__ partials)
 {
     constexpr bool RCP = Acc::RCP;                 // 'prod': reciprocals 1 / (x + 1) staged next to the values
     __shared__ int64_t stage[2][32][kSuperRow];
@@ -180,6 +219,10 @@ __global__ __launch_bounds__(256) void cross_super_kernel(const CrossOpt o, uint
         stage[buf][row][col] = v;
         if constexpr (RCP) rstage[buf][row][col] = rcp_counts((double)(uint32_t)v + 1.0);   // (unused when v >= 2^31)
     };
+    // CODES: the code of bin 16 u + l of a row is byte u of its word l -- a lane reads the codes of its four bins at once
+    constexpr bool CODES = Acc::CODES;
+    __shared__ __attribute__((aligned(4))) uint8_t cstage[CODES ? 2 : 1][CODES ? 32 : 1][CODES ? kCodeRow : 4];
+    auto put_code = [&](int buf, int row, int col, uint8_t v) { cstage[buf][row][4 * (col & 15) + (col >> 4)] = v; };
     const CrossSets &c = o.c;
     const CrossBlock blk = cross_block(c, nsuper, superR);
     const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
@@ -193,12 +236,26 @@ __global__ __launch_bounds__(256) void cross_super_kernel(const CrossOpt o, uint
     const int64_t *src[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) src[q] = cross_row(c, blk.si, blk.sj, 4 * q + lrow) + lcol;
+    const uint8_t *csrc[CODES ? 8 : 1];
+    if constexpr (CODES) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int r = 4 * q + lrow;
+            csrc[q] = r < 16 ? o.lcodes + (uint64_t)min(blk.si * 16 + r, c.Q - 1) * o.cstride
+                             : o.rcodes + (uint64_t)min(blk.sj * 16 + (r - 16), c.R - 1) * o.cstride;
+        }
+    }
     const uint64_t chunks = c.n / kSuperBins;
     int64_t next[8];
+    uint8_t nextc[CODES ? 8 : 1];
     uint64_t ch = blk.group;
     if (ch < chunks) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) put(0, 4 * q + lrow, lcol, src[q][ch * kSuperBins]);
+        if constexpr (CODES) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) put_code(0, 4 * q + lrow, lcol, cross_code(csrc[q], ch * kSuperBins + lcol, o.cshift));
+        }
     }
     __syncthreads();
     int cur = 0;
@@ -207,8 +264,20 @@ __global__ __launch_bounds__(256) void cross_super_kernel(const CrossOpt o, uint
         if (more) {
 #pragma unroll
             for (int q = 0; q < 8; ++q) next[q] = src[q][(ch + blk.ngroups) * kSuperBins];
+            if constexpr (CODES) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) nextc[q] = cross_code(csrc[q], (ch + blk.ngroups) * kSuperBins + lcol, o.cshift);
+            }
         }
         if (mine) {
+            uint32_t wx[CODES ? 4 : 1], wy[CODES ? 4 : 1];
+            if constexpr (CODES) {
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    wx[a] = *reinterpret_cast<const uint32_t *>(&cstage[cur][4 * (g >> 2) + a][4 * l]);
+                    wy[a] = *reinterpret_cast<const uint32_t *>(&cstage[cur][16 + 4 * (g & 3) + a][4 * l]);
+                }
+            }
 #pragma unroll 1   // (unrolled 2 / 4 times: 21.3 / 20.4 ms against 19.9 for 64 profiles at k = 12)
             for (int u = 0; u < kSuperBins / 16; ++u) {
                 int64_t x[4], y[4];
@@ -225,6 +294,14 @@ __global__ __launch_bounds__(256) void cross_super_kernel(const CrossOpt o, uint
                         ry[a] = rstage[cur][16 + 4 * (g & 3) + a][16 * u + l];
                     }
                     acc.add(x, y, rx, ry);
+                } else if constexpr (CODES) {
+                    uint8_t cx[4], cy[4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        cx[a] = (uint8_t)(wx[a] >> (8 * u));
+                        cy[a] = (uint8_t)(wy[a] >> (8 * u));
+                    }
+                    acc.add(x, y, cx, cy);
                 } else {
                     acc.add(x, y);
                 }
@@ -233,6 +310,10 @@ __global__ __launch_bounds__(256) void cross_super_kernel(const CrossOpt o, uint
         if (more) {
 #pragma unroll
             for (int q = 0; q < 8; ++q) put(cur ^ 1, 4 * q + lrow, lcol, next[q]);
+            if constexpr (CODES) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) put_code(cur ^ 1, 4 * q + lrow, lcol, nextc[q]);
+            }
         }
         __syncthreads();
         cur ^= 1;

@@ -1,7 +1,8 @@
 // cross_option_kernels.hpp -- the Q x R rectangle (and the lower triangle of a set against itself) for every built-in
 // ProfileDistance that is NOT plain: any mix of positive, scale (+- down) and the metrics prod / sum / euclidean / cosine
-// (kpal_cross_profile_distance[_device], kpal_profile_distance_matrix_device).  Dynamic smoothing is not here: a node's
-// collapse decision depends on both partners, so smoothed tables exist per pair only (kpal_cross.hip loops the pair pipeline).
+// (kpal_cross_profile_distance[_device], kpal_profile_distance_matrix_device).  Dynamic smoothing is not here: these entries
+// keep one pair pipeline per pair (kpal_cross.hip loops it); a node's collapse decision is an OR of one flag per partner, and
+// smooth_set_kernels.hpp runs the smoothed rectangle from per-profile pyramids with this file's arithmetic (SmoothAcc).
 //
 // The arithmetic of a term is option_distance_kernel<METRIC, SCALED>'s (option_kernels.hpp), term for term: wrapping int64
 // when unscaled, float64 `count * scale` when scaled, IEEE division in the multiset terms.  What is new is that the steps
@@ -40,6 +41,8 @@ template <int MODE, bool SCALED, bool POSITIVE>
 struct OptAcc {
     static constexpr int NACC = MODE == 3 ? 3 : MODE == kOptTotals ? 2 : 1;
     static constexpr bool RCP = false;
+    static constexpr bool CODES = false;
+    using Opt = CrossOpt;
     double s[NACC][4][4];
     unsigned long long m[NACC][4][4];
     double ls[4][4], rs[4][4];
@@ -86,40 +89,45 @@ struct OptAcc {
                     xi = both ? xi : 0;
                     yi = both ? yi : 0;
                 }
-                if constexpr (MODE == kOptTotals) {
-                    m[0][a][b] += (uint64_t)xi;
-                    m[1][a][b] += (uint64_t)yi;
-                } else if constexpr (SCALED) {
-                    const double xd = (double)xi * ls[a][b], yd = (double)yi * rs[a][b];
-                    if constexpr (MODE <= 1) {
-                        if (xd != 0.0 || yd != 0.0) {
-                            s[0][a][b] += MODE == 0 ? pw_prod(xd, yd) : pw_sum(xd, yd);
-                            m[0][a][b] += 1;
-                        }
-                    } else if constexpr (MODE == 2) {
-                        const double d = xd - yd;
-                        s[0][a][b] += d * d;
-                    } else {
-                        s[0][a][b] += xd * yd;
-                        s[1][a][b] += xd * xd;
-                        s[2][a][b] += yd * yd;
-                    }
-                } else {
-                    if constexpr (MODE <= 1) {
-                        if (xi != 0 || yi != 0) {
-                            s[0][a][b] += MODE == 0 ? pw_prod(xi, yi) : pw_sum(xi, yi);
-                            m[0][a][b] += 1;
-                        }
-                    } else if constexpr (MODE == 2) {
-                        const uint64_t d = (uint64_t)xi - (uint64_t)yi;
-                        m[0][a][b] += d * d;
-                    } else {
-                        m[0][a][b] += (uint64_t)xi * (uint64_t)yi;
-                        m[1][a][b] += (uint64_t)xi * (uint64_t)xi;
-                        m[2][a][b] += (uint64_t)yi * (uint64_t)yi;
-                    }
-                }
+                term(a, b, xi, yi);
             }
+    }
+    // the term of pair (a, b) for the counts (xi, yi) that are left of a bin
+    __device__ __forceinline__ void term(int a, int b, int64_t xi, int64_t yi)
+    {
+        if constexpr (MODE == kOptTotals) {
+            m[0][a][b] += (uint64_t)xi;
+            m[1][a][b] += (uint64_t)yi;
+        } else if constexpr (SCALED) {
+            const double xd = (double)xi * ls[a][b], yd = (double)yi * rs[a][b];
+            if constexpr (MODE <= 1) {
+                if (xd != 0.0 || yd != 0.0) {
+                    s[0][a][b] += MODE == 0 ? pw_prod(xd, yd) : pw_sum(xd, yd);
+                    m[0][a][b] += 1;
+                }
+            } else if constexpr (MODE == 2) {
+                const double d = xd - yd;
+                s[0][a][b] += d * d;
+            } else {
+                s[0][a][b] += xd * yd;
+                s[1][a][b] += xd * xd;
+                s[2][a][b] += yd * yd;
+            }
+        } else {
+            if constexpr (MODE <= 1) {
+                if (xi != 0 || yi != 0) {
+                    s[0][a][b] += MODE == 0 ? pw_prod(xi, yi) : pw_sum(xi, yi);
+                    m[0][a][b] += 1;
+                }
+            } else if constexpr (MODE == 2) {
+                const uint64_t d = (uint64_t)xi - (uint64_t)yi;
+                m[0][a][b] += d * d;
+            } else {
+                m[0][a][b] += (uint64_t)xi * (uint64_t)yi;
+                m[1][a][b] += (uint64_t)xi * (uint64_t)xi;
+                m[2][a][b] += (uint64_t)yi * (uint64_t)yi;
+            }
+        }
     }
     __device__ __forceinline__ void finish() {}
     __device__ __forceinline__ Partial partial(int n, int a, int b) const { return Partial{s[n][a][b], m[n][a][b]}; }

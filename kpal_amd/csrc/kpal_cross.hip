@@ -8,12 +8,16 @@
 // on the values; matrix_all_kernels.hpp for a multiset triangle of 17..64 profiles; the fp64 Gram matrix on the matrix cores
 // for euclidean), one fixed-order reduction of the per-workgroup partials.
 //   with options (cross_option_kernels.hpp): a totals pass or a masked-totals rectangle pass more when the profiles are scaled;
-// dynamic smoothing alone stays one pair pipeline (kpal_pair.hip) per pair, on tables balanced once.
+// dynamic smoothing in those entries stays one pair pipeline (kpal_pair.hip) per pair, on tables balanced once.
+//   dynamic smoothing over whole sets (kpal_cross_smooth_distance_device, kpal_smooth_distance_matrix_device; smooth_plan.hpp,
+// smooth_set_kernels.hpp): one pyramid of node sums and codes per profile (k + 1 launches for all of them), then two passes of
+// the rectangle kernels, over the bins and over the pyramids, and one reduction.
 #include "kpal_host.hpp"
 
 #include "cross_kernels.hpp"
 #include "cross_option_kernels.hpp"
 #include "matrix_all_kernels.hpp"
+#include "smooth_set_kernels.hpp"
 
 static const MatrixSwitches &matrix_switches()
 {
@@ -152,7 +156,7 @@ static int cross_gram_euclidean(kpal_ctx *ctx, const CrossSets &c, double *out, 
 }
 
 template <class Acc>
-static int launch_cross(kpal_ctx *ctx, const char *name, bool staged, const CrossOpt &o, const CrossGrid &g, Partial *pp)
+static int launch_cross(kpal_ctx *ctx, const char *name, bool staged, const typename Acc::Opt &o, const CrossGrid &g, Partial *pp)
 {
     if (staged) LAUNCH(ctx, name, (cross_super_kernel<Acc>), dim3(g.gx * g.units), dim3(256), o, g.units, g.superR, pp);
     else LAUNCH(ctx, name, (cross_tile_kernel<Acc>), dim3(g.gx * g.units), dim3(256), o, g.gx, pp);
@@ -388,7 +392,8 @@ KPAL_API int kpal_cross_profile_distance_device(kpal_ctx *ctx, int k, int Q, con
     CrossSets c = {dev_left, dev_right, Q, R, n, 0};
     if (opt->do_balance) CHK(balance_sets(ctx, k, c));
     if (opt->do_smooth) {
-        // smoothed tables exist per pair only (a node collapses by both partners' counts): the pair pipeline on the balanced tables
+        // this entry materialises the smoothed tables of every pair: the pair pipeline on the balanced tables
+        // (kpal_cross_smooth_distance_device runs the rectangle from per-profile pyramids instead)
         for (int q = 0; q < Q; ++q)
             for (int r = 0; r < R; ++r)
                 CHK(profile_distance_pair(ctx, k, c.left + (uint64_t)q * n, c.right + (uint64_t)r * n, opt, true, &out[(size_t)q * R + r]));
@@ -447,4 +452,107 @@ KPAL_API int kpal_profile_distance_matrix(kpal_ctx *ctx, int P, int k, const int
     CHK(upload_set(ctx, prof, P, n, host_profiles, "profile"));
     // uploaded once; balanced once per profile and every pair in a fixed number of launches
     return kpal_profile_distance_matrix_device(ctx, P, k, prof, opt, out_lower);
+}
+
+// ----------------------------------------------------------------------------------------------
+// dynamic smoothing over a rectangle / a lower triangle (smooth_plan.hpp, smooth_set_kernels.hpp)
+// ----------------------------------------------------------------------------------------------
+template <int MODE>
+static int launch_smooth_pass(kpal_ctx *ctx, bool staged, bool scaled, const CrossCodeOpt &o, const CrossGrid &g, Partial *pp)
+{
+    const char *name = staged ? "smooth_set_super" : "smooth_set_tile";
+    return scaled ? launch_cross<SmoothAcc<MODE, true>>(ctx, name, staged, o, g, pp) : launch_cross<SmoothAcc<MODE, false>>(ctx, name, staged, o, g, pp);
+}
+
+// Every pair of c (c.tri: below the diagonal) with dynamic smoothing and no positive step, from tables that are already
+// balanced and are not written.  out: Q x R row-major, or the lower triangle in distance_matrix order.
+static int cross_smooth_core(kpal_ctx *ctx, int k, const CrossSets &c, const kpal_distance_options *opt, double *out)
+{
+    const bool scaled = opt->do_scale != 0, tri = c.tri != 0;
+    const uint32_t nprof = tri ? (uint32_t)c.Q : (uint32_t)c.Q + (uint32_t)c.R;
+    const uint64_t stride = smooth_stride(k), elements = (uint64_t)nprof * stride;
+    // both passes take the kernel kind and the grid of the bins: groups without a chunk of the (three times shorter) pyramids
+    // write zeros, and the pyramid pass is `nacc` accumulators more of ONE partial layout
+    const bool staged = cross_staged(c.Q, c.R, c.n);
+    const CrossGrid g = cross_grid(ctx->num_cu, c, staged);
+    const uint32_t nacc = option_nacc(opt->metric), gx = g.gx;
+    const uint64_t slots = g.slots;
+    if (partials_too_many(slots * nacc * 2, gx)) return set_err(KPAL_E_INVALID, "cross distance: %d x %d profiles are too many for one call", c.Q, c.R);
+    CHK(ensure(ctx, ctx->opt_levels, (size_t)smooth_scratch_bytes(k, nprof)));
+    CHK(ensure(ctx, ctx->scratch[3], (size_t)nprof * sizeof(Partial)));
+    CHK(ensure(ctx, ctx->partials, (size_t)slots * nacc * 2 * gx * sizeof(Partial)));
+    int64_t *sums = (int64_t *)ctx->opt_levels.p;
+    uint8_t *codes = (uint8_t *)(sums + elements);
+    Partial *pp = (Partial *)ctx->partials.p, *totals = (Partial *)ctx->scratch[3].p;
+    const SmoothSet set = {c, nprof, k, stride, sums, codes, codes + elements, totals};
+    for (int h = 0; h < k; ++h) {
+        const uint32_t per = option_totals_gx(ctx->num_cu, nprof, smooth_level_nodes(k, h));
+        LAUNCH(ctx, "smooth_set_level", smooth_set_level_kernel, dim3(nprof * per), dim3(256), set, h, per, opt->summary, opt->threshold);
+    }
+    const uint32_t per = option_totals_gx(ctx->num_cu, nprof, stride);
+    LAUNCH(ctx, "smooth_set_codes", smooth_set_codes_kernel, dim3(nprof * per), dim3(256), set, per);
+    const uint8_t *rcodes = tri ? codes : codes + (uint64_t)c.Q * stride;
+    const CrossCodeOpt bins = {{c, opt->down ? 1 : 0, totals, tri ? 0u : (uint32_t)c.Q, (uint32_t)slots}, codes, rcodes, stride, 2};
+    const CrossSets pyramids = {sums, tri ? sums : sums + (uint64_t)c.Q * stride, c.Q, c.R, stride, c.tri};
+    const CrossCodeOpt nodes = {{pyramids, bins.down, totals, bins.roff, bins.slots}, codes, rcodes, stride, 0};
+    Partial *pass[2] = {pp, pp + slots * nacc * gx};
+    const CrossCodeOpt *of[2] = {&bins, &nodes};
+    for (int i = 0; i < 2; ++i)
+        switch (opt->metric) {
+        case KPAL_PAIRWISE_PROD: CHK(launch_smooth_pass<0>(ctx, staged, scaled, *of[i], g, pass[i])); break;
+        case KPAL_PAIRWISE_SUM: CHK(launch_smooth_pass<1>(ctx, staged, scaled, *of[i], g, pass[i])); break;
+        case KPAL_EUCLIDEAN: CHK(launch_smooth_pass<2>(ctx, staged, scaled, *of[i], g, pass[i])); break;
+        default: CHK(launch_smooth_pass<3>(ctx, staged, scaled, *of[i], g, pass[i])); break;
+        }
+    std::vector<Partial> res;
+    CHK(finish_partials(ctx, (uint32_t)(slots * nacc * 2), gx, res));
+    auto value = [&](int i, int j) -> double {
+        const size_t slot = cross_slot(c, g.sideR, i, j);
+        Partial p[3];
+        for (uint32_t a = 0; a < nacc; ++a) {   // bins, then nodes: a fixed order
+            const Partial &b = res[a * slots + slot], &n = res[(nacc + a) * slots + slot];
+            p[a] = Partial{b.s + n.s, b.m + n.m};
+        }
+        return finish_distance(opt->metric, scaled, p[0], p[nacc / 2], p[nacc - 1]);
+    };
+    if (tri) {
+        for (int i = 1; i < c.Q; ++i)
+            for (int j = 0; j < i; ++j) out[triangle_index(i, j)] = value(i, j);
+    } else {
+        for (int q = 0; q < c.Q; ++q)
+            for (int r = 0; r < c.R; ++r) out[(size_t)q * c.R + r] = value(q, r);
+    }
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_cross_smooth_distance_device(kpal_ctx *ctx, int k, int Q, const int64_t *dev_left, int R, const int64_t *dev_right,
+                                               const kpal_distance_options *opt, double *out)
+{
+    CTX_ENTER(ctx);
+    CHK(check_options(opt));
+    if (!opt->do_smooth) return kpal_cross_profile_distance_device(ctx, k, Q, dev_left, R, dev_right, opt, out);
+    CHK(cross_check(k, Q, R, 0, dev_left, dev_right, out));
+    if (((uintptr_t)dev_left & 15) || ((uintptr_t)dev_right & 15)) return set_err(KPAL_E_INVALID, "device tables must be 16-byte aligned");
+    // with positive, or past the budget: one pair pipeline per pair
+    if (!smooth_batched(k, Q, R, opt->do_positive != 0, kSmoothBudgetBytes)) return kpal_cross_profile_distance_device(ctx, k, Q, dev_left, R, dev_right, opt, out);
+    CrossSets c = {dev_left, dev_right, Q, R, 1ULL << (2 * k), 0};
+    if (opt->do_balance) CHK(balance_sets(ctx, k, c));
+    return cross_smooth_core(ctx, k, c, opt, out);
+}
+
+KPAL_API int kpal_smooth_distance_matrix_device(kpal_ctx *ctx, int P, int k, const int64_t *dev_profiles,
+                                                const kpal_distance_options *opt, double *out_lower)
+{
+    CTX_ENTER(ctx);
+    if (P < 1) return set_err(KPAL_E_INVALID, "P must be >= 1");
+    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
+    CHK(check_options(opt));
+    if (P == 1) return KPAL_OK;
+    if (!dev_profiles || !out_lower) return set_err(KPAL_E_INVALID, "NULL pointer");
+    if (!opt->do_smooth || !smooth_batched(k, P, 0, opt->do_positive != 0, kSmoothBudgetBytes))
+        return kpal_profile_distance_matrix_device(ctx, P, k, dev_profiles, opt, out_lower);
+    if ((uintptr_t)dev_profiles & 15) return set_err(KPAL_E_INVALID, "device tables must be 16-byte aligned");
+    CrossSets c = {dev_profiles, dev_profiles, P, P, 1ULL << (2 * k), 1};
+    if (opt->do_balance) CHK(balance_sets(ctx, k, c));
+    return cross_smooth_core(ctx, k, c, opt, out_lower);
 }

@@ -15,10 +15,9 @@
 #include <stdint.h>
 
 #include "vec_kernels.hpp"
+#include "smooth_summary.hpp"   // summarise4: shared with smooth_set_kernels.hpp, so that both decide a tie alike
 
 namespace kpal {
-
-constexpr int kSummaryMin = 0, kSummaryAverage = 1, kSummaryMedian = 2;
 
 // left' = left * bool(right); right' = right * bool(left')  ==  both zero unless both non-zero.
 __global__ __launch_bounds__(256) void positive_kernel(const int64_t *__restrict__ l, const int64_t *__restrict__ r,
@@ -30,19 +29,6 @@ __global__ __launch_bounds__(256) void positive_kernel(const int64_t *__restrict
         lo[i] = both ? x : 0;
         ro[i] = both ? y : 0;
     }
-}
-
-// Summary of four int64 quarter sums as NumPy evaluates it on an int64 array of length 4:
-// np.min -> the integer; np.mean -> float64 sum of the converted values / 4; np.median -> mean of
-// the two middle values.  Returned as double for the comparison with the threshold.
-__device__ __forceinline__ double summarise4(const int64_t (&q)[4], int summary)
-{
-    if (summary == kSummaryMin) return (double)min(min(q[0], q[1]), min(q[2], q[3]));
-    if (summary == kSummaryAverage) return ((((double)q[0] + (double)q[1]) + (double)q[2]) + (double)q[3]) / 4.0;
-    // median: sort four values with a 5-comparator network, average the middle two
-    int64_t a = min(q[0], q[1]), b = max(q[0], q[1]), c = min(q[2], q[3]), d = max(q[2], q[3]);
-    const int64_t lo = max(a, c), hi = min(b, d);   // the two middle values are {max of mins, min of maxes}
-    return ((double)min(lo, hi) + (double)max(lo, hi)) / 2.0;
 }
 
 // One level: node j of `nparent` nodes has the four children child[4j .. 4j+3] (the level below,

@@ -12,7 +12,8 @@ a user-supplied callable cannot enter a kernel and keeps the reference's NumPy f
 
 Beyond the reference: :func:`cross_distances` / :func:`cross_distance_matrix` / :func:`nearest` -- the Q x R rectangle of
 distances between a left and a right set of profiles (``kpal_cross_distance_device``; with positive / scale / cosine
-``kpal_cross_profile_distance_device``), a fixed number of launches per chunk of the right side.
+``kpal_cross_profile_distance_device``; with dynamic smoothing ``kpal_cross_smooth_distance_device``), a fixed number of
+launches per chunk of the right side.
 """
 import numpy as np
 
@@ -175,6 +176,14 @@ def distance_matrix(profiles, output, precision, dist):
     if dist._is_plain() and metric is not None and metric != _native.COSINE and same_k and integer:
         values = _native.context().distance_matrix([p.counts for p in profiles], profiles[0].length, metric,
                                                    do_balance=dist._do_balance)
+    elif options is not None and options.do_smooth:
+        # gathered once; one pyramid of node sums and codes per profile, every pair through the rectangle kernels
+        ctx = _cross_context(profiles)
+        pset = _DeviceSet(ctx, profiles)
+        try:
+            values = ctx.smooth_distance_matrix_device(count, profiles[0].length, pset.ptr, options)
+        finally:
+            pset.release()
     elif options is not None:
         # profiles uploaded (and balanced) once, every pair through the option kernels
         values = _native.context().profile_distance_matrix([p.counts for p in profiles], profiles[0].length, options)
@@ -271,9 +280,12 @@ def cross_distances(left_profiles, right_profiles, dist, max_bytes=None):
     lie.  Any other ``dist`` made of built-ins -- positive, scale, cosine -- takes the same route through
     ``kpal_cross_profile_distance_device``: each profile balanced once, the masks and the pairs' scale factors applied inside
     the rectangle kernels (one totals pass, or one more rectangle pass for the masked totals of positive + scale), still a
-    fixed number of launches per chunk.  Dynamic smoothing is one call per chunk as well, but runs the pair pipeline once per
-    pair inside the library (smoothed tables depend on both partners).  A user-supplied callable, a non-numeric threshold,
-    mixed k or non-integer counts are ``dist.distance`` pair by pair."""
+    fixed number of launches per chunk.  So is dynamic smoothing (``kpal_cross_smooth_distance_device``): a node collapses when
+    the summary of EITHER partner's quarters is at or below the threshold, a flag per profile, so every profile gets one
+    pyramid of node sums and codes and a pair's distance is taken over the bins and nodes live for that pair.  Only positive
+    + smoothing (node sums of masked tables depend on the partner), and pyramids past the library's 32 GiB budget, run the pair
+    pipeline once per pair inside the library.  A user-supplied callable, a non-numeric threshold, mixed k or non-integer
+    counts are ``dist.distance`` pair by pair."""
     left = list(left_profiles)
     if not left:
         raise ValueError('cross_distances needs at least one left profile')
@@ -302,6 +314,8 @@ def cross_distances(left_profiles, right_profiles, dist, max_bytes=None):
                 if plain:
                     blocks.append(ctx.cross_distance_device(k, len(left), lset.ptr, len(chunk), rset.ptr, metric,
                                                             do_balance=dist._do_balance))
+                elif options.do_smooth:
+                    blocks.append(ctx.cross_smooth_distance_device(k, len(left), lset.ptr, len(chunk), rset.ptr, options))
                 else:
                     blocks.append(ctx.cross_profile_distance_device(k, len(left), lset.ptr, len(chunk), rset.ptr, options))
             finally:
@@ -390,6 +404,8 @@ def _device_matrix(profiles, dist, metric):
             gathered = base = ctx.alloc(P * table_bytes)
             for i in range(P):
                 ctx.d2d(base + i * table_bytes, devs[i][1], table_bytes)
+        if not plain and options.do_smooth:    # one call: a pyramid per profile, the pairs' live elements inside the triangle kernels
+            return ctx.smooth_distance_matrix_device(P, k, base, options)
         if not plain:    # one call: profiles balanced once, the partner-dependent steps inside the triangle kernels
             return ctx.profile_distance_matrix_device(P, k, base, options)
         return ctx.distance_matrix_device(P, k, base, metric, do_balance=dist._do_balance)

@@ -10,7 +10,11 @@ JSON record (and prints it).
 With --options="-S --positive" (any of -b --positive -S -d, -D cosine|euclidean, -P sum): kpal_cross_profile_distance_device
 timed against one kpal_profile_distance_device call per pair -- what cross_distances did for such a distance before the
 rectangle took options -- in the same process on the same tables.
-    python tools/xbench.py --Q 64 --R 64 --k 12 --options=-S --out profiles/cross/xbench_options_k12_64x64_S.json"""
+    python tools/xbench.py --Q 64 --R 64 --k 12 --options=-S --out profiles/cross/xbench_options_k12_64x64_S.json
+With -m among the options (dynamic smoothing; -s min|average|median, -t THRESHOLD): kpal_cross_smooth_distance_device -- one
+pyramid per profile, launches that do not grow with Q x R -- timed against kpal_cross_profile_distance_device on the same
+tables, which loops the pair pipeline inside the library as every smoothed rectangle did before (--pair-reps: its repeats).
+    python tools/xbench.py --Q 64 --R 64 --k 12 --options="-m -S" --pair-reps 1 --out profiles/cross/xbench_smooth_k12_64x64_m_S.json"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -101,15 +105,23 @@ def option_run():
     op.add_argument('-d', dest='down', action='store_true')
     op.add_argument('-D', dest='function', default=None, choices=('euclidean', 'cosine'))
     op.add_argument('-P', dest='pairwise', default='prod', choices=('prod', 'sum'))
+    op.add_argument('-m', dest='do_smooth', action='store_true')
+    op.add_argument('-s', dest='summary', default='min', choices=('min', 'average', 'median'))
+    op.add_argument('-t', dest='threshold', type=float, default=0.0)
     o = op.parse_args(a.options.split())
     code = {'euclidean': 2, 'cosine': 3}[o.function] if o.function else {'prod': 0, 'sum': 1}[o.pairwise]
     options = _native.DistanceOptions(do_balance=int(o.do_balance), do_positive=int(o.do_positive), do_scale=int(o.do_scale),
-                                      down=int(o.down), metric=code)
+                                      down=int(o.down), metric=code, do_smooth=int(o.do_smooth),
+                                      summary=('min', 'average', 'median').index(o.summary), threshold=o.threshold)
 
     def rectangle():
+        if o.do_smooth:
+            return ctx.cross_smooth_distance_device(a.k, Q, dleft, R, dright, options)
         return ctx.cross_profile_distance_device(a.k, Q, dleft, R, dright, options)
 
     def pair_loop():
+        if o.do_smooth:                                 # the pair pipeline per pair inside the library: the entry as it was
+            return ctx.cross_profile_distance_device(a.k, Q, dleft, R, dright, options)
         out = np.empty((Q, R))
         for q in range(Q):
             for r in range(R):
@@ -128,7 +140,8 @@ def option_run():
     worst_rel = float(rel[np.isfinite(want)].max()) if np.isfinite(want).any() else 0.0
     assert same_kind and worst_rel <= 2e-9, (same_kind, worst_rel)        # each is within 1e-9 of the reference's value
     rec = {'tool': 'tools/xbench.py --options', 'src_sha': bench.source_sha(), 'k': a.k, 'Q': Q, 'R': R, 'options': a.options,
-           'reads_per_profile': a.reads, 'cross_profile_distance_device': t_rect, 'per_pair_loop': t_pair,
+           'reads_per_profile': a.reads, 'cross_smooth_distance_device' if o.do_smooth else 'cross_profile_distance_device': t_rect,
+           'cross_profile_distance_device_pair_loop' if o.do_smooth else 'per_pair_loop': t_pair,
            'median_below_per_pair_min': t_rect['median_ms'] < t_pair['min_ms'],
            'speedup_median_over_per_pair_min': t_pair['min_ms'] / t_rect['median_ms'],
            'table_bytes_read_once': (Q + R) * table, 'kernels_of_one_call': kernels, 'max_relative_difference': worst_rel}
