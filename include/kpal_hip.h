@@ -176,6 +176,31 @@ int kpal_fasta_records_file_open(kpal_ctx *ctx, const char *path, uint64_t begin
 int kpal_fasta_records_file_next(kpal_ctx *ctx, uint64_t *n_records, uint64_t *flat_bytes, uint64_t *text_offset, int *done);
 int kpal_fasta_records_file_tell(kpal_ctx *ctx, uint64_t *offset);   /* file offset of the first byte no piece has covered yet: where a closed scan is opened again */
 int kpal_fasta_records_file_close(kpal_ctx *ctx);
+/* The same index over four-line FASTQ text, one record per READ (beyond the reference; the rules of kpal_count_feed_fastq:
+ * validation, the quality mask and the flattening are the count path's own tokeniser).  kpal_fastq_records_begin fills the
+ * index that kpal_fasta_records_begin fills -- header_off is the offset of the read's title line ('@') in host_text, flat_start
+ * the start of '\n' + its sequence line, masked bases as 'N', in the flattened stream; an empty read is a record of no bases --
+ * and kpal_fasta_records_index / _count / _count_device and kpal_fasta_windows_layout / _count / _count_device serve whichever
+ * format indexed the context last.  Window coordinates count masked bases: a masked base is a base that breaks k-mers.
+ * FASTQ text, indexed by read.  The text may be cut anywhere.
+ * *consumed = bytes of host_text that the indexed records cover;
+ *   the caller carries the rest into its next call.
+ * final != 0: the text ends here.
+ *   consumed = nbytes, trailing empty lines are no record,
+ *   a record cut off is malformed.
+ * records_before: records of the same text indexed by earlier calls
+ *   (used only to number a malformed record, 1-based over the whole text).
+ * Malformed text is KPAL_E_INVALID, "malformed FASTQ record N: ..." with N = records_before + 1 + the record's index in the
+ * text; after any error the context holds no index.  A text of 4 GiB is refused.  Independent of the begin / feed / finish
+ * state: the open FASTQ text of a count is neither read nor disturbed. */
+int kpal_fastq_records_begin(kpal_ctx *ctx, const uint8_t *host_text, size_t nbytes, const kpal_fastq_options *opt,
+                             int final, uint64_t records_before, uint64_t *n_records, uint64_t *flat_bytes, uint64_t *consumed);
+/* ... over a FILE: the scan that kpal_fasta_records_file_next / _tell / _close then serve is one of FASTQ reads.  Every _next
+ * indexes the next piece of whole reads -- the carried rest + a staging buffer's worth of the file (64 MiB, KPAL_FASTA_CHUNK),
+ * cut behind the last read it finishes; a piece that finishes none gathers further -- _tell is the file offset of the carried
+ * read's title line, and the piece that reaches `end` ends the text. */
+int kpal_fastq_records_file_open(kpal_ctx *ctx, const char *path, uint64_t begin, uint64_t end,
+                                 const kpal_fastq_options *opt, uint64_t records_before);
 /* One profile per sliding window of each record (beyond the reference), over the records indexed by the last
  * kpal_fasta_records_begin / kpal_fasta_records_file_next.  Coordinates are bases of the flattened record; for a record of L
  * bases window j covers bases [j * step, min(j * step + window, L)): none for L = 0, one for L <= window, else
@@ -184,7 +209,8 @@ int kpal_fasta_records_file_close(kpal_ctx *ctx);
  * Accepted: 1 <= step <= window, window % step == 0, k <= window; anything else is KPAL_E_INVALID.
  * kpal_fasta_windows_layout: *n_windows of the piece and, unless NULL, first_window[r] = number of record r's first window
  * (n_records + 1 values, the last = *n_windows).  kpal_fasta_windows_count counts windows [first, first + n) into host_out,
- * n tables of 4^k int64; the range may begin and end inside a record.  The cost per base does not grow with window / step. */
+ * n tables of 4^k int64; the range may begin and end inside a record.  The cost per base does not grow with window / step.
+ * The records are those of the last index, FASTA records or FASTQ reads (kpal_fastq_records_begin). */
 int kpal_fasta_windows_layout(kpal_ctx *ctx, uint64_t window, uint64_t step, uint64_t *n_windows, uint64_t *first_window);
 int kpal_fasta_windows_count(kpal_ctx *ctx, int k, uint64_t window, uint64_t step, uint64_t first, uint64_t n, int64_t *host_out);
 int kpal_fasta_windows_count_device(kpal_ctx *ctx, int k, uint64_t window, uint64_t step, uint64_t first, uint64_t n, int64_t *dev_out);   /* the same into the caller's device memory (kpal_dev_alloc) */

@@ -88,6 +88,9 @@ SIGNATURES = {
     'kpal_fasta_records_file_next': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
     'kpal_fasta_records_file_tell': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
     'kpal_fasta_records_file_close': (ctypes.c_int, [_vp]),
+    'kpal_fastq_records_begin': (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.POINTER(FastqOptions), ctypes.c_int, ctypes.c_uint64,
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    'kpal_fastq_records_file_open': (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(FastqOptions), ctypes.c_uint64]),
     'kpal_fasta_records_count': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp]),
     'kpal_fasta_windows_layout': (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), _vp]),
     'kpal_fasta_windows_count': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp]),
@@ -490,6 +493,27 @@ class Context(object):
         self._records_scan = getattr(self, '_records_scan', 0) + 1      # (a scan interleaved with another one would read the other's index)
         return n.value, nf.value
 
+    def fastq_records_begin(self, text, min_quality=None, quality_offset=33, final=True, records_before=0):
+        """Tokenise FASTQ text, cut anywhere, on the device and index its reads -> (n_records, flattened bytes, consumed): the
+        bytes of ``text`` the indexed reads cover -- the caller carries the rest into its next call; ``final``: the text ends
+        here (consumed = all of it, a read cut off is malformed).  ``records_before`` numbers a malformed read (ValueError)
+        over the whole text.  The index stays in the context, where the ``fasta_records_*`` / ``fasta_windows_*`` calls read it."""
+        a = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
+        opt = _fastq_options(min_quality, quality_offset)
+        n, nf, used = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._records = 0                                               # (a call that fails leaves no index)
+        self._records_scan = getattr(self, '_records_scan', 0) + 1
+        _check(self._L.kpal_fastq_records_begin(self._h, a.ctypes.data if a.size else None, a.size, ctypes.byref(opt), 1 if final else 0,
+                                                int(records_before), ctypes.byref(n), ctypes.byref(nf), ctypes.byref(used)))
+        self._records = n.value
+        return n.value, nf.value, used.value
+
+    def fastq_records_file_open(self, path, begin=0, end=0, min_quality=None, quality_offset=33, records_before=0):
+        """Start a by-read scan of bytes [begin, end) of a FASTQ file the library reads itself (end = 0: to its end; ``begin`` is
+        the start of a title line): ``fasta_records_file_next`` / ``_tell`` / ``_close`` serve it."""
+        opt = _fastq_options(min_quality, quality_offset)
+        _check(self._L.kpal_fastq_records_file_open(self._h, os.fsencode(path), int(begin), int(end), ctypes.byref(opt), int(records_before)))
+
     def fasta_records_file_open(self, path, begin=0, end=0):
         """Start a by-record scan of bytes [begin, end) of a FASTA file the library reads itself (end = 0: to its end)."""
         _check(self._L.kpal_fasta_records_file_open(self._h, os.fsencode(path), int(begin), int(end)))
@@ -497,9 +521,10 @@ class Context(object):
     def fasta_records_file_next(self):
         """Index the next piece of whole records -> (n_records, flattened bytes, file offset of the piece), or None at the end."""
         n, nf, off, done = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
+        self._records = 0                                               # (a call that fails leaves no index: a malformed FASTQ piece)
+        self._records_scan = getattr(self, '_records_scan', 0) + 1
         _check(self._L.kpal_fasta_records_file_next(self._h, ctypes.byref(n), ctypes.byref(nf), ctypes.byref(off), ctypes.byref(done)))
         self._records = n.value
-        self._records_scan = getattr(self, '_records_scan', 0) + 1
         return None if done.value else (n.value, nf.value, off.value)
 
     def fasta_records_file_tell(self):

@@ -121,6 +121,23 @@ __global__ void fq_carry_kernel(const uint32_t *__restrict__ pos, const uint64_t
     if (status[1] < R) status[0] = min(status[0], (status[1] << 3) | kFqNoAt);
 }
 
+// ---- record index (Profile.from_fastq_by_record / _by_window: one profile per read, per window of a read) ----
+// Title offsets: for each of the R records the chunk finishes, the byte of the chunk its title line begins at -- the start of
+// line 4r, the counterpart of the FASTA index's header offsets (the host reads the read's name there and nowhere else).  One
+// thread per record; pos[4r - 1] exists for every r < R (record R - 1 is not blank, so line 4R - 4 begins inside the chunk).
+//
+// The other half of the index, the records' starts in the flattened stream, is NOT derived from these line bounds: the host
+// compacts the '\n' bytes of the stream itself (fa_mark_count_kernel<0> / fa_offset_kernel / fa_mark_scatter_kernel<0>, as the
+// FASTA index does).  fq_scatter_kernel writes exactly one '\n' per record it keeps and none inside a sequence line, so the r-th
+// '\n' IS where record r starts, whatever the scatter decided about a '\r' at a line's end -- a scan of line lengths would have to
+// restate that rule and could disagree with it -- and the number of '\n' bytes checks the record count of the status words
+// against what was really written.  It costs one more read of the stream, at most half the text, in HBM.
+__global__ __launch_bounds__(256) void fq_title_offsets_kernel(const uint32_t *__restrict__ pos, uint64_t R, uint64_t *__restrict__ title)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < R) title[r] = r == 0 ? 0 : (uint64_t)pos[4 * r - 1] + 1;
+}
+
 // Exclusive sum of one value per thread over the 256-thread workgroup (plus `seed`).
 __device__ __forceinline__ uint64_t fq_block_exclusive_sum(uint32_t v, uint64_t seed, uint32_t *sh /* [4] */)
 {

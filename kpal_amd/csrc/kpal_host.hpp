@@ -151,7 +151,7 @@ struct kpal_ctx {
     // FASTA ingest (kpal_text.hip): raw text and flattened stream of two chunks in flight, scan metadata, the flattened tail of
     // the previous chunk (the k-1 bytes the next one's first windows begin in), the chunks' flattened sizes in pinned host memory
     DevBuf fa_raw[2], fa_flat[2], fa_meta[2], fa_tail;
-    // record index of the text of the last kpal_fasta_records_begin (from_fasta_by_record): raw text, flattened stream, scan metadata,
+    // record index of the text of the last kpal_fasta_records_begin / kpal_fastq_records_begin (from_fasta_by_record, from_fastq_by_record): raw text, flattened stream, scan metadata,
     // record starts in the flattened stream (R + 1) and header offsets in the raw text (R) on the device and on the host
     DevBuf rec_raw, rec_flat, rec_meta, rec_starts, rec_hdr;
     std::vector<uint64_t> rec_starts_host, rec_hdr_host;
@@ -160,6 +160,10 @@ struct kpal_ctx {
     int rec_fd = -1;
     uint64_t rec_pos = 0, rec_end = 0, rec_piece_at = 0;
     std::vector<uint8_t> rec_carry;
+    // ... the scan is one of FASTQ reads (kpal_fastq_records_file_open): its mask and the records its pieces have indexed so far
+    bool rec_fastq = false;
+    int rec_fq_min_quality = -1, rec_fq_offset = 33;
+    uint64_t rec_fq_records = 0;
     // ... cut into sliding windows (kpal_fasta_windows_*): first window and first tile of every record (R + 1 values each; on
     // the device one behind the other) for the (window, step) last asked for -- a new record index clears them -- and the
     // tile tables of the call in flight
@@ -353,6 +357,12 @@ void staged_memcpy(void *dst, const void *src, size_t n);                 // kpa
 int fa_flatten(kpal_ctx *ctx, const uint8_t *raw, uint64_t m, int state, int tail, uint8_t *flat, void *meta, uint64_t **offs_out,
                void **rest = nullptr);                                    // kpal_text.hip: the FASTA flattening of raw[0, m) into flat
 int open_text_range(const char *path, uint64_t begin, uint64_t end, FaSource &src);   // kpal_text.hip: a byte range of a regular file, opened for sequential reading
+// kpal_text.hip: the FASTQ tokeniser (fastq_kernels.hpp is compiled there alone), for the count path and the record index
+int fq_mask_options(const kpal_fastq_options *opt, int *min_quality, int *offset);   // the mask of a FASTQ call, checked (min_quality -1: none)
+int fq_tokenise(kpal_ctx *ctx, const uint8_t *raw, uint64_t n, bool fin, int min_quality, int offset, uint8_t *flat);   // one FASTQ chunk on the device -> flat stream, newline positions (fq_pos), status words
+int fq_tokenise_wait(kpal_ctx *ctx, uint64_t records, const unsigned long long **status);   // the status words of that chunk on the host; a malformed record is the error
+int fq_title_offsets(kpal_ctx *ctx, uint64_t R, uint64_t *dev_title);    // where the title lines of the R records that chunk finishes begin (device, queued)
+int fq_chunk_too_long(uint64_t records);                                  // kpal_text.hip: the error of a FASTQ chunk of 4 GiB
 void fq_reset(kpal_ctx *ctx);                                             // kpal_text.hip: the unfinished FASTQ record of a count is dropped
 int count_end_text(kpal_ctx *ctx);                                        // kpal_text.hip: an open FASTQ text is ended (its carried record counted, or the count abandoned)
 int table_ready(kpal_ctx *ctx);                                           // kpal_quads2.hip: zeros materialised, pending finalisation done: the table is the table

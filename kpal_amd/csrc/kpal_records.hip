@@ -1,5 +1,6 @@
-// kpal_records.hip -- one profile per record or per sliding window of a FASTA text: kpal_count_records, the record index over
-// memory and over a file the library reads itself (kpal_fasta_records_*), the sliding windows (kpal_fasta_windows_*).
+// kpal_records.hip -- one profile per record or per sliding window of a FASTA text, per read or per window of a read of a FASTQ
+// text: kpal_count_records, the record index over memory and over a file the library reads itself (kpal_fasta_records_*,
+// kpal_fastq_records_*: one index, filled by either format), the sliding windows (kpal_fasta_windows_*).
 #include "kpal_host.hpp"
 
 #include "count_kernels.hpp"
@@ -53,26 +54,10 @@ KPAL_API int kpal_count_records(kpal_ctx *ctx, int k, const uint8_t *host_flat, 
 // kpal_fasta_records_count then counts batches of records into one table each (count_records_kernel), as many as the caller has
 // room for.
 // ----------------------------------------------------------------------------------------------
-// in_pinned0: host_text lies in ctx->pinned[0] (the file reader put it there): the DMA engine reads it in place
-static int fasta_records_index_text(kpal_ctx *ctx, const uint8_t *host_text, size_t nbytes, bool in_pinned0, uint64_t *n_records, uint64_t *flat_bytes)
+// text[0, m) -> raw on the device through the pinned staging buffers (host threads copy piece i + 1 while the DMA takes piece i)
+// in_pinned0: the text lies in ctx->pinned[0] (the file reader put it there): the DMA engine reads it in place
+static int records_upload(kpal_ctx *ctx, uint8_t *raw, const uint8_t *text, size_t m, bool in_pinned0)
 {
-    *n_records = *flat_bytes = 0;
-    ctx->rec_n = ctx->rec_nf = 0;
-    ctx->win_window = ctx->win_step = 0;
-    ctx->rec_starts_host.clear();
-    ctx->rec_hdr_host.clear();
-    const size_t first = nbytes ? fasta_first_header(host_text, nbytes, true) : 0;   // text before the first header is no record (klib.py:131: SeqIO)
-    if (first >= nbytes) return KPAL_OK;
-    const uint8_t *text = host_text + first;
-    const size_t m = nbytes - first;
-    const size_t pad = kpal_ctx::kStagePad;
-    const uint32_t nblocks = (uint32_t)((m + kFaBlockBytes - 1) / kFaBlockBytes);
-    CHK(ensure(ctx, ctx->rec_raw, m + 64));
-    CHK(ensure(ctx, ctx->rec_flat, m + pad + 64));
-    CHK(ensure(ctx, ctx->rec_meta, (size_t)nblocks * (8 + 8 + 4 + 4) + 2 * (size_t)(nblocks + 1) * 8 + 128));
-    uint8_t *raw = (uint8_t *)ctx->rec_raw.p;
-    uint8_t *flat = (uint8_t *)ctx->rec_flat.p + pad;
-    // text -> device through the pinned staging buffers (host threads copy piece i + 1 while the DMA takes piece i)
     CHK(ensure_pinned(ctx));
     if (in_pinned0) {
         CHK(pinned_wait(ctx, 0));   // (an earlier DMA out of the buffer: long done, the caller has refilled it)
@@ -87,6 +72,35 @@ static int fasta_records_index_text(kpal_ctx *ctx, const uint8_t *host_text, siz
             CHK(pinned_h2d(ctx, slot, raw + off, ctx->pinned[slot], len));
         }
     }
+    return KPAL_OK;
+}
+
+// the context holds no index
+static void records_index_clear(kpal_ctx *ctx)
+{
+    ctx->rec_n = ctx->rec_nf = 0;
+    ctx->win_window = ctx->win_step = 0;
+    ctx->rec_starts_host.clear();
+    ctx->rec_hdr_host.clear();
+}
+
+// in_pinned0: host_text lies in ctx->pinned[0] (records_upload)
+static int fasta_records_index_text(kpal_ctx *ctx, const uint8_t *host_text, size_t nbytes, bool in_pinned0, uint64_t *n_records, uint64_t *flat_bytes)
+{
+    *n_records = *flat_bytes = 0;
+    records_index_clear(ctx);
+    const size_t first = nbytes ? fasta_first_header(host_text, nbytes, true) : 0;   // text before the first header is no record (klib.py:131: SeqIO)
+    if (first >= nbytes) return KPAL_OK;
+    const uint8_t *text = host_text + first;
+    const size_t m = nbytes - first;
+    const size_t pad = kpal_ctx::kStagePad;
+    const uint32_t nblocks = (uint32_t)((m + kFaBlockBytes - 1) / kFaBlockBytes);
+    CHK(ensure(ctx, ctx->rec_raw, m + 64));
+    CHK(ensure(ctx, ctx->rec_flat, m + pad + 64));
+    CHK(ensure(ctx, ctx->rec_meta, (size_t)nblocks * (8 + 8 + 4 + 4) + 2 * (size_t)(nblocks + 1) * 8 + 128));
+    uint8_t *raw = (uint8_t *)ctx->rec_raw.p;
+    uint8_t *flat = (uint8_t *)ctx->rec_flat.p + pad;
+    CHK(records_upload(ctx, raw, text, m, in_pinned0));
     // the flattening; behind its scratch the header lines' offsets (offs2) and the marks of both compactions
     uint64_t *offs, *offs2;
     CHK(fa_flatten(ctx, raw, m, 0, 1, flat, ctx->rec_meta.p, &offs, (void **)&offs2));
@@ -135,6 +149,81 @@ KPAL_API int kpal_fasta_records_begin(kpal_ctx *ctx, const uint8_t *host_text, s
     return fasta_records_index_text(ctx, host_text, nbytes, false, n_records, flat_bytes);
 }
 
+// ----------------------------------------------------------------------------------------------
+// Profile.from_fastq_by_record / _by_window: the same index over FASTQ text.  The piece -- it begins at a title line; it may end
+// anywhere unless `fin` -- is tokenised by the count path's own function (fq_tokenise: validation, mask, flattening), which
+// leaves the newline positions and the status words behind: the records the piece finishes (R), the byte where the unfinished
+// rest begins (*consumed), the flattened size.  Title offsets come from the newline positions (fq_title_offsets_kernel), flat
+// starts from the '\n' bytes of the stream (fastq_kernels.hpp says why).  Everything that counts reads the index only.
+// ----------------------------------------------------------------------------------------------
+static int fastq_records_index_text(kpal_ctx *ctx, const uint8_t *host_text, size_t nbytes, bool in_pinned0, int min_quality, int offset, bool fin,
+                                    uint64_t records_before, uint64_t *n_records, uint64_t *flat_bytes, uint64_t *consumed)
+{
+    *n_records = *flat_bytes = *consumed = 0;
+    records_index_clear(ctx);
+    if (nbytes == 0) return KPAL_OK;
+    const uint64_t n = nbytes;
+    if (n >= ((uint64_t)1 << 32) - 64) return fq_chunk_too_long(records_before);
+    const size_t pad = kpal_ctx::kStagePad;
+    const uint32_t nblocks = (uint32_t)((n + kFaBlockBytes - 1) / kFaBlockBytes);
+    CHK(ensure(ctx, ctx->rec_raw, n + 64));
+    CHK(ensure(ctx, ctx->rec_flat, n + pad + 64));
+    CHK(ensure(ctx, ctx->rec_meta, (size_t)(nblocks + 1) * 8 + (size_t)nblocks * 4 + 64));
+    uint8_t *raw = (uint8_t *)ctx->rec_raw.p;
+    uint8_t *flat = (uint8_t *)ctx->rec_flat.p + pad;
+    uint64_t *offs = (uint64_t *)ctx->rec_meta.p;
+    uint32_t *marks = (uint32_t *)(offs + nblocks + 1);
+    CHK(records_upload(ctx, raw, host_text, n, in_pinned0));
+    CHK(fq_tokenise(ctx, raw, n, fin, min_quality, offset, flat));
+    const unsigned long long *hs;
+    CHK(fq_tokenise_wait(ctx, records_before, &hs));
+    const uint64_t R = hs[2], nf = hs[4], used = fin ? n : hs[3];
+    if (used > n || nf > n || nf < R)
+        return set_err(KPAL_E_HIP, "FASTQ record index: %llu records, %llu flattened bytes, rest at %llu of %llu bytes", (unsigned long long)R,
+                       (unsigned long long)nf, (unsigned long long)used, (unsigned long long)n);
+    *consumed = used;
+    if (R == 0) return KPAL_OK;
+    CHK(ensure(ctx, ctx->rec_hdr, (size_t)R * 8));
+    CHK(ensure(ctx, ctx->rec_starts, (size_t)(R + 1) * 8));
+    CHK(fq_title_offsets(ctx, R, (uint64_t *)ctx->rec_hdr.p));
+    // record starts of the flattened stream: its '\n' bytes, counted before they are listed -- the list has room for R
+    const uint32_t fblocks = (uint32_t)((nf + kFaBlockBytes - 1) / kFaBlockBytes);   // <= nblocks
+    LAUNCH(ctx, "fa_mark_count", (fa_mark_count_kernel<0>), dim3(fblocks), dim3(kFaThreads), (const uint8_t *)flat, nf, marks);
+    LAUNCH(ctx, "fa_offset", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)marks, fblocks, offs);
+    uint64_t seps = 0;
+    HIPCHK(hipMemcpyAsync(&seps, offs + fblocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (seps != R)
+        return set_err(KPAL_E_HIP, "FASTQ record index: the tokeniser reports %llu records but the stream holds %llu record starts",
+                       (unsigned long long)R, (unsigned long long)seps);
+    LAUNCH(ctx, "fa_mark_scatter", (fa_mark_scatter_kernel<0>), dim3(fblocks), dim3(kFaThreads), (const uint8_t *)flat, nf, (const uint64_t *)offs,
+           (uint64_t *)ctx->rec_starts.p);
+    HIPCHK(hipMemcpyAsync((uint64_t *)ctx->rec_starts.p + R, &nf, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    ctx->rec_hdr_host.resize((size_t)R);
+    ctx->rec_starts_host.resize((size_t)R + 1);
+    HIPCHK(hipMemcpyAsync(ctx->rec_hdr_host.data(), ctx->rec_hdr.p, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->rec_starts_host.data(), ctx->rec_starts.p, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->rec_starts_host[(size_t)R] = nf;
+    ctx->rec_n = R;
+    ctx->rec_nf = nf;
+    *n_records = R;
+    *flat_bytes = nf;
+    return KPAL_OK;
+}
+
+KPAL_API int kpal_fastq_records_begin(kpal_ctx *ctx, const uint8_t *host_text, size_t nbytes, const kpal_fastq_options *opt, int final,
+                                      uint64_t records_before, uint64_t *n_records, uint64_t *flat_bytes, uint64_t *consumed)
+{
+    CTX_ENTER(ctx);
+    if (!n_records || !flat_bytes || !consumed || (nbytes && !host_text)) return set_err(KPAL_E_INVALID, "NULL pointer");
+    *n_records = *flat_bytes = *consumed = 0;
+    records_index_clear(ctx);
+    int min_quality, offset;
+    CHK(fq_mask_options(opt, &min_quality, &offset));
+    return fastq_records_index_text(ctx, host_text, nbytes, false, min_quality, offset, final != 0, records_before, n_records, flat_bytes, consumed);
+}
+
 // ---- the same over a FILE the library reads itself (fa_read: the pool's threads pread into the pinned staging buffer; no byte of the text
 // passes through Python): every kpal_fasta_records_file_next indexes the next piece of WHOLE records -- up to the end of line
 // before the last header line of what fits the 64 MiB staging buffer; the unfinished record behind it is carried to the next
@@ -146,6 +235,8 @@ static void fasta_records_file_reset(kpal_ctx *ctx)
     ctx->rec_pos = ctx->rec_end = ctx->rec_piece_at = 0;
     ctx->rec_carry.clear();
     ctx->rec_carry.shrink_to_fit();
+    ctx->rec_fastq = false;
+    ctx->rec_fq_records = 0;
 }
 
 KPAL_API int kpal_fasta_records_file_open(kpal_ctx *ctx, const char *path, uint64_t begin, uint64_t end)
@@ -158,6 +249,27 @@ KPAL_API int kpal_fasta_records_file_open(kpal_ctx *ctx, const char *path, uint6
     ctx->rec_fd = src.fd;
     ctx->rec_pos = ctx->rec_piece_at = src.pos;
     ctx->rec_end = src.end;
+    return KPAL_OK;
+}
+
+// ... of FASTQ reads: kpal_fasta_records_file_next / _tell / _close serve the scan, piece by piece of whole reads
+KPAL_API int kpal_fastq_records_file_open(kpal_ctx *ctx, const char *path, uint64_t begin, uint64_t end, const kpal_fastq_options *opt,
+                                          uint64_t records_before)
+{
+    CTX_ENTER(ctx);
+    if (!path) return set_err(KPAL_E_INVALID, "path is NULL");
+    int min_quality, offset;
+    CHK(fq_mask_options(opt, &min_quality, &offset));
+    fasta_records_file_reset(ctx);
+    FaSource src;
+    CHK(open_text_range(path, begin, end, src));
+    ctx->rec_fd = src.fd;
+    ctx->rec_pos = ctx->rec_piece_at = src.pos;
+    ctx->rec_end = src.end;
+    ctx->rec_fastq = true;
+    ctx->rec_fq_min_quality = min_quality;
+    ctx->rec_fq_offset = offset;
+    ctx->rec_fq_records = records_before;
     return KPAL_OK;
 }
 
@@ -176,6 +288,73 @@ static size_t fasta_last_boundary(const uint8_t *buf, size_t n, size_t from)
     return n;
 }
 
+// The next piece of a FASTQ scan.  Unlike a FASTA piece it cannot be cut on the host (a quality line may begin with '@'): the
+// carried rest + the next staging buffer's worth of the file are tokenised as they are, and the tokeniser says where the
+// records it finishes end; the rest is carried.  A text that finishes no record is gathered further -- without a device call
+// while it has fewer than the four line ends a record needs.
+// whether buf[0, n) holds the four line ends a FASTQ record needs
+static bool fastq_four_line_ends(const uint8_t *buf, size_t n)
+{
+    const uint8_t *p = buf, *const end = buf + n;
+    for (int i = 0; i < 4; ++i) {
+        p = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
+        if (!p) return false;
+        ++p;
+    }
+    return true;
+}
+
+static int fastq_records_file_next(kpal_ctx *ctx, uint64_t *n_records, uint64_t *flat_bytes, uint64_t *text_offset, int *done)
+{
+    const size_t stage = std::min<size_t>(kpal_ctx::kStage, ctx->fa_chunk);
+    FaSource src;
+    src.fd = ctx->rec_fd;
+    for (;;) {
+        *n_records = *flat_bytes = *text_offset = 0;
+        *done = 1;
+        if (ctx->rec_carry.empty() && ctx->rec_pos >= ctx->rec_end) {   // the end
+            fasta_records_file_reset(ctx);
+            return KPAL_OK;
+        }
+        const size_t c = ctx->rec_carry.size();
+        const bool fits = c < stage;
+        const size_t want = (size_t)std::min<uint64_t>(fits ? stage - c : stage, ctx->rec_end - ctx->rec_pos);
+        uint8_t *buf;
+        if (fits) {   // the carried rest + the next bytes of the file into the pinned buffer
+            CHK(pinned_wait(ctx, 0));
+            buf = (uint8_t *)ctx->pinned[0];
+            if (c) memcpy(buf, ctx->rec_carry.data(), c);
+        } else {      // a read longer than the staging buffer: gathered in pageable memory
+            ctx->rec_carry.resize(c + want);
+            buf = ctx->rec_carry.data();
+        }
+        if (want) {
+            if (int e = fa_read(src, buf + c, ctx->rec_pos, want)) return set_err(KPAL_E_IO, "reading the FASTQ input failed: %s", strerror(e));
+            ctx->rec_pos += want;
+        }
+        const size_t n = c + want;
+        const bool at_end = ctx->rec_pos >= ctx->rec_end;
+        uint64_t used = 0;
+        if (at_end || fastq_four_line_ends(buf, n)) {
+            const uint64_t at = ctx->rec_piece_at;
+            CHK(fastq_records_index_text(ctx, buf, n, fits, ctx->rec_fq_min_quality, ctx->rec_fq_offset, at_end, ctx->rec_fq_records, n_records, flat_bytes, &used));
+            *text_offset = at;
+        }
+        if (used == 0 && !at_end) {   // no read ends in this text: keep gathering
+            if (fits) ctx->rec_carry.assign(buf, buf + n);
+            continue;
+        }
+        // the unfinished read behind the piece is carried (the DMA out of the pinned buffer has been waited for: the index is complete)
+        std::vector<uint8_t> tail(buf + used, buf + n);
+        ctx->rec_carry.swap(tail);
+        ctx->rec_piece_at += used;
+        ctx->rec_fq_records += *n_records;
+        *done = 0;
+        if (*n_records == 0) continue;   // (empty lines at the end of the file only)
+        return KPAL_OK;
+    }
+}
+
 KPAL_API int kpal_fasta_records_file_next(kpal_ctx *ctx, uint64_t *n_records, uint64_t *flat_bytes, uint64_t *text_offset, int *done)
 {
     CTX_ENTER(ctx);
@@ -184,6 +363,7 @@ KPAL_API int kpal_fasta_records_file_next(kpal_ctx *ctx, uint64_t *n_records, ui
     *done = 1;
     if (ctx->rec_fd < 0) return set_err(KPAL_E_STATE, "kpal_fasta_records_file_next without kpal_fasta_records_file_open");
     CHK(ensure_pinned(ctx));
+    if (ctx->rec_fastq) return fastq_records_file_next(ctx, n_records, flat_bytes, text_offset, done);
     const size_t stage = std::min<size_t>(kpal_ctx::kStage, ctx->fa_chunk);   // (KPAL_FASTA_CHUNK: tests put the seams everywhere)
     FaSource src;
     src.fd = ctx->rec_fd;

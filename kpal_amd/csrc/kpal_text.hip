@@ -206,14 +206,22 @@ static int fq_options(const kpal_fastq_options *opt, FqMask &m)
     return KPAL_OK;
 }
 
-// The text = carry_in, then the source.  final_text: the text ends with the source (a record still open there is cut off); else
-// the unfinished rest goes to *carry_out (which may be carry_in).  records: records finished before, advanced.  count: the stream
-// is counted into the running count; else it is copied to host_out (*n_out bytes).
-static int fastq_pipeline(kpal_ctx *ctx, FaSource &src, const std::vector<uint8_t> &carry_in, bool final_text, FqMask m,
-                          uint64_t &records, bool count, uint8_t *host_out, uint64_t *n_out, std::vector<uint8_t> *carry_out)
+int fq_mask_options(const kpal_fastq_options *opt, int *min_quality, int *offset)
 {
-    const size_t stage = ctx->fa_chunk, pad = kpal_ctx::kStagePad;
-    CHK(ensure_pinned(ctx));
+    FqMask m;
+    CHK(fq_options(opt, m));
+    *min_quality = m.min_quality;
+    *offset = m.offset;
+    return KPAL_OK;
+}
+
+// The tokenising of ONE chunk, shared by the count path (fastq_pipeline) and the record index (kpal_records.hip): raw[0, n) on
+// the device, beginning at a title line, n < 4 GiB - 64 -> flat; fin: the text ends with the chunk.  Queued on the context's
+// stream: the newline positions stay in fq_pos, the status words go to fq_status and from there to fq_status_host, and fq_ev is
+// recorded behind that copy -- the caller waits for it (fq_tokenise_wait) when it needs the words.
+int fq_tokenise(kpal_ctx *ctx, const uint8_t *raw, uint64_t n, bool fin, int min_quality, int offset, uint8_t *flat)
+{
+    const FqMask m = {min_quality, offset};
     if (!ctx->fq_status_host) {
         hipError_t e = hipHostMalloc((void **)&ctx->fq_status_host, kFqStatusWords * sizeof(unsigned long long), hipHostMallocDefault);
         if (e != hipSuccess) {
@@ -223,6 +231,67 @@ static int fastq_pipeline(kpal_ctx *ctx, FaSource &src, const std::vector<uint8_
     }
     if (!ctx->fq_ev) HIPCHK(hipEventCreateWithFlags(&ctx->fq_ev, hipEventDisableTiming));
     CHK(ensure(ctx, ctx->fq_status, kFqStatusWords * sizeof(unsigned long long)));
+    const uint32_t nb = (uint32_t)((n + kFaBlockBytes - 1) / kFaBlockBytes);
+    CHK(ensure(ctx, ctx->fq_pos, n * sizeof(uint32_t) + 64));
+    CHK(ensure(ctx, ctx->fq_meta, (size_t)(nb + 1) * 16 + (size_t)nb * 8 + 64));
+    uint64_t *line_offs = (uint64_t *)ctx->fq_meta.p;
+    uint64_t *kept_offs = line_offs + nb + 1;
+    uint32_t *nl_cnt = (uint32_t *)(kept_offs + nb + 1);
+    uint32_t *kept = nl_cnt + nb;
+    uint32_t *pos = (uint32_t *)ctx->fq_pos.p;
+    unsigned long long *st = (unsigned long long *)ctx->fq_status.p;
+    HIPCHK(hipMemsetAsync(st, 0xFF, 2 * sizeof(unsigned long long), ctx->stream));
+    HIPCHK(hipMemsetAsync(st + 2, 0, (kFqStatusWords - 2) * sizeof(unsigned long long), ctx->stream));
+    const unsigned rec_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n / 4 / 256 + 1, (uint64_t)ctx->num_cu * 4));
+    LAUNCH(ctx, "fq_newlines", (fa_mark_count_kernel<0>), dim3(nb), dim3(kFaThreads), raw, n, nl_cnt);
+    LAUNCH(ctx, "fq_line_scan", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)nl_cnt, nb, line_offs);
+    LAUNCH(ctx, "fq_newline_pos", fq_newline_pos_kernel, dim3(nb), dim3(kFaThreads), raw, n, (const uint64_t *)line_offs, pos);
+    LAUNCH(ctx, "fq_records", fq_record_kernel, dim3(rec_grid), dim3(256), raw, n, (const uint32_t *)pos, (const uint64_t *)(line_offs + nb),
+           fin ? 1 : 0, st);
+    LAUNCH(ctx, "fq_carry", fq_carry_kernel, dim3(1), dim3(1), (const uint32_t *)pos, (const uint64_t *)(line_offs + nb), n, st);
+    LAUNCH(ctx, "fq_count", fq_count_kernel, dim3(nb), dim3(kFaThreads), raw, n, (const uint64_t *)line_offs, nb, (const uint32_t *)pos, m, st, kept);
+    LAUNCH(ctx, "fq_offset", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)kept, nb, kept_offs);
+    LAUNCH(ctx, "fq_scatter", fq_scatter_kernel, dim3(nb), dim3(kFaThreads), raw, n, (const uint64_t *)line_offs, nb, (const uint32_t *)pos, m, st,
+           (const uint64_t *)kept_offs, flat);
+    HIPCHK(hipMemcpyAsync(ctx->fq_status_host, st, kFqStatusWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipEventRecord(ctx->fq_ev, ctx->stream));
+    return KPAL_OK;
+}
+
+// ... and its status words, once they have arrived (fastq_kernels.hpp: kFqStatusWords); a malformed record is the error, numbered
+// behind the `records` records of the same text that earlier chunks finished
+int fq_tokenise_wait(kpal_ctx *ctx, uint64_t records, const unsigned long long **status)
+{
+    HIPCHK(hipEventSynchronize(ctx->fq_ev));
+    const unsigned long long *hs = ctx->fq_status_host;
+    if (hs[0] != ~0ull)
+        return set_err(KPAL_E_INVALID, "malformed FASTQ record %llu: %s", (unsigned long long)(records + (hs[0] >> 3) + 1),
+                       fq_error_text((unsigned)(hs[0] & 7)));
+    *status = hs;
+    return KPAL_OK;
+}
+
+// The title lines of the R records the chunk tokenised last finishes (its newline positions are still in fq_pos): their offsets
+// in the chunk, R values of device memory, queued on the context's stream.
+int fq_title_offsets(kpal_ctx *ctx, uint64_t R, uint64_t *dev_title)
+{
+    LAUNCH(ctx, "fq_title_offsets", fq_title_offsets_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), (const uint32_t *)ctx->fq_pos.p, R, dev_title);
+    return KPAL_OK;
+}
+
+int fq_chunk_too_long(uint64_t records)
+{
+    return set_err(KPAL_E_INVALID, "FASTQ record %llu: a record (or a run of empty lines) longer than 4 GiB", (unsigned long long)records + 1);
+}
+
+// The text = carry_in, then the source.  final_text: the text ends with the source (a record still open there is cut off); else
+// the unfinished rest goes to *carry_out (which may be carry_in).  records: records finished before, advanced.  count: the stream
+// is counted into the running count; else it is copied to host_out (*n_out bytes).
+static int fastq_pipeline(kpal_ctx *ctx, FaSource &src, const std::vector<uint8_t> &carry_in, bool final_text, FqMask m,
+                          uint64_t &records, bool count, uint8_t *host_out, uint64_t *n_out, std::vector<uint8_t> *carry_out)
+{
+    const size_t stage = ctx->fa_chunk, pad = kpal_ctx::kStagePad;
+    CHK(ensure_pinned(ctx));
 
     // the carried text: fq_raw[cslot][cstart, cstart + clen)
     int cslot = 1;
@@ -257,46 +326,16 @@ static int fastq_pipeline(kpal_ctx *ctx, FaSource &src, const std::vector<uint8_
         const size_t m_bytes = ck.n;
         const bool fin = final_text && src.pos >= src.end;
         const uint64_t n = clen + m_bytes;
-        if (n >= ((uint64_t)1 << 32) - 64)
-            return set_err(KPAL_E_INVALID, "FASTQ record %llu: a record (or a run of empty lines) longer than 4 GiB",
-                           (unsigned long long)records + 1);
-        const uint32_t nb = (uint32_t)((n + kFaBlockBytes - 1) / kFaBlockBytes);
+        if (n >= ((uint64_t)1 << 32) - 64) return fq_chunk_too_long(records);
         CHK(ensure(ctx, ctx->fq_raw[slot], n + 64));   // (never the carry's buffer: cslot != slot)
         CHK(ensure(ctx, ctx->fq_flat[slot], n + pad + 64));
-        CHK(ensure(ctx, ctx->fq_pos, n * sizeof(uint32_t) + 64));
-        CHK(ensure(ctx, ctx->fq_meta, (size_t)(nb + 1) * 16 + (size_t)nb * 8 + 64));
         uint8_t *raw = (uint8_t *)ctx->fq_raw[slot].p;
-        uint8_t *flat = (uint8_t *)ctx->fq_flat[slot].p + pad;
-        uint64_t *line_offs = (uint64_t *)ctx->fq_meta.p;
-        uint64_t *kept_offs = line_offs + nb + 1;
-        uint32_t *nl_cnt = (uint32_t *)(kept_offs + nb + 1);
-        uint32_t *kept = nl_cnt + nb;
-        uint32_t *pos = (uint32_t *)ctx->fq_pos.p;
-        unsigned long long *st = (unsigned long long *)ctx->fq_status.p;
         if (clen) HIPCHK(hipMemcpyAsync(raw, (const uint8_t *)ctx->fq_raw[cslot].p + cstart, clen, hipMemcpyDeviceToDevice, ctx->stream));
         if (m_bytes) CHK(pinned_h2d(ctx, slot, raw + clen, ck.data, m_bytes));
-        HIPCHK(hipMemsetAsync(st, 0xFF, 2 * sizeof(unsigned long long), ctx->stream));
-        HIPCHK(hipMemsetAsync(st + 2, 0, (kFqStatusWords - 2) * sizeof(unsigned long long), ctx->stream));
-        const unsigned rec_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n / 4 / 256 + 1, (uint64_t)ctx->num_cu * 4));
-        LAUNCH(ctx, "fq_newlines", (fa_mark_count_kernel<0>), dim3(nb), dim3(kFaThreads), (const uint8_t *)raw, n, nl_cnt);
-        LAUNCH(ctx, "fq_line_scan", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)nl_cnt, nb, line_offs);
-        LAUNCH(ctx, "fq_newline_pos", fq_newline_pos_kernel, dim3(nb), dim3(kFaThreads), (const uint8_t *)raw, n, (const uint64_t *)line_offs, pos);
-        LAUNCH(ctx, "fq_records", fq_record_kernel, dim3(rec_grid), dim3(256), (const uint8_t *)raw, n, (const uint32_t *)pos,
-               (const uint64_t *)(line_offs + nb), fin ? 1 : 0, st);
-        LAUNCH(ctx, "fq_carry", fq_carry_kernel, dim3(1), dim3(1), (const uint32_t *)pos, (const uint64_t *)(line_offs + nb), n, st);
-        LAUNCH(ctx, "fq_count", fq_count_kernel, dim3(nb), dim3(kFaThreads), (const uint8_t *)raw, n, (const uint64_t *)line_offs, nb,
-               (const uint32_t *)pos, m, st, kept);
-        LAUNCH(ctx, "fq_offset", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)kept, nb, kept_offs);
-        LAUNCH(ctx, "fq_scatter", fq_scatter_kernel, dim3(nb), dim3(kFaThreads), (const uint8_t *)raw, n, (const uint64_t *)line_offs, nb,
-               (const uint32_t *)pos, m, st, (const uint64_t *)kept_offs, flat);
-        HIPCHK(hipMemcpyAsync(ctx->fq_status_host, st, kFqStatusWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipEventRecord(ctx->fq_ev, ctx->stream));
+        CHK(fq_tokenise(ctx, raw, n, fin, m.min_quality, m.offset, (uint8_t *)ctx->fq_flat[slot].p + pad));
         CHK(consume());                          // the chunk before: its count runs behind this chunk's tokenising
-        HIPCHK(hipEventSynchronize(ctx->fq_ev));
-        const unsigned long long *hs = ctx->fq_status_host;
-        if (hs[0] != ~0ull)
-            return set_err(KPAL_E_INVALID, "malformed FASTQ record %llu: %s", (unsigned long long)(records + (hs[0] >> 3) + 1),
-                           fq_error_text((unsigned)(hs[0] & 7)));
+        const unsigned long long *hs;
+        CHK(fq_tokenise_wait(ctx, records, &hs));
         records += hs[2];
         cslot = slot;
         cstart = fin ? n : hs[3];

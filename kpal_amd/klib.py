@@ -176,17 +176,24 @@ def _line_end(text, start):
     return a if b < 0 else b
 
 
+def _byte_reader(handle):
+    """``(reader, encoding)``: what to ``read()`` the text of ``handle`` from -- the undecoded bytes under a text handle in an
+    ASCII-compatible encoding that has not been read from yet (a pipe, a decompressing wrapper; titles are decoded with that
+    encoding), else the handle itself."""
+    if isinstance(handle, io.TextIOWrapper):
+        try:
+            if codecs.lookup(handle.encoding or '').name in ('utf-8', 'ascii', 'iso8859-1') and handle.tell() == 0:
+                return handle.buffer, handle.encoding
+        except (LookupError, OSError, ValueError):
+            pass
+    return handle, 'ascii'
+
+
 def _whole_record_chunks(handle):
     """FASTA text of ``handle`` in pieces of about ``_FASTA_CHUNK`` bytes that hold WHOLE records: ``(bytes, str or None, encoding)`` --
     the text as bytes (what the device tokenises) and, for handles that yield ``str`` in an encoding of their own, the same
     text as the ``str`` the names are read from (one byte per character: positions agree)."""
-    reader, keep_str, encoding = handle, False, 'ascii'
-    if isinstance(handle, io.TextIOWrapper):
-        try:                              # an ASCII-compatible text encoding: its bytes, undecoded (titles are decoded with it)
-            if codecs.lookup(handle.encoding or '').name in ('utf-8', 'ascii', 'iso8859-1') and handle.tell() == 0:
-                reader, encoding = handle.buffer, handle.encoding
-        except (LookupError, OSError, ValueError):
-            reader = handle
+    (reader, encoding), keep_str = _byte_reader(handle), False
     pending = bytearray()                 # text not handed out yet: ends inside a record
     pending_str = []
     while True:
@@ -212,17 +219,79 @@ def _whole_record_chunks(handle):
         yield bytes(pending), (''.join(pending_str) if keep_str else None), encoding
 
 
-def _indexed_pieces(ctx, handle, prefix, who):
-    """The records of a FASTA handle, piece by piece of whole records, each piece tokenised and indexed ON THE DEVICE
-    (``kpal_fasta_records_begin`` / ``kpal_fasta_records_file_next``): yields ``(names, bases, indexed)`` -- the records'
+def _fasta_texts(ctx, handle):
+    """Pieces of whole records of a FASTA handle, each indexed on the device: ``(text, text_str, encoding, n_records, again)``,
+    ``again()`` indexing the same text once more."""
+    for text, text_str, encoding in _whole_record_chunks(handle):
+        def again(text=text):
+            return ctx.fasta_records_begin(text)[0]
+        yield text, text_str, encoding, again(), again
+
+
+def _four_line_ends(text):
+    """Whether ``text`` holds the four ``\\n`` a FASTQ record needs."""
+    at = -1
+    for _ in range(4):
+        at = text.find(b'\n', at + 1)
+        if at < 0:
+            return False
+    return True
+
+
+def _fastq_texts(ctx, handle, seen, min_quality, quality_offset):
+    """The same for a FASTQ handle.  What ``read()`` returns is cut anywhere, and only the tokeniser knows where a read ends
+    (a quality line may begin with ``@``): a piece is tokenised behind the rest the piece before left unfinished, the bytes of the
+    reads it finishes are kept -- ``again()`` indexes those as a text that ends there -- and the rest is carried.  ``seen[0]``,
+    the reads the caller has taken so far, numbers a malformed read over the whole handle."""
+    reader, encoding = _byte_reader(handle)
+    carry, carry_str = b'', None
+    final = False
+    while not final:
+        text = reader.read(_FASTA_CHUNK)
+        final = not text
+        text_str = None
+        if not isinstance(text, bytes):
+            text_str = text if carry_str is None else carry_str + text
+            text = text.encode('latin-1', 'replace')
+        text = carry + text
+        if not final and not _four_line_ends(text):      # (a read is four lines: nothing to index yet)
+            carry, carry_str = text, text_str
+            continue
+        if not text:
+            break
+        before = seen[0]
+        n_records, _, consumed = ctx.fastq_records_begin(text, min_quality, quality_offset, final, before)
+        kept, carry = text[:consumed], text[consumed:]
+        kept_str = None
+        if text_str is not None:
+            kept_str, carry_str = text_str[:consumed], text_str[consumed:]
+        if n_records:
+            def again(kept=kept, before=before):
+                return ctx.fastq_records_begin(kept, min_quality, quality_offset, True, before)[0]
+            yield kept, kept_str, encoding, n_records, again
+
+
+def _indexed_pieces(ctx, handle, prefix, who, fastq=None, keep_text=False):
+    """The records of a FASTA handle -- with ``fastq = (min_quality, quality_offset)``, the reads of a FASTQ handle -- piece by
+    piece of whole records, each piece tokenised and indexed ON THE DEVICE (``kpal_fasta_records_begin`` /
+    ``kpal_fastq_records_begin`` / ``kpal_fasta_records_file_next``): yields ``(names, bases, indexed)`` -- the records'
     names (``prefix`` + the first word of the title, or the 1-based index of an untitled record, kpal/klib.py:132), their
     lengths in bases, and a callable that makes sure the context still holds THIS piece's index.
 
     The reference's generators are independent of each other (zip() of two, nesting, one abandoned half-way), and the
     callers of this one yield with a piece indexed on the process-wide context.  So they call ``indexed()`` before every
-    batch: when another scan has used the context since, the piece is indexed again."""
-    index = 0                                  # records seen so far
-    plain = _plain_file(handle)
+    batch: when another scan has used the context since, the piece is indexed again.
+
+    A malformed FASTQ read raises ``ValueError`` when the scan reaches its piece: nothing of that piece has been yielded.
+    ``keep_text``: the handle is read here whatever it is, and ``indexed.text`` is the piece's text."""
+    seen = [0]                                 # records seen so far
+
+    def name_of(title):
+        words = title.split(None, 1)
+        seen[0] += 1
+        return prefix + (words[0] if words else str(seen[0]))
+
+    plain = None if keep_text else _plain_file(handle)
     if plain is not None and os.path.getsize(plain[0]) > plain[1]:
         # an ordinary file: the library reads it itself (parallel preads into pinned memory, pieces of whole records);
         # the names are read from the header lines through a read-only mapping of the file
@@ -230,8 +299,11 @@ def _indexed_pieces(ctx, handle, prefix, who):
         encoding = handle.encoding if isinstance(handle, io.TextIOWrapper) else 'ascii'
         # Nothing of the scan lives in the context across a yield: the scan is opened at `resume`, asked for ONE piece and
         # closed again; a piece that has to be indexed again is bytes [at, resume).
-        def index_piece(begin, end):
-            ctx.fasta_records_file_open(plain[0], begin, end)
+        def index_piece(begin, end, before):
+            if fastq is None:
+                ctx.fasta_records_file_open(plain[0], begin, end)
+            else:
+                ctx.fastq_records_file_open(plain[0], begin, end, fastq[0], fastq[1], before)
             try:
                 piece = ctx.fasta_records_file_next()
                 return piece, (ctx.fasta_records_file_tell() if piece is not None else end)
@@ -241,7 +313,8 @@ def _indexed_pieces(ctx, handle, prefix, who):
         with open(plain[0], 'rb') as raw, mmap.mmap(raw.fileno(), 0, access=mmap.ACCESS_READ) as text:
             resume = plain[1]
             while True:
-                piece, resume = index_piece(resume, 0)
+                before = seen[0]
+                piece, resume = index_piece(resume, 0, before)
                 if piece is None:
                     break
                 n_records, _, at = piece
@@ -249,15 +322,11 @@ def _indexed_pieces(ctx, handle, prefix, who):
                     continue
                 scan = [ctx._records_scan]
                 header_off, flat_start = ctx.fasta_records_index()
-                names = []
-                for h in (header_off + np.uint64(at)).tolist():
-                    words = text[h + 1:_line_end(text, h)].decode(encoding, 'replace').split(None, 1)
-                    index += 1
-                    names.append(prefix + (words[0] if words else str(index)))
+                names = [name_of(text[h + 1:_line_end(text, h)].decode(encoding, 'replace')) for h in (header_off + np.uint64(at)).tolist()]
 
-                def indexed(at=at, resume=resume, n_records=n_records, scan=scan):
+                def indexed(at=at, resume=resume, n_records=n_records, scan=scan, before=before):
                     if ctx._records_scan != scan[0]:
-                        again, _ = index_piece(at, resume)
+                        again, _ = index_piece(at, resume, before)
                         if again is None or again[0] != n_records:
                             raise RuntimeError('%s: bytes %d..%d of %s changed under the scan' % (who, at, resume, plain[0]))
                         scan[0] = ctx._records_scan
@@ -265,25 +334,24 @@ def _indexed_pieces(ctx, handle, prefix, who):
                 yield names, np.diff(flat_start) - np.uint64(1), indexed
         handle.seek(0, os.SEEK_END)          # the handle has been consumed, as by the reference's SeqIO.parse loop
         return
-    for text, text_str, encoding in _whole_record_chunks(handle):
-        n_records, _ = ctx.fasta_records_begin(text)
+    texts = _fasta_texts(ctx, handle) if fastq is None else _fastq_texts(ctx, handle, seen, fastq[0], fastq[1])
+    for text, text_str, encoding, n_records, again in texts:
         if n_records == 0:
             continue
         header_off, flat_start = ctx.fasta_records_index()
         names = []
         for h in header_off.tolist():
             end = _line_end(text, h)
-            title = text_str[h + 1:end] if text_str is not None else text[h + 1:end].decode(encoding, 'replace')
-            words = title.split(None, 1)
-            index += 1
-            names.append(prefix + (words[0] if words else str(index)))
+            names.append(name_of(text_str[h + 1:end] if text_str is not None else text[h + 1:end].decode(encoding, 'replace')))
         scan = [ctx._records_scan]
 
-        def indexed(text=text, scan=scan):
+        def indexed(again=again, scan=scan):
             if ctx._records_scan != scan[0]:     # another scan used the context since the last batch: this text again
-                ctx.fasta_records_begin(text)
+                again()
                 scan[0] = ctx._records_scan
 
+        if keep_text:
+            indexed.text = text
         yield names, np.diff(flat_start) - np.uint64(1), indexed
 
 
@@ -308,6 +376,24 @@ def _window_arguments(length, window, step):
     if window > 1 << 62:
         raise ValueError('the window (%d) is too long' % window)
     return length, window, step
+
+
+def _read_arguments(length, min_quality, quality_offset):
+    """``length`` as an integer; ValueError unless it is a k-mer length and the mask options are those of ``from_fastq``."""
+    length = int(length)
+    if length < 1 or length > _native.KPAL_MAX_K:
+        raise ValueError('k-mer length must be in 1..%d (got %d)' % (_native.KPAL_MAX_K, length))
+    _native.fastq_options_check(min_quality, quality_offset)
+    return length
+
+
+def _fastq_reads(ctx, handle, prefix, min_quality, quality_offset):
+    """``(name, read)`` per read of a FASTQ handle, the reads as the device tokeniser flattens them (``kpal_fastq_flatten``:
+    masked bases are ``N``) -- for a k whose tables are counted one at a time."""
+    for names, _, indexed in _indexed_pieces(ctx, handle, prefix, 'from_fastq', (min_quality, quality_offset), keep_text=True):
+        reads = ctx.fastq_flatten(indexed.text, min_quality, quality_offset).split(b'\n')[1:]
+        for pair in zip(names, reads):
+            yield pair
 
 
 def _join_block(block):
@@ -525,13 +611,7 @@ class Profile(object):
             ctx.count_feed_fastq_file(plain[0], plain[1], 0, min_quality, quality_offset)
             handle.seek(0, os.SEEK_END)
             return cls._finish_count(ctx, length, name)
-        reader = handle
-        if isinstance(handle, io.TextIOWrapper):
-            try:                              # a pipe or a decompressing wrapper in an ASCII-compatible text encoding: its bytes, undecoded
-                if codecs.lookup(handle.encoding or '').name in ('utf-8', 'ascii', 'iso8859-1') and handle.tell() == 0:
-                    reader = handle.buffer
-            except (LookupError, OSError, ValueError):
-                reader = handle
+        reader, _ = _byte_reader(handle)
         while True:
             text = reader.read(_FASTA_CHUNK)   # raw pieces cut anywhere: the library carries the unfinished record
             if not text:
@@ -590,13 +670,76 @@ class Profile(object):
         per_batch = _RECORD_BATCH_BYTES // table_bytes
         if per_batch < 2:
             for i, (record_name, seq) in enumerate(_fasta_records(handle)):
-                record_name = prefix + (record_name or str(i + 1))
-                for start in range(0, _window_count(len(seq), window, step) * step, step):
-                    end = min(start + window, len(seq))
-                    yield cls.from_sequences([seq[start:end]], length, name='%s:%d-%d' % (record_name, start + 1, end))
+                for profile in cls._windows_one_by_one(seq, prefix + (record_name or str(i + 1)), length, window, step):
+                    yield profile
             return
         ctx = _native.context()
-        for names, bases, indexed in _indexed_pieces(ctx, handle, prefix, 'from_fasta_by_window'):
+        for profile in cls._indexed_windows(ctx, handle, length, window, step, prefix, per_batch, 'from_fasta_by_window'):
+            yield profile
+
+    @classmethod
+    def from_fastq_by_record(cls, handle, length, prefix=None, min_quality=None, quality_offset=33):
+        """One profile per read of a four-line FASTQ handle (beyond the reference, which reads FASTA only), named as
+        ``from_fasta_by_record`` names records: ``prefix_`` + the first word of the title behind ``@``, or the read's 1-based
+        number over the handle when the title has no word.  An empty read gives an all-zero profile.
+
+        Reads are tokenised, validated and masked (``min_quality``, ``quality_offset``: as ``from_fastq``) by the device
+        tokeniser of ``from_fastq``, which here also indexes them (``kpal_fastq_records_begin`` / ``_file_open``); batches of
+        reads are then counted exactly as batches of FASTA records are, and their tables stay in HBM under the same budgets.
+        The handle is taken piece by piece -- an ordinary file is read by the library itself.  A malformed read raises
+        ``ValueError`` naming its 1-based number when the generator reaches its piece: the profiles of earlier pieces have
+        been yielded, none of that piece is (a piece of an ordinary file is a staging buffer's worth behind the carried rest;
+        of any other handle, what one ``read()`` returns behind it -- the rest that the last one leaves is a piece of its
+        own, which the end of the handle ends).  A k whose table alone exceeds the batch budget falls back to
+        ``from_sequences`` per read, on the reads as the device masks them."""
+        length = _read_arguments(length, min_quality, quality_offset)
+        prefix = prefix + '_' if prefix else ''
+        table_bytes = 8 * 4 ** length
+        per_batch = _RECORD_BATCH_BYTES // table_bytes
+        ctx = _native.context()
+        if per_batch < 2:
+            for read_name, read in _fastq_reads(ctx, handle, prefix, min_quality, quality_offset):
+                yield cls.from_sequences([read], length, name=read_name)
+            return
+        for names, _, indexed in _indexed_pieces(ctx, handle, prefix, 'from_fastq_by_record', (min_quality, quality_offset)):
+            for first in range(0, len(names), per_batch):
+                indexed()
+                n = min(per_batch, len(names) - first)
+                for profile in cls._record_batch(ctx, length, first, n, names):
+                    yield profile
+
+    @classmethod
+    def from_fastq_by_window(cls, handle, length, window, step=None, prefix=None, min_quality=None, quality_offset=33):
+        """One profile per sliding window of every read of a four-line FASTQ handle: the windows of
+        ``from_fasta_by_window`` over the read's sequence line, named ``<read>:<start + 1>-<end>`` with the read names of
+        ``from_fastq_by_record``.  Coordinates count masked bases (``min_quality``): a masked base is a base that breaks
+        k-mers.  Indexing, batching, residency and errors are those of ``from_fastq_by_record``."""
+        length, window, step = _window_arguments(length, window, step)
+        _read_arguments(length, min_quality, quality_offset)
+        prefix = prefix + '_' if prefix else ''
+        table_bytes = 8 * 4 ** length
+        per_batch = _RECORD_BATCH_BYTES // table_bytes
+        ctx = _native.context()
+        if per_batch < 2:
+            for read_name, read in _fastq_reads(ctx, handle, prefix, min_quality, quality_offset):
+                for profile in cls._windows_one_by_one(read, read_name, length, window, step):
+                    yield profile
+            return
+        for profile in cls._indexed_windows(ctx, handle, length, window, step, prefix, per_batch, 'from_fastq_by_window',
+                                            (min_quality, quality_offset)):
+            yield profile
+
+    @classmethod
+    def _windows_one_by_one(cls, seq, record_name, length, window, step):
+        """The window profiles of one record by ``from_sequences`` (a k whose table alone exceeds the batch budget)."""
+        for start in range(0, _window_count(len(seq), window, step) * step, step):
+            end = min(start + window, len(seq))
+            yield cls.from_sequences([seq[start:end]], length, name='%s:%d-%d' % (record_name, start + 1, end))
+
+    @classmethod
+    def _indexed_windows(cls, ctx, handle, length, window, step, prefix, per_batch, who, fastq=None):
+        """The window profiles of every record of a handle, its records indexed on the device (``_indexed_pieces``)."""
+        for names, bases, indexed in _indexed_pieces(ctx, handle, prefix, who, fastq):
             n_windows, first_window = ctx.fasta_windows_layout(window, step)
             for first in range(0, n_windows, per_batch):
                 indexed()

@@ -87,31 +87,44 @@ def cat(input_handles, output_handle, names=None, prefixes=None):
 
 
 def count(input_handles, output_handle, size, names=None, by_record=False, fastq=False, min_quality=None, phred64=False,
-          by_window=None, step=None):
+          by_window=None, step=None, by_read=False):
     """k-mer profiles of FASTA files (kpal/kmer.py:112-146): one profile per file, or per record
     with ``by_record`` (record names, prefixed by the file's name when several files are given).
     With ``fastq`` the inputs are four-line FASTQ files, one profile per file (beyond the reference); ``min_quality`` masks
     bases of a lower Phred quality, read with offset 64 instead of 33 under ``phred64``.
     With ``by_window`` = W (beyond the reference) there is one profile per sliding window of W bases of every record, ``step``
-    bases apart (default W; it must divide W), named ``<record>:<start>-<end>`` and prefixed like the records' profiles."""
+    bases apart (default W; it must divide W), named ``<record>:<start>-<end>`` and prefixed like the records' profiles.
+    With ``by_read`` (beyond the reference) the inputs are four-line FASTQ files and there is one profile per read, named and
+    prefixed as ``by_record`` names records; with ``by_window`` as well, one per sliding window of every read.  ``fastq`` next
+    to it is redundant."""
+    if by_read and by_record:
+        raise ValueError('--by-read and --by-record exclude each other (--by-read is the --by-record of FASTQ input)')
     if fastq and by_record:
-        raise ValueError('--by-record does not apply to FASTQ input (one profile per read is not supported)')
+        raise ValueError('--by-record does not apply to FASTQ input (one profile per read is --by-read)')
     if by_window is not None and by_record:
         raise ValueError('--by-window and --by-record exclude each other (a window profile is named after its record already)')
-    if by_window is not None and fastq:
-        raise ValueError('--by-window does not apply to FASTQ input (windows are cut from FASTA records)')
+    if by_window is not None and fastq and not by_read:
+        raise ValueError('--by-window does not apply to FASTQ input (windows of reads are --by-read --by-window)')
     if step is not None and by_window is None:
         raise ValueError('--step applies to --by-window only')
     if by_window is not None:
         klib._window_arguments(size, by_window, step)
-    if not fastq and (min_quality is not None or phred64):
-        raise ValueError('--min-quality and --phred64 apply to FASTQ input only (add --fastq)')
+    if not (fastq or by_read) and (min_quality is not None or phred64):
+        raise ValueError('--min-quality and --phred64 apply to FASTQ input only (add --fastq or --by-read)')
+    if by_read:
+        klib._read_arguments(size, min_quality, 64 if phred64 else 33)
     names = names or [_name_from_handle(handle) for handle in input_handles]
     if len(names) != len(input_handles):
         raise ValueError(NAMES_COUNT_ERROR)
     several = len(input_handles) > 1
     for handle, name in zip(input_handles, names):
-        if fastq:
+        if by_read and by_window is not None:
+            profiles = klib.Profile.from_fastq_by_window(handle, size, by_window, step=step, prefix=name if several else None,
+                                                         min_quality=min_quality, quality_offset=64 if phred64 else 33)
+        elif by_read:
+            profiles = klib.Profile.from_fastq_by_record(handle, size, prefix=name if several else None, min_quality=min_quality,
+                                                         quality_offset=64 if phred64 else 33)
+        elif fastq:
             profiles = [klib.Profile.from_fastq(handle, size, name=name, min_quality=min_quality,
                                                 quality_offset=64 if phred64 else 33)]
         elif by_record:
@@ -498,10 +511,13 @@ def build_parser():
                      help='with --by-window: bases between the starts of two windows (a divisor of W; default: W)')
     sub.add_argument('--fastq', dest='fastq', action='store_true',
                      help='the INPUTs are four-line FASTQ files of reads (one k-mer profile per file)')
+    sub.add_argument('--by-read', dest='by_read', action='store_true',
+                     help='the INPUTs are four-line FASTQ files: make a k-mer profile per read (profiles are named by the '
+                     'read names and prefixed like those of --by-record); with --by-window W, per sliding window of every read')
     sub.add_argument('--min-quality', dest='min_quality', metavar='Q', type=int, default=None,
-                     help='with --fastq: mask bases whose Phred quality is below Q (0..93; default: no mask)')
+                     help='with --fastq or --by-read: mask bases whose Phred quality is below Q (0..93; default: no mask)')
     sub.add_argument('--phred64', dest='phred64', action='store_true',
-                     help='with --fastq: quality bytes are Phred + 64 (default: Phred + 33)')
+                     help='with --fastq or --by-read: quality bytes are Phred + 64 (default: Phred + 33)')
     sub = command('merge', merge, ['paired_input_profile', 'output_profile'])
     sub.add_argument('-m', dest='merger', type=str, default='sum', choices=metrics.mergers,
                      help='merge function (default: %(default)s)')
