@@ -5,13 +5,19 @@ call is batched -- driven by a stand-alone program built with the address and un
 value is a literal written down from the rule, none is computed with the header.
 
 Height h = 0 .. k-1 has 4^(k-1-h) nodes and starts 4^(k-1) + ... + 4^(k-h) elements into the pyramid; (4^k - 1) / 3 nodes in
-all; ten bytes of scratch per element (an int64 sum, a code, a flag)."""
+all; ten bytes of scratch per element (an int64 sum, a code, a flag).
+
+The last rows hold tests/smooth_cases.py -- the Python restatement of the grid rules that the GPU tests of multi-trip shapes
+(tests/test_gpu_smooth_sets_trips.py) take their preconditions from -- against this program and matrix_plan_check at 256
+compute units, and its trip counts against the literals of smooth_cases.TABLE."""
 import os
 import re
 import shutil
 import subprocess
 
 import pytest
+
+import smooth_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PADDING = -1
@@ -105,3 +111,88 @@ def test_batched(plan):
           (('batched', 15, 4, 5, 0, 32 * GIB), 1), (('batched', 15, 5, 5, 0, 32 * GIB), 0),
           (('batched', 16, 1, 1, 0, 32 * GIB), 1), (('batched', 16, 2, 1, 0, 32 * GIB), 0),
           (('batched', 12, 64, 64, 0, 32 * GIB), 1)])
+
+
+@pytest.fixture(scope='module')
+def answers(tmp_path_factory):
+    """ask(program, [query words]) -> [tuple of ints]: the answers of matrix_plan_check / smooth_plan_check, nothing asserted"""
+    if shutil.which('g++') is None:
+        pytest.skip('no g++')
+    exes = {}
+    for name in ('matrix_plan_check', 'smooth_plan_check'):
+        exes[name] = str(tmp_path_factory.mktemp(name) / name)
+        b = subprocess.run(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-Wall', '-o', exes[name],
+                            os.path.join(ROOT, 'tests', 'native', name + '.cpp')], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+        assert b.returncode == 0 and not b.stdout.strip(), b.stdout.decode()[-3000:]
+
+    def ask(name, queries):
+        text = ''.join(' '.join(str(int(w)) if not isinstance(w, str) else w for w in q) + '\n' for q in queries)
+        r = subprocess.run([exes[name]], input=text.encode(), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+        got = r.stdout.decode().split('\n')
+        assert r.returncode == 0 and got[-2].endswith('_PLAN_DONE %d' % len(queries)), got[-20:]
+        return [tuple(int(w) for w in line.split()) for line in got[:len(queries)]]
+    return ask
+
+
+@pytest.mark.parametrize('shape', sorted(smooth_cases.TABLE), ids=lambda s: 'k%d_%dx%d%s' % (s[0], s[1], s[2], '_tri' if s[3] else ''))
+def test_trips_restatement_is_the_headers(answers, shape):
+    """smooth_cases' cross_staged, cross_grid, option_totals_gx, smooth_stride and smooth_level_* give what the headers give,
+    at every shape of the table and every height."""
+    k, Q, R, tri = shape
+    cu, n = smooth_cases.TABLE_CU, 4 ** k
+    nprof = Q if tri else Q + R
+    staged = smooth_cases.cross_staged(Q, R, n)
+    units, gx = smooth_cases.cross_grid(cu, Q, R, n, tri, staged)
+    stride = smooth_cases.smooth_stride(k)
+    ntiles = ((Q + 3) // 4) * ((Q + 3) // 4 + 1) // 2 if tri else ((Q + 3) // 4) * ((R + 3) // 4)
+    got = answers('matrix_plan_check', [('staged', Q, R, n), ('grid', cu, Q, R, n, tri, staged), ('grid', cu, Q, R, stride, tri, staged), ('gxt', cu, nprof, stride)]
+                  + [('gxt', cu, nprof, smooth_cases.smooth_level_nodes(k, h)) for h in range(k)])
+    assert got[0] == (int(staged),)
+    assert got[1] == (units, gx, 16 * ntiles, (R + 3) // 4, (R + 15) // 16)
+    assert got[3] == (smooth_cases.option_totals_gx(cu, nprof, stride),)
+    assert got[4:] == [(smooth_cases.option_totals_gx(cu, nprof, smooth_cases.smooth_level_nodes(k, h)),) for h in range(k)]
+    # the pyramid pass is launched with the grid of the bins, whatever cross_grid would make of the pyramids' own length
+    assert got[2][1] <= gx
+    got = answers('smooth_plan_check', [('stride', k), ('nodes', k)] + [('level', k, h) for h in range(k)])
+    assert got[0] == (stride,) and got[1] == (smooth_cases.smooth_nodes(k),) and stride % smooth_cases.SUPER_BINS == 0
+    assert got[2:] == [(smooth_cases.smooth_level_offset(k, h), smooth_cases.smooth_level_nodes(k, h)) for h in range(k)]
+
+
+@pytest.mark.parametrize('shape', sorted(smooth_cases.TABLE), ids=lambda s: 'k%d_%dx%d%s' % (s[0], s[1], s[2], '_tri' if s[3] else ''))
+def test_trips_of_the_table(shape):
+    """The trip counts at 256 compute units are the literals of the table, and every shape has a loop that goes round twice."""
+    k, Q, R, tri = shape
+    want = smooth_cases.TABLE[shape]
+    t = smooth_cases.trips(smooth_cases.TABLE_CU, k, Q, R, tri)
+    assert (t['staged'], t['units'], t['gx'], t['bins'], t['pyramid']) == (want['staged'], want['units'], want['gx'], want['bins'], want['pyramid']), t
+    assert t['first'] == want['gx'] * (64 if want['staged'] else 256)
+    if want['level0'] is not None:
+        assert (t['levels'][0], t['codes']) == (want['level0'], want['codes']), t
+    assert len(t['levels']) == k and t['levels'][k - 1] == (1, 1)
+    assert t['bins'][1] >= 2
+
+
+def test_trips_by_hand():
+    """_span and last_trip_chunk on ranges small enough to count on one's fingers."""
+    span, last = smooth_cases._span, smooth_cases.last_trip_chunk
+    assert span(10, 4) == (2, 3)          # walkers 0, 1 take three items (0 4 8, 1 5 9), walkers 2, 3 two
+    assert span(8, 4) == (2, 2) and span(3, 4) == (1, 1) and span(4, 4) == (1, 1) and span(5, 4) == (1, 2) and span(1, 256) == (1, 1)
+    assert last(10, 4, 0) == (8, 2) and last(10, 4, 1) == (9, 2) and last(10, 4, 3) == (7, 1) and last(4096, 1024, 5) == (3077, 3)
+    # one-trip shapes of tests/test_gpu_smooth_sets.py: what the new module is for
+    for k, Q, R in ((6, 17, 33), (7, 17, 18), (6, 3, 40), (6, 5, 7)):
+        t = smooth_cases.trips(256, k, Q, R)
+        assert t['bins'] == (1, 1) and t['pyramid'] == (1, 1) and t['codes'][1] == 1 and all(l == (1, 1) for l in t['levels']), (k, Q, R, t)
+
+
+def test_codes_reference_by_hand():
+    """k = 2: sixteen bins, four height-0 nodes, the root -- codes written down from the definitions."""
+    table = [5, 5, 5, 5, 0, 9, 9, 9, 5, 5, 5, 5, 1, 1, 1, 1]
+    r = smooth_cases.codes_reference(table, 2, 'min', 0)                 # node 1 has a zero quarter; the root's quarters are 20, 27, 20, 4
+    assert [s.tolist() for s in r['sums']] == [[20, 27, 20, 4], [71]]
+    assert [c.tolist() for c in r['codes']] == [[0, 1, 0, 0], [0]] and r['dead_bins'].tolist() == [False] * 4 + [True] * 4 + [False] * 8
+    assert r['pyramid'].tolist() == [0, 1, 0, 0, 0] + [2] * 59
+    r = smooth_cases.codes_reference(table, 2, 'average', 17.75)        # the root's average is 17.75: a tie collapses; node 3's is 1
+    assert [f.tolist() for f in r['flags']] == [[True, True, True, True], [True]]
+    assert [c.tolist() for c in r['codes']] == [[2, 2, 2, 2], [1]] and r['dead_bins'].all()
+    r = smooth_cases.codes_reference(table, 2, 'median', 5)              # medians 5, 9, 5, 1 and (20 + 20) / 2
+    assert [c.tolist() for c in r['codes']] == [[1, 0, 1, 1], [0]]
