@@ -410,6 +410,26 @@ typedef struct kpal_profile_stats {
 int kpal_stats(kpal_ctx *ctx, size_t n, const int64_t *host_counts, kpal_profile_stats *out);
 int kpal_stats_device(kpal_ctx *ctx, size_t n, const int64_t *dev_counts, kpal_profile_stats *out);
 
+/* The same summaries (kpal/klib.py:193-225) for every one of n_tables vectors of `bins` entries lying one behind the other,
+ * replacing a loop of kpal_stats calls (one per profile of `kpal count --by-record`, `kpal info`, `kpal stats`): a number of
+ * launches and two synchronisations per pass that do not grow with n_tables -- six launches and two per 8-bit digit of the
+ * radix select, as many digits as the widest value range of the pass needs.  A vector's summary does not depend on the set it is
+ * in nor on its place there, bit for bit; values as kpal_stats (total, non_zero, min, max and median exact; mean and std
+ * <= 1e-9 relative).  Passes are cut inside (stat_plan.hpp: scratch budget, 65535 profiles); KPAL_STAT_SET_PROFILES, read on
+ * every call, lowers the profiles of a pass.  KPAL_E_INVALID: a NULL pointer, n_tables == 0, bins == 0, tables not 8-byte
+ * aligned.  The host variant uploads through the context's scratch. */
+int kpal_stats_set_device(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *dev_tables /* n_tables x bins */,
+                          kpal_profile_stats *host_out /* n_tables */);
+int kpal_stats_set(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *host_tables,
+                   kpal_profile_stats *host_out);
+/* kmer.get_balance scores (kpal/kmer.py:243-245) of n_tables consecutive 4^k tables, replacing a loop of kpal_strand_balance
+ * calls: the fused split + multiset kernel over tiles x profiles and one reduction per pass.  KPAL_E_INVALID: k outside
+ * 1..KPAL_MAX_K, a NULL pointer, n_tables == 0, a pairwise other than prod or sum, tables not 8-byte aligned. */
+int kpal_strand_balance_set_device(kpal_ctx *ctx, int k, size_t n_tables, const int64_t *dev_tables /* n_tables x 4^k */,
+                                   int pairwise, double *host_out /* n_tables */);
+int kpal_strand_balance_set(kpal_ctx *ctx, int k, size_t n_tables, const int64_t *host_tables, int pairwise,
+                            double *host_out);
+
 /* Profile.merge(profile, merger) for the built-in metrics.mergers (kpal/metrics.py:174-179,
  * kpal/klib.py:269-283): out = merger(left, right); out may be left or right. */
 #define KPAL_MERGE_SUM 0   /* x + y */

@@ -149,6 +149,10 @@ SIGNATURES = {
     'kpal_smooth_distance_matrix_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _optp, _f64p]),
     'kpal_stats': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _statp]),
     'kpal_stats_device': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _statp]),
+    'kpal_stats_set': (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _statp]),
+    'kpal_stats_set_device': (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _statp]),
+    'kpal_strand_balance_set': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_size_t, _vp, ctypes.c_int, _f64p]),
+    'kpal_strand_balance_set_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_size_t, _vp, ctypes.c_int, _f64p]),
     'kpal_merge': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, _vp]),
     'kpal_merge_device': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, _vp]),
     'kpal_shrink': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
@@ -291,6 +295,13 @@ def _as_i64(a, what='counts'):
     if a.dtype.kind not in 'iub':
         raise TypeError('%s must be an integer array (got %s)' % (what, a.dtype))
     return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _as_i64_2d(a, what='tables'):
+    a = _as_i64(a, what)
+    if a.ndim != 2 or a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError('%s must have shape (n_tables, bins) with neither zero (got %s)' % (what, a.shape))
+    return a
 
 
 class DeviceTable(object):
@@ -790,6 +801,36 @@ class Context(object):
     def stats_device(self, dev_counts, n):
         out = ProfileStats()
         _check(self._L.kpal_stats_device(self._h, int(n), dev_counts, ctypes.byref(out)))
+        return out
+
+    def stats_set_device(self, dev_ptr, n_tables, bins):
+        """The summaries of n_tables consecutive int64 vectors of ``bins`` entries at a device address -> a ctypes array of
+        ProfileStats (kpal_stats_set_device: launches that do not grow with n_tables)."""
+        out = (ProfileStats * int(n_tables))()
+        _check(self._L.kpal_stats_set_device(self._h, int(n_tables), int(bins), _vp(dev_ptr), out))
+        return out
+
+    def stats_set(self, tables_2d):
+        """stats_set_device for a host array of shape (n_tables, bins)."""
+        t = _as_i64_2d(tables_2d)
+        out = (ProfileStats * t.shape[0])()
+        _check(self._L.kpal_stats_set(self._h, t.shape[0], t.shape[1], t.ctypes.data, out))
+        return out
+
+    def strand_balance_set_device(self, k, n_tables, dev_ptr, pairwise=PAIRWISE_PROD):
+        """The strand balance of n_tables consecutive 4**k tables at a device address -> float64[n_tables]."""
+        out = np.zeros(int(n_tables), dtype=np.float64)
+        _check(self._L.kpal_strand_balance_set_device(self._h, int(k), int(n_tables), _vp(dev_ptr), int(pairwise),
+                                                      out.ctypes.data_as(_f64p)))
+        return out
+
+    def strand_balance_set(self, tables_2d, k, pairwise=PAIRWISE_PROD):
+        """strand_balance_set_device for a host array of shape (n_tables, 4**k)."""
+        t = _as_i64_2d(tables_2d)
+        if t.shape[1] != 4 ** int(k):
+            raise ValueError('profile length %d != 4**%d' % (t.shape[1], k))
+        out = np.zeros(t.shape[0], dtype=np.float64)
+        _check(self._L.kpal_strand_balance_set(self._h, int(k), t.shape[0], t.ctypes.data, int(pairwise), out.ctypes.data_as(_f64p)))
         return out
 
     def merge(self, left, right, merger):

@@ -3,7 +3,8 @@
 // one unit calls in another.  (kpal_ctx.hip: context + profiling API; kpal_count.hip: counting front end and the
 // round-1 pipelines; kpal_text.hip: FASTA and FASTQ ingest; kpal_records.hip: one profile per record / per sliding window;
 // kpal_quads.hip / kpal_quads2.hip: the quad record pipelines, planned by quad_plan.hpp; kpal_vec.hip: one vector -- balance,
-// split, summaries, merge, shrink; kpal_pair.hip: the distance of one pair, plain and with options; kpal_cross.hip: the distances
+// split, summaries, merge, shrink; kpal_sets.hip: the summaries and the strand balance of a whole set of vectors, planned by
+// stat_plan.hpp; kpal_pair.hip: the distance of one pair, plain and with options; kpal_cross.hip: the distances
 // of sets of profiles, triangle and rectangle, planned by matrix_plan.hpp; kpal_multi.hip: multi-GPU entry points over RCCL.)
 #pragma once
 #include "../../include/kpal_hip.h"

@@ -4,6 +4,7 @@
 
 #include "vec_kernels.hpp"
 #include "stat_kernels.hpp"
+#include "stat_plan.hpp"
 
 KPAL_API uint64_t kpal_reverse_complement(uint64_t number, int k)
 {
@@ -211,16 +212,7 @@ KPAL_API int kpal_stats_device(kpal_ctx *ctx, size_t n, const int64_t *dev_count
     out->non_zero = (int64_t)t.non_zero;
     out->min = t.mn;
     out->max = t.mx;
-    // the 128-bit sum as a double: magnitude first, so that a small negative sum does not cancel
-    uint64_t mag_lo = t.sum_lo, mag_hi = (uint64_t)t.sum_hi;
-    const bool negative = t.sum_hi < 0;
-    if (negative) {
-        mag_lo = ~mag_lo + 1ULL;
-        mag_hi = ~mag_hi + (mag_lo == 0 ? 1ULL : 0ULL);
-    }
-    const double magnitude = std::ldexp((double)mag_hi, 64) + (double)mag_lo;
-    const double exact_sum = negative ? -magnitude : magnitude;
-    out->mean = exact_sum / (double)n;
+    out->mean = stat_mean(t.sum_lo, t.sum_hi, (uint64_t)n);   // the 128-bit sum as a double, magnitude first (stat_plan.hpp: the set entry's mean is this one)
     // std: sum((x - mean)^2) / n, kpal/klib.py:220-225 (ndarray.std)
     double *dv = (double *)ctx->partials.p;
     LAUNCH(ctx, "stats_var", stats_var_kernel, dim3(grid), dim3(kStatThreads), dev_counts, (uint64_t)n, out->mean, dv);

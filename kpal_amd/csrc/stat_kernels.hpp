@@ -12,6 +12,8 @@
 //   S6  shrink_kernel         sums of 4^factor consecutive counts, int64 wrap (klib.py:329-352)
 //
 // All are single-pass streaming kernels bound by HBM: 8 bytes read per bin (S5: 16 read + 8 written).
+// Two units include this header (kpal_vec.hip; kpal_sets.hip for StatPartial and the select key): the kernels that are no templates
+// are static.  The same summaries for all profiles of a set at once: stat_set_kernels.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -55,7 +57,7 @@ __device__ __forceinline__ StatPartial stat_shfl_down(const StatPartial &p, int 
 constexpr int kStatThreads = 256;
 
 // partial[blockIdx.x] = summary of this workgroup's grid-stride share.
-__global__ __launch_bounds__(kStatThreads) void stats_kernel(const int64_t *__restrict__ x, uint64_t n,
+static __global__ __launch_bounds__(kStatThreads) void stats_kernel(const int64_t *__restrict__ x, uint64_t n,
                                                              StatPartial *__restrict__ partial)
 {
     __shared__ StatPartial wsum[kStatThreads / 64];
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(kStatThreads) void stats_kernel(const int64_t *__re
 }
 
 // partial[blockIdx.x] = sum over the workgroup's share of ((double)x - mean)^2, fixed order.
-__global__ __launch_bounds__(kStatThreads) void stats_var_kernel(const int64_t *__restrict__ x, uint64_t n, double mean,
+static __global__ __launch_bounds__(kStatThreads) void stats_var_kernel(const int64_t *__restrict__ x, uint64_t n, double mean,
                                                                  double *__restrict__ partial)
 {
     __shared__ double wsum[kStatThreads / 64];
@@ -110,7 +112,7 @@ __device__ __host__ __forceinline__ uint64_t select_key(int64_t v) { return (uin
 // hist[d] += number of elements whose key matches `prefix` on the bits of `mask` and has digit d at
 // `shift`.  Counts are typically concentrated in one or two digits, so the wave first counts the
 // digit of its first lane with a ballot; only the other lanes use one LDS atomic each.
-__global__ __launch_bounds__(kStatThreads) void select_hist_kernel(const int64_t *__restrict__ x, uint64_t n, uint64_t mask,
+static __global__ __launch_bounds__(kStatThreads) void select_hist_kernel(const int64_t *__restrict__ x, uint64_t n, uint64_t mask,
                                                                    uint64_t prefix, int shift,
                                                                    unsigned long long *__restrict__ hist)
 {
@@ -137,7 +139,7 @@ __global__ __launch_bounds__(kStatThreads) void select_hist_kernel(const int64_t
 }
 
 // partial[blockIdx.x] = smallest key above `key0` in the workgroup's share (UINT64_MAX if none).
-__global__ __launch_bounds__(kStatThreads) void select_next_kernel(const int64_t *__restrict__ x, uint64_t n, uint64_t key0,
+static __global__ __launch_bounds__(kStatThreads) void select_next_kernel(const int64_t *__restrict__ x, uint64_t n, uint64_t key0,
                                                                    unsigned long long *__restrict__ partial)
 {
     __shared__ uint64_t wmin[kStatThreads / 64];
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(256) void merge_kernel(const int64_t *__restrict__ 
 // out[j] = sum of in[j*m .. j*m + m), m = 4^factor (int64 wrap).  Thread t adds the input pair
 // (2t, 2t+1) with one 16-byte load; for m <= 128 the m/2 lanes of an output combine with shuffles,
 // for larger m a wave walks its output's inputs.
-__global__ __launch_bounds__(256) void shrink_small_kernel(const int64_t *__restrict__ in, uint64_t n_pairs, int lanes_per_out,
+static __global__ __launch_bounds__(256) void shrink_small_kernel(const int64_t *__restrict__ in, uint64_t n_pairs, int lanes_per_out,
                                                            int64_t *__restrict__ out)
 {
     const uint64_t stride = (uint64_t)gridDim.x * 256;
@@ -198,7 +200,7 @@ __global__ __launch_bounds__(256) void shrink_small_kernel(const int64_t *__rest
     }
 }
 
-__global__ __launch_bounds__(256) void shrink_large_kernel(const int64_t *__restrict__ in, uint64_t n_out, uint64_t m,
+static __global__ __launch_bounds__(256) void shrink_large_kernel(const int64_t *__restrict__ in, uint64_t n_out, uint64_t m,
                                                            int64_t *__restrict__ out)
 {
     const int lane = threadIdx.x & 63;

@@ -9,7 +9,8 @@
 // fp64 sums are reduced in a FIXED order (per-thread serial, wave shuffle tree, block tree,
 // then a single-workgroup pass over the per-block partials) so results are run-to-run
 // reproducible; they agree with NumPy's pairwise summation to ~1e-15 relative.
-// Two units include this header (kpal_vec.hip; kpal_pair.hip for the pair kernels): the kernels that are no templates are static.
+// Three units include this header (kpal_vec.hip; kpal_pair.hip for the pair kernels; kpal_sets.hip for the strand balance bodies): the
+// kernels that are no templates are static.
 #pragma once
 #include "matrix_common.hpp"
 
@@ -171,9 +172,10 @@ static __global__ __launch_bounds__(256) void split_write_kernel(const int64_t *
 }
 
 // ---- strand balance: multiset(*split()) fused ------------------------------------------------
+// The body serves one profile (strand_balance_kernel) and the profiles of a set (strand_balance_set_kernel, stat_set_kernels.hpp:
+// the profile from blockIdx.y): the workgroups of blockIdx.x stride through the n bins of `c`; the reduced partial is valid in thread 0.
 template <int PW>
-__global__ __launch_bounds__(256) void strand_balance_kernel(const int64_t *__restrict__ c, int k, uint64_t n,
-                                                             Partial *__restrict__ partials)
+__device__ __forceinline__ Partial strand_balance_body(const int64_t *__restrict__ c, int k, uint64_t n)
 {
     Partial p = {0.0, 0ULL};
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -191,7 +193,14 @@ __global__ __launch_bounds__(256) void strand_balance_kernel(const int64_t *__re
             p.m += 1;
         }
     }
-    p = block_reduce(p);
+    return block_reduce(p);
+}
+
+template <int PW>
+__global__ __launch_bounds__(256) void strand_balance_kernel(const int64_t *__restrict__ c, int k, uint64_t n,
+                                                             Partial *__restrict__ partials)
+{
+    const Partial p = strand_balance_body<PW>(c, k, n);
     if (threadIdx.x == 0) partials[blockIdx.x] = p;
 }
 
@@ -348,12 +357,12 @@ __global__ __launch_bounds__(1024) void pair_distance_balanced_kernel(const int6
 // kmer.get_balance score (kpal/kmer.py:243-245) with the split halves never materialised: every
 // unordered pair {i, rc(i)} is visited once -- from the tile of the smaller M, or, inside a
 // self-paired tile, from its smaller index (palindromes contribute f = r = c[i], klib.py:322-323).
+// (The body: tile M = blockIdx.x of profile `c`, for strand_balance_tiled_kernel and strand_balance_tiled_set_kernel; the reduced
+// partial is valid in thread 0.)
 template <int PW>
-__global__ __launch_bounds__(1024) void strand_balance_tiled_kernel(const int64_t *__restrict__ c, int k,
-                                                                    Partial *__restrict__ partials)
+__device__ __forceinline__ Partial strand_balance_tiled_body(const int64_t *__restrict__ c, int k, unsigned long long (*A)[65], unsigned long long (*B)[65])
 {
     constexpr int T = 3, S = 64;
-    __shared__ unsigned long long A[S][S + 1], B[S][S + 1];
     const int md = k - 2 * T;
     const uint64_t M = blockIdx.x;
     const uint64_t Mr = md > 0 ? revcomp(M, md) : 0;
@@ -394,7 +403,15 @@ __global__ __launch_bounds__(1024) void strand_balance_tiled_kernel(const int64_
             }
         }
     }
-    p = block_reduce(p);
+    return block_reduce(p);
+}
+
+template <int PW>
+__global__ __launch_bounds__(1024) void strand_balance_tiled_kernel(const int64_t *__restrict__ c, int k,
+                                                                    Partial *__restrict__ partials)
+{
+    __shared__ unsigned long long A[64][65], B[64][65];
+    const Partial p = strand_balance_tiled_body<PW>(c, k, A, B);
     if (threadIdx.x == 0) partials[blockIdx.x] = p;
 }
 

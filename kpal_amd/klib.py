@@ -27,7 +27,7 @@ import stat
 
 import numpy as np
 
-from . import _native, metrics
+from . import _native, kdistlib, metrics
 
 # The C gatherer of from_sequences (csrc/kpal_gather.c, built by __graft_entry__.build(): walks the list's objects and copies them on
 # several threads); without it the sequences are joined by the interpreter -- same stream, ~3 x slower for lists of short reads.
@@ -64,6 +64,7 @@ class _DeviceBatch(object):
         else:
             self.ptr = ctx.alloc(self.nbytes)
         self.host = None
+        self._stats = None
         _DeviceBatch.live_bytes += self.nbytes
 
     def table(self, index):
@@ -75,6 +76,14 @@ class _DeviceBatch(object):
             self.ctx.d2h(host, self.ptr)
             self.host = host
         return self.host[index]
+
+    def stats(self, index):
+        """The summaries of table ``index``.  The first request summarises the WHOLE batch in one ``kpal_stats_set_device``
+        call (launches that do not grow with the batch; a profile at a time cost five launches and five round trips each) and
+        keeps the result: the tables of a batch are never written, so it stays valid."""
+        if self._stats is None:
+            self._stats = self.ctx.stats_set_device(self.ptr, self.n_tables, self.nbytes // (8 * self.n_tables))
+        return self._stats[index]
 
     def __del__(self):
         try:
@@ -455,6 +464,85 @@ def _encode(sequence):
         return bytes(sequence)
     # non-latin-1 characters can never be nucleotides: they become '?' (a separator)
     return str(sequence).encode('latin-1', 'replace')
+
+
+def _summary_dict(s):
+    return {'total': np.int64(s.total), 'non_zero': int(s.non_zero), 'mean': np.float64(s.mean),
+            'median': np.float64(s.median), 'std': np.float64(s.std)}
+
+
+def _set_counts(profile):
+    """Whether ``profile`` can be one table of a device set: 4^k integer counts, in HBM or on the host.  (A table in HBM is not
+    asked for its counts.)"""
+    if profile._device_counts():
+        return True
+    c = np.asanyarray(profile.counts)
+    return c.dtype.kind in 'iub' and c.ndim == 1 and c.size == 4 ** profile.length
+
+
+def _device_sets(profiles, indices):
+    """``indices`` -- places in ``profiles`` of integer profiles -- by k-mer length and in groups of at most
+    ``_RECORD_BATCH_BYTES`` of tables: yields (places, context, device address of their consecutive tables, k).  Tables that
+    are consecutive in one batch are used where they lie, others are gathered (``kdistlib._DeviceSet``)."""
+    by_length = {}
+    for i in indices:
+        by_length.setdefault(profiles[i].length, []).append(i)
+    for k, places in sorted(by_length.items()):
+        per = max(1, _RECORD_BATCH_BYTES // (8 * 4 ** k))
+        for at in range(0, len(places), per):
+            group = places[at:at + per]
+            members = [profiles[i] for i in group]
+            ctx = kdistlib._cross_context(members)
+            dset = kdistlib._DeviceSet(ctx, members)
+            try:
+                yield group, ctx, dset.ptr, k
+            finally:
+                dset.release()
+
+
+def summaries(profiles):
+    """``[p.summary() for p in profiles]`` -- the same keys, types and values -- with the integer profiles summarised as SETS
+    (``kpal_stats_set_device``: a number of launches that does not grow with the set).  A table that is still in HBM is
+    summarised where it lies with the rest of its batch, once (``_DeviceBatch.stats``), and stays there; host counts of one
+    k-mer length are uploaded in groups of at most ``_RECORD_BATCH_BYTES``.  Lengths may be mixed; profiles that are not
+    integer counts (scaled ones) take their own ``summary()``."""
+    profiles = list(profiles)
+    out = [None] * len(profiles)
+    host = []
+    for i, p in enumerate(profiles):
+        if p._device_counts():
+            out[i] = p.summary()
+        elif _set_counts(p):
+            host.append(i)
+        else:
+            out[i] = p.summary()
+    for group, ctx, ptr, k in _device_sets(profiles, host):
+        stats = ctx.stats_set_device(ptr, len(group), 4 ** k)
+        for j, i in enumerate(group):
+            out[i] = _summary_dict(stats[j])
+    return out
+
+
+def strand_balances(profiles, pairwise='prod'):
+    """The strand balance score of every profile (kpal/kmer.py:243-245: the multiset distance between the forward and the
+    reverse-complement half) as a list of float, the integer profiles as SETS (``kpal_strand_balance_set_device``: two launches
+    per set) under the rules of ``summaries``; no table that is still in HBM is downloaded.  ``pairwise``: 'prod' or 'sum'.
+    Other profiles take the NumPy route of ``kmer.get_balance``: ``split`` and ``metrics.multiset``."""
+    native = {'prod': _native.PAIRWISE_PROD, 'sum': _native.PAIRWISE_SUM}[pairwise]
+    profiles = list(profiles)
+    out = [None] * len(profiles)
+    sets = []
+    for i, p in enumerate(profiles):
+        if _set_counts(p):
+            sets.append(i)
+        else:
+            forward, reverse = p.split()
+            out[i] = float(metrics.multiset(forward, reverse, metrics.pairwise[pairwise]))
+    for group, ctx, ptr, k in _device_sets(profiles, sets):
+        scores = ctx.strand_balance_set_device(k, len(group), ptr, native)
+        for j, i in enumerate(group):
+            out[i] = float(scores[j])
+    return out
 
 
 class Profile(object):
@@ -843,20 +931,20 @@ class Profile(object):
 
     @property
     def non_zero(self):
-        dev = self._device_counts()
-        return int(dev[0].stats_device(dev[1], self.number).non_zero) if dev else np.count_nonzero(self.counts)
+        return int(self._device_stats().non_zero) if self._device_counts() else np.count_nonzero(self.counts)
 
     @property
     def total(self):
-        dev = self._device_counts()
-        return np.int64(dev[0].stats_device(dev[1], self.number).total) if dev else self.counts.sum()
+        return np.int64(self._device_stats().total) if self._device_counts() else self.counts.sum()
 
     def _device_stats(self):
-        """``kpal_stats`` over integer counts (one upload -- none for a table that is still in HBM --, two streaming passes and
-        a radix select), or None when the counts are not integers (scaled profiles keep NumPy's float formulation)."""
-        dev = self._device_counts()
-        if dev:
-            return dev[0].stats_device(dev[1], self.number)
+        """``kpal_stats`` over integer counts (one upload, two streaming passes and a radix select), or None when the counts are
+        not integers (scaled profiles keep NumPy's float formulation).  A table that is still in HBM is summarised there, with all
+        tables of its batch at once (``_DeviceBatch.stats``); once its counts have been handed out, the host array is summarised
+        anew every time -- whoever holds it may have changed it."""
+        if self._device_counts():
+            batch, index, _ = self._device
+            return batch.stats(index)
         c = np.asanyarray(self.counts)
         if c.dtype.kind not in 'iub' or c.ndim != 1 or c.size == 0:
             return None
@@ -886,8 +974,7 @@ class Profile(object):
         s = self._device_stats()
         if s is None:
             return dict((key, getattr(self, key)) for key in ('total', 'non_zero', 'mean', 'median', 'std'))
-        return {'total': np.int64(s.total), 'non_zero': int(s.non_zero), 'mean': np.float64(s.mean),
-                'median': np.float64(s.median), 'std': np.float64(s.std)}
+        return _summary_dict(s)
 
     # ---- I/O -------------------------------------------------------------------------------
     def save(self, handle, name=None):
@@ -896,8 +983,8 @@ class Profile(object):
         if name and ('/' in name or '.' in name):
             raise ValueError('Profile name may not contain / or . characters.')
         name = name or self.name or next(str(n) for n in itertools.count(1) if str(n) not in handle['profiles'])
+        attrs = self.summary()        # before ``counts`` is touched: a table still in HBM is summarised there, with its whole batch
         dataset = handle.create_dataset('profiles/' + name, data=self.counts, dtype='int64', compression='gzip')
-        attrs = self.summary()        # all five summaries from one pass over the counts
         dataset.attrs['length'] = self.length
         for key in ('total', 'non_zero', 'mean', 'median', 'std'):
             dataset.attrs[key] = attrs[key]

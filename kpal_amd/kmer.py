@@ -163,26 +163,34 @@ def balance(input_handle, output_handle, names=None):
         profile.save(output_handle)
 
 
+def _profile_groups(input_handle, names):
+    """The profiles ``names`` of a file, read in groups of at most ``klib._RECORD_BATCH_BYTES`` of counts (never less than one
+    profile): what the set functions of klib take at a time."""
+    group, size = [], 0
+    for name in names:
+        profile = klib.Profile.from_file(input_handle, name=name)
+        group.append(profile)
+        size += np.asanyarray(profile.counts).nbytes
+        if size >= klib._RECORD_BATCH_BYTES:
+            yield group
+            group, size = [], 0
+    if group:
+        yield group
+
+
 def get_balance(input_handle, output_handle, precision=10, names=None):
     """``name balance`` lines: the multiset distance between the forward and the
-    reverse-complement half of each profile (kpal/kmer.py:222-247) -- one fused kernel."""
-    from . import _native
-    for name in _profile_names(input_handle, names):
-        profile = klib.Profile.from_file(input_handle, name=name)
-        counts = np.asanyarray(profile.counts)
-        if counts.dtype.kind in 'iub':
-            score = _native.context().strand_balance(counts, profile.length, _native.PAIRWISE_PROD)
-        else:
-            forward, reverse = profile.split()
-            score = metrics.multiset(forward, reverse, metrics.pairwise['prod'])
-        print(name, _fixed(precision, score), file=output_handle)
+    reverse-complement half of each profile (kpal/kmer.py:222-247) -- one fused kernel over all profiles of a group."""
+    for group in _profile_groups(input_handle, _profile_names(input_handle, names)):
+        for profile, score in zip(group, klib.strand_balances(group, 'prod')):
+            print(profile.name, _fixed(precision, score), file=output_handle)
 
 
 def get_stats(input_handle, output_handle, precision=10, names=None):
-    """``name mean std`` lines (kpal/kmer.py:250-271)."""
-    for name in _profile_names(input_handle, names):
-        profile = klib.Profile.from_file(input_handle, name=name)
-        print(name, _fixed(precision, profile.mean), _fixed(precision, profile.std), file=output_handle)
+    """``name mean std`` lines (kpal/kmer.py:250-271), the summaries of a group of profiles from one set call."""
+    for group in _profile_groups(input_handle, _profile_names(input_handle, names)):
+        for profile, stats in zip(group, klib.summaries(group)):
+            print(profile.name, _fixed(precision, stats['mean']), _fixed(precision, stats['std']), file=output_handle)
 
 
 def distribution(input_handle, output_handle, names=None):
@@ -198,7 +206,7 @@ def distribution(input_handle, output_handle, names=None):
 def info(input_handle, output_handle, names=None):
     """Print some information about k-mer profiles.
 
-    (kpal/kmer.py:298-335.)  The five summaries of a profile come from one pass over it on the device."""
+    (kpal/kmer.py:298-335.)  The five summaries of the profiles of a group come from one set call on the device."""
     names = _profile_names(input_handle, names)
 
     def text(value):
@@ -206,18 +214,17 @@ def info(input_handle, output_handle, names=None):
 
     print('File format version:', text(input_handle.attrs['version']), file=output_handle)
     print('Produced by:', text(input_handle.attrs['producer']), file=output_handle)
-    for name in names:
-        profile = klib.Profile.from_file(input_handle, name=name)
-        stats = profile.summary()
-        print('', file=output_handle)
-        print('Profile:', profile.name, file=output_handle)
-        print('- k-mer length:', str(profile.length), '({0} k-mers)'.format(profile.number), file=output_handle)
-        print('- Zero counts:', str(profile.number - stats['non_zero']), file=output_handle)
-        print('- Non-zero counts:', str(stats['non_zero']), file=output_handle)
-        print('- Sum of counts:', str(stats['total']), file=output_handle)
-        print('- Mean of counts:', '{0:.3f}'.format(stats['mean']), file=output_handle)
-        print('- Median of counts:', '{0:.3f}'.format(stats['median']), file=output_handle)
-        print('- Standard deviation of counts:', '{0:.3f}'.format(stats['std']), file=output_handle)
+    for group in _profile_groups(input_handle, names):
+        for profile, stats in zip(group, klib.summaries(group)):
+            print('', file=output_handle)
+            print('Profile:', profile.name, file=output_handle)
+            print('- k-mer length:', str(profile.length), '({0} k-mers)'.format(profile.number), file=output_handle)
+            print('- Zero counts:', str(profile.number - stats['non_zero']), file=output_handle)
+            print('- Non-zero counts:', str(stats['non_zero']), file=output_handle)
+            print('- Sum of counts:', str(stats['total']), file=output_handle)
+            print('- Mean of counts:', '{0:.3f}'.format(stats['mean']), file=output_handle)
+            print('- Median of counts:', '{0:.3f}'.format(stats['median']), file=output_handle)
+            print('- Standard deviation of counts:', '{0:.3f}'.format(stats['std']), file=output_handle)
 
 
 def get_count(input_handle, output_handle, word, names=None):
