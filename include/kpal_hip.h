@@ -379,7 +379,30 @@ int kpal_cross_profile_distance(kpal_ctx *ctx, int k, int Q, const int64_t *cons
 int kpal_cross_profile_distance_device(kpal_ctx *ctx, int k, int Q, const int64_t *dev_left /* Q x 4^k */, int R,
                                        const int64_t *dev_right /* R x 4^k */, const kpal_distance_options *opt,
                                        double *out /* host, Q x R, row-major */);
-/* The two device entries above for an option set WITH dynamic smoothing in a number of launches that does not grow with the
+/* The n nearest right profiles of every left profile under the distance of kpal_cross_profile_distance: for row q the n
+ * smallest of out[q, :] in the order of kdistlib.nearest -- ascending distance, equal distances by the lower index, NaN last,
+ * NaNs by index -- without the Q x R rectangle ever existing on the host.  The rectangle is cut into tiles over both sides
+ * (nearest_plan.hpp: every tile passes the 32-bit limit of the partials and keeps its workspace within 4 GiB), so no Q and R
+ * is refused for its size; a tile is the launches of kpal_cross_profile_distance_device, a kernel that finishes its distances
+ * on the device (the doubles that entry returns, bit for bit) and one that merges them into the n best of every row, which
+ * stay on the device over a band of tiles: a number of launches per tile that does not grow with the tile, and Q x n values
+ * downloaded.  1 <= n <= KPAL_NEAREST_MAX.
+ *   dist_inout / index_inout (host, Q x n, row-major): columns [0, have) hold the running best of earlier calls over earlier
+ * chunks of the right side, in order; on return columns [0, min(n, have + R)) are the best of those and of this call's
+ * right_first + r, in order, and the other columns NaN / -1.  The indices of one row must be distinct.  have = 0 starts.
+ *   tile_q / tile_r > 0 cap the sides of a tile (0: the plan's choice); they only shrink tiles.
+ * Option sets with do_smooth compute every tile with kpal_cross_smooth_distance_device into a host buffer of one tile and
+ * select on the host, under the same order.  Inputs are not written; the workspace is the context's.  KPAL_E_INVALID: what
+ * kpal_cross_profile_distance_device refuses, n < 1, n > KPAL_NEAREST_MAX, have < 0, have > n, a negative tile cap. */
+#define KPAL_NEAREST_MAX 64
+int kpal_cross_nearest(kpal_ctx *ctx, int k, int Q, const int64_t *const *host_left, int R,
+                       const int64_t *const *host_right, const kpal_distance_options *opt, int n, int64_t right_first,
+                       int have, int tile_q, int tile_r, double *dist_inout, int64_t *index_inout);
+int kpal_cross_nearest_device(kpal_ctx *ctx, int k, int Q, const int64_t *dev_left /* Q x 4^k */, int R,
+                              const int64_t *dev_right /* R x 4^k */, const kpal_distance_options *opt, int n,
+                              int64_t right_first, int have, int tile_q, int tile_r,
+                              double *dist_inout /* host, Q x n */, int64_t *index_inout /* host, Q x n */);
+/* kpal_profile_distance_matrix_device and kpal_cross_profile_distance_device for an option set WITH dynamic smoothing in a number of launches that does not grow with the
  * number of pairs.  The reference collapses a node iff min(f(left quarters), f(right quarters)) <= threshold (kdistlib.py:
  * 99-100), that is iff f(left quarters) <= threshold OR f(right quarters) <= threshold: a flag per profile.  Every profile is
  * balanced once and gets one pyramid of node sums and node codes (k + 1 launches for all profiles); a pair's distance is the

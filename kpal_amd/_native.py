@@ -37,6 +37,7 @@ class DistanceOptions(ctypes.Structure):
 
 
 _optp = ctypes.POINTER(DistanceOptions)
+NEAREST_MAX = 64   # KPAL_NEAREST_MAX: the most candidates per row kpal_cross_nearest selects on the device
 
 
 class FastqOptions(ctypes.Structure):
@@ -138,6 +139,11 @@ SIGNATURES = {
                                                    ctypes.POINTER(_vp), _optp, _f64p]),
     'kpal_cross_profile_distance_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, _optp,
                                                           _f64p]),
+    'kpal_cross_nearest': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp), ctypes.c_int, ctypes.POINTER(_vp),
+                                          _optp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f64p,
+                                          _i64p]),
+    'kpal_cross_nearest_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, _optp, ctypes.c_int,
+                                                 ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f64p, _i64p]),
     'kpal_profile_distance': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _optp, _f64p]),
     'kpal_profile_distance_device': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _optp, _f64p]),
     'kpal_dynamic_smooth': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_double]),
@@ -767,6 +773,43 @@ class Context(object):
         _check(self._L.kpal_cross_smooth_distance_device(self._h, int(k), int(Q), _vp(dev_left), int(R), _vp(dev_right),
                                                          ctypes.byref(options), out.ctypes.data_as(_f64p)))
         return out
+
+    @staticmethod
+    def _nearest_buffers(Q, n, dist, index):
+        if dist is None:
+            dist = np.full((int(Q), int(n)), np.nan, dtype=np.float64)
+            index = np.full((int(Q), int(n)), -1, dtype=np.int64)
+        if (dist.shape != (int(Q), int(n)) or index.shape != dist.shape or dist.dtype != np.float64 or index.dtype != np.int64
+                or not dist.flags['C_CONTIGUOUS'] or not index.flags['C_CONTIGUOUS']):
+            raise ValueError('dist / index must be C-contiguous float64 / int64 arrays of shape (Q, n)')
+        return dist, index
+
+    def cross_nearest(self, left, right, k, options, n, right_first=0, have=0, tile_q=0, tile_r=0, dist=None, index=None):
+        """cross_nearest_device for lists of int64[4**k] host vectors."""
+        la, ra = [_as_i64(p) for p in left], [_as_i64(p) for p in right]
+        for a in la + ra:
+            if a.size != 4 ** k:
+                raise ValueError('profile length %d != 4**%d' % (a.size, k))
+        Q, R = len(la), len(ra)
+        dist, index = self._nearest_buffers(Q, n, dist, index)
+        lp = (_vp * Q)(*[a.ctypes.data for a in la])
+        rp = (_vp * R)(*[a.ctypes.data for a in ra])
+        _check(self._L.kpal_cross_nearest(self._h, int(k), Q, lp, R, rp, ctypes.byref(options), int(n), int(right_first), int(have),
+                                          int(tile_q), int(tile_r), dist.ctypes.data_as(_f64p), index.ctypes.data_as(_i64p)))
+        return dist, index
+
+    def cross_nearest_device(self, k, Q, dev_left, R, dev_right, options, n, right_first=0, have=0, tile_q=0, tile_r=0,
+                             dist=None, index=None):
+        """The ``n`` (<= NEAREST_MAX) nearest of the R consecutive right tables for each of the Q consecutive left tables under a
+        DistanceOptions, selected on the device in tiles -> (dist float64[Q, n], index int64[Q, n]) in the order of
+        ``kdistlib.nearest``, NaN / -1 behind min(n, have + R) entries.  ``dist`` / ``index``: the result of an earlier call over
+        an earlier chunk of the right side, whose first ``have`` columns are merged in (and which are written); indices are
+        ``right_first + r``.  ``tile_q`` / ``tile_r`` cap the tile sides (0: the library's plan)."""
+        dist, index = self._nearest_buffers(Q, n, dist, index)
+        _check(self._L.kpal_cross_nearest_device(self._h, int(k), int(Q), _vp(dev_left), int(R), _vp(dev_right), ctypes.byref(options),
+                                                 int(n), int(right_first), int(have), int(tile_q), int(tile_r),
+                                                 dist.ctypes.data_as(_f64p), index.ctypes.data_as(_i64p)))
+        return dist, index
 
     # -- ProfileDistance with options ------------------------------------------------------------
     def profile_distance(self, left, right, k, options):

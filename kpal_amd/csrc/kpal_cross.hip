@@ -39,8 +39,8 @@ static int upload_set(kpal_ctx *ctx, int64_t *dst, int count, uint64_t n, const 
 }
 
 // The left and the right set of a rectangle, one behind the other in scratch[0].
-static int upload_rectangle(kpal_ctx *ctx, uint64_t n, int Q, const int64_t *const *host_left, int R, const int64_t *const *host_right,
-                            int64_t **dl, int64_t **dr)
+int upload_rectangle(kpal_ctx *ctx, uint64_t n, int Q, const int64_t *const *host_left, int R, const int64_t *const *host_right,
+                     int64_t **dl, int64_t **dr)
 {
     CHK(ensure(ctx, ctx->scratch[0], ((size_t)Q + (size_t)R) * n * 8));
     *dl = (int64_t *)ctx->scratch[0].p;
@@ -50,7 +50,7 @@ static int upload_rectangle(kpal_ctx *ctx, uint64_t n, int Q, const int64_t *con
 }
 
 // Balanced copies of `count` consecutive tables at `dst` (one launch_balance per profile).
-static int balance_set(kpal_ctx *ctx, int k, int count, const int64_t *src, int64_t *dst)
+int balance_set(kpal_ctx *ctx, int k, int count, const int64_t *src, int64_t *dst)
 {
     const uint64_t n = 1ULL << (2 * k);
     for (int p = 0; p < count; ++p) CHK(launch_balance(ctx, k, src + (uint64_t)p * n, dst + (uint64_t)p * n));
@@ -129,8 +129,9 @@ static int gram_euclidean(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof,
     return KPAL_OK;
 }
 
-// ... of a rectangle, from the fp64 dot products of cross_gram_kernel and the norms of cross_norm_kernel: the same rule.
-static int cross_gram_euclidean(kpal_ctx *ctx, const CrossSets &c, double *out, bool *exact)
+// The fp64 dot products of cross_gram_kernel and the norms of cross_norm_kernel of a rectangle, as workgroup partials in
+// ctx->partials: lay->groups groups of lay->gx, the dots at cross_gram_index, the Q + R norms behind them.
+int cross_gram_launch(kpal_ctx *ctx, const CrossSets &c, CrossGramLayout *lay)
 {
     const int blocksQ = (c.Q + 63) / 64, blocksR = (c.R + 63) / 64;
     const uint32_t nblocks = (uint32_t)blocksQ * (uint32_t)blocksR, nprof = (uint32_t)c.Q + (uint32_t)c.R;
@@ -141,8 +142,20 @@ static int cross_gram_euclidean(kpal_ctx *ctx, const CrossSets &c, double *out, 
     Partial *pp = (Partial *)ctx->partials.p;
     LAUNCH(ctx, "cross_gram", cross_gram_kernel, dim3(nblocks * gx), dim3(256), c, gx, blocksR, pp);
     LAUNCH(ctx, "cross_norm", cross_norm_kernel, dim3(nprof * gx), dim3(256), c, gx, pp + dots * gx);
+    *lay = CrossGramLayout{blocksR, gx, dots, groups};
+    return KPAL_OK;
+}
+
+// ... of a rectangle, from those dot products and norms: the same rule.
+static int cross_gram_euclidean(kpal_ctx *ctx, const CrossSets &c, double *out, bool *exact)
+{
+    CrossGramLayout lay;
+    CHK(cross_gram_launch(ctx, c, &lay));
+    const int blocksR = lay.blocksR;
+    const uint32_t nprof = (uint32_t)c.Q + (uint32_t)c.R;
+    const size_t dots = lay.dots;
     std::vector<Partial> res;
-    CHK(finish_partials(ctx, (uint32_t)groups, gx, res));
+    CHK(finish_partials(ctx, (uint32_t)lay.groups, lay.gx, res));
     for (uint32_t p = 0; p < nprof; ++p)
         if (!gram_exact(res[dots + p].s)) {
             *exact = false;
@@ -166,10 +179,11 @@ static int launch_cross(kpal_ctx *ctx, const char *name, bool staged, const type
 // Every pair of c for a plain metric: the register-tile kernel, or (staged: c.n is a multiple of 64) the LDS-staged ones --
 // with `recip` the reciprocal form of 'prod' / 'sum' first, valid while every count is below 2^16 ('prod') or fits the table
 // ('sum'): the kernel says whether it saw a larger one, and the pair-of-counts kernel then runs after all.  res: the reduced
-// partial of pair (i, j) at cross_slot(i, j); the triangle's launches keep the names they always had.
-static int cross_pairs(kpal_ctx *ctx, const CrossSets &c, int metric, bool staged, bool recip, bool allreduce, std::vector<Partial> &res)
+// partial of pair (i, j) at cross_slot(i, j); the triangle's launches keep the names they always had.  cross_pairs_launch:
+// the kernels alone -- the workgroup partials lie in ctx->partials, g->slots groups of g->gx.
+int cross_pairs_launch(kpal_ctx *ctx, const CrossSets &c, int metric, bool staged, bool recip, CrossGrid *grid)
 {
-    const CrossGrid g = cross_grid(ctx->num_cu, c, staged);
+    const CrossGrid g = *grid = cross_grid(ctx->num_cu, c, staged);
     if (partials_too_many(g.slots, g.gx)) return set_err(KPAL_E_INVALID, "%d x %d profiles are too many for one call", c.Q, c.R);
     CHK(ensure(ctx, ctx->partials, g.slots * g.gx * sizeof(Partial)));
     Partial *pp = (Partial *)ctx->partials.p;
@@ -191,6 +205,13 @@ static int cross_pairs(kpal_ctx *ctx, const CrossSets &c, int metric, bool stage
         else if (metric == KPAL_PAIRWISE_SUM) CHK(launch_cross<PlainAcc<1>>(ctx, name, staged, o, g, pp));
         else CHK(launch_cross<PlainAcc<2>>(ctx, name, staged, o, g, pp));
     }
+    return KPAL_OK;
+}
+
+static int cross_pairs(kpal_ctx *ctx, const CrossSets &c, int metric, bool staged, bool recip, bool allreduce, std::vector<Partial> &res)
+{
+    CrossGrid g;
+    CHK(cross_pairs_launch(ctx, c, metric, staged, recip, &g));
     return finish_partials(ctx, (uint32_t)g.slots, g.gx, res, allreduce);
 }
 
@@ -332,15 +353,16 @@ static int launch_cross_option_metric(kpal_ctx *ctx, const char *name, bool stag
 }
 
 // Every pair of c (c.tri: pairs below the diagonal only) for a batched option set -- no smoothing, not plain -- from tables
-// that are already balanced.  out: Q x R row-major, or the lower triangle in distance_matrix order.
-static int cross_option_core(kpal_ctx *ctx, const CrossSets &c, const kpal_distance_options *opt, double *out)
+// that are already balanced.  cross_option_launch: the kernels alone -- the workgroup partials of the option_nacc(metric)
+// accumulators lie in ctx->partials, accumulator a of a pair at a * g->slots + its slot, g->gx of each.
+int cross_option_launch(kpal_ctx *ctx, const CrossSets &c, const kpal_distance_options *opt, CrossGrid *grid)
 {
     const bool scaled = opt->do_scale != 0, positive = opt->do_positive != 0, tri = c.tri != 0;
     const bool staged = cross_staged(c.Q, c.R, c.n);
-    const CrossGrid g = cross_grid(ctx->num_cu, c, staged);
+    const CrossGrid g = *grid = cross_grid(ctx->num_cu, c, staged);
     const uint64_t slots = g.slots;
     const uint32_t gx = g.gx;
-    const uint32_t nacc = option_nacc(opt->metric), nacc_max = option_nacc_max(opt->metric, scaled, positive);
+    const uint32_t nacc_max = option_nacc_max(opt->metric, scaled, positive);
     if (partials_too_many(slots * nacc_max, gx)) return set_err(KPAL_E_INVALID, "cross distance: %d x %d profiles are too many for one call", c.Q, c.R);
     const uint32_t nprof = tri ? (uint32_t)c.Q : (uint32_t)c.Q + (uint32_t)c.R;
     const uint32_t gxt = option_totals_gx(ctx->num_cu, nprof, c.n);
@@ -364,8 +386,19 @@ static int cross_option_core(kpal_ctx *ctx, const CrossSets &c, const kpal_dista
     case KPAL_EUCLIDEAN: CHK(launch_cross_option_metric<2>(ctx, name, staged, scaled, positive, o, g, pp)); break;
     default: CHK(launch_cross_option_metric<3>(ctx, name, staged, scaled, positive, o, g, pp)); break;
     }
+    return KPAL_OK;
+}
+
+// out: Q x R row-major, or the lower triangle in distance_matrix order.
+static int cross_option_core(kpal_ctx *ctx, const CrossSets &c, const kpal_distance_options *opt, double *out)
+{
+    const bool scaled = opt->do_scale != 0, tri = c.tri != 0;
+    CrossGrid g;
+    CHK(cross_option_launch(ctx, c, opt, &g));
+    const uint64_t slots = g.slots;
+    const uint32_t nacc = option_nacc(opt->metric);
     std::vector<Partial> res;
-    CHK(finish_partials(ctx, (uint32_t)(slots * nacc), gx, res));
+    CHK(finish_partials(ctx, (uint32_t)(slots * nacc), g.gx, res));
     auto value = [&](int i, int j) -> double {   // (accumulators 1 and 2 exist for the cosine only: p0 again, unread)
         const size_t slot = cross_slot(c, g.sideR, i, j);
         return finish_distance(opt->metric, scaled, res[slot], res[(nacc / 2) * slots + slot], res[(nacc - 1) * slots + slot]);

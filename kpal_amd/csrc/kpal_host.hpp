@@ -5,7 +5,8 @@
 // kpal_quads.hip / kpal_quads2.hip: the quad record pipelines, planned by quad_plan.hpp; kpal_vec.hip: one vector -- balance,
 // split, summaries, merge, shrink; kpal_sets.hip: the summaries and the strand balance of a whole set of vectors, planned by
 // stat_plan.hpp; kpal_pair.hip: the distance of one pair, plain and with options; kpal_cross.hip: the distances
-// of sets of profiles, triangle and rectangle, planned by matrix_plan.hpp; kpal_multi.hip: multi-GPU entry points over RCCL.)
+// of sets of profiles, triangle and rectangle, planned by matrix_plan.hpp; kpal_nearest.hip: the nearest n of a rectangle,
+// tiled by nearest_plan.hpp; kpal_multi.hip: multi-GPU entry points over RCCL.)
 #pragma once
 #include "../../include/kpal_hip.h"
 
@@ -196,6 +197,7 @@ struct kpal_ctx {
     DevBuf scratch[4];
     DevBuf partials, result;
     DevBuf opt_l, opt_r, opt_levels, opt_profiles;   // ProfileDistance option pipeline
+    DevBuf near_dist, near_best;             // kpal_nearest.hip: the finished distances of one tile (and the word of the Gram test behind them); the n best of a band's rows
     // the canonical tile pairs of the LDS-tiled balance kernels for the k they were last built for (kpal_vec.hip: canon_tiles)
     DevBuf canon;
     std::vector<uint32_t> canon_host;
@@ -374,6 +376,19 @@ int profile_distance_pair(kpal_ctx *ctx, int k, const int64_t *dl, const int64_t
                           double *out);   // kpal_pair.hip: the option pipeline of one pair of 16-byte aligned device tables (balanced: do_balance is not applied again)
 int distance_matrix_core(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof, int metric, double *out_lower, bool allreduce,
                          int tiled = -1);   // kpal_cross.hip (tiled: -1 decided from n; 0 / 1 agreed between the ranks)
+// kpal_cross.hip: the launches of the rectangle cores up to where their host loops begin -- the workgroup partials are left in
+// ctx->partials for finish_partials, or for kpal_nearest.hip, which reduces and finishes them on the device
+struct CrossGramLayout {
+    int blocksR;
+    uint32_t gx;
+    size_t dots, groups;   // reduced: the dot of (q, r) at cross_gram_index(blocksR, q, r), the Q + R norms from `dots` on
+};
+int balance_set(kpal_ctx *ctx, int k, int count, const int64_t *src, int64_t *dst);
+int upload_rectangle(kpal_ctx *ctx, uint64_t n, int Q, const int64_t *const *host_left, int R, const int64_t *const *host_right,
+                     int64_t **dl, int64_t **dr);   // the left and the right set, one behind the other in scratch[0]
+int cross_gram_launch(kpal_ctx *ctx, const CrossSets &c, CrossGramLayout *lay);
+int cross_pairs_launch(kpal_ctx *ctx, const CrossSets &c, int metric, bool staged, bool recip, CrossGrid *grid);
+int cross_option_launch(kpal_ctx *ctx, const CrossSets &c, const kpal_distance_options *opt, CrossGrid *grid);
 int reduce_partials(kpal_ctx *ctx, const Partial *partials, uint32_t nq, uint32_t nblocks, Partial *out);   // kpal_vec.hip: nq groups of nblocks device partials added in a fixed order
 int finish_partials(kpal_ctx *ctx, uint32_t nq, uint32_t nblocks, std::vector<Partial> &out, bool allreduce = false);   // kpal_vec.hip: reduce nq groups of nblocks partials, fetch them
 double finish_value(int metric, const Partial &p, int64_t *aux);         // kpal_vec.hip: the distance of one reduced partial of a plain metric (aux: its count / wrapping dot)

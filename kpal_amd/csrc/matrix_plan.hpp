@@ -172,7 +172,7 @@ inline size_t triangle_index(int i, int j) { return (size_t)i * (i - 1) / 2 + j;
 
 // Dot product of profiles i and j in the reduced result of the Gram kernels: block `blk` of 64 x 64 profiles holds 16 tiles of
 // 16 x 16.  Triangle (i >= j): GramPlan's order; rectangle: the blocks row-major over blocksR.
-inline size_t gram_entry(size_t blk, int i, int j)
+KPAL_MATRIX_HD size_t gram_entry(size_t blk, int i, int j)
 {
     return (blk * 16 + (size_t)((i % 64) / 16 * 4 + (j % 64) / 16)) * 256 + (size_t)((i % 16) * 16 + (j % 16));
 }
@@ -181,12 +181,14 @@ inline size_t gram_index(const GramPlan &g, int i, int j)
     const int I = i / 64, J = j / 64;
     return gram_entry(I == J ? (size_t)I : g.nd + (size_t)I * (I - 1) / 2 + J, i, j);
 }
-inline size_t cross_gram_index(int blocksR, int q, int r) { return gram_entry((size_t)(q / 64) * blocksR + (size_t)(r / 64), q, r); }
+KPAL_MATRIX_HD size_t cross_gram_index(int blocksR, int q, int r) { return gram_entry((size_t)(q / 64) * blocksR + (size_t)(r / 64), q, r); }
 
 // ---- finishing ------------------------------------------------------------------------------------------------------------
+// (host and device: the build keeps -ffp-contract=off, and the fp64 divide and square root are correctly rounded on both, so a
+// kernel that finishes a pair -- nearest_kernels.hpp -- gives the bits of the host loops)
 // The distance from the reduced accumulators of a pair: p0 alone, but for the cosine similarity (p0 the dot, p1 / p2 the
 // squared norms).  scaled: the sums were formed in fp64 (.s); else the euclidean and cosine ones are wrapping int64 (.m).
-inline double finish_distance(int metric, bool scaled, const Partial &p0, const Partial &p1, const Partial &p2)
+KPAL_MATRIX_HD double finish_distance(int metric, bool scaled, const Partial &p0, const Partial &p1, const Partial &p2)
 {
     if (metric <= KPAL_PAIRWISE_SUM) return p0.s / (double)(p0.m + 1ULL);   // metrics.py:123
     if (metric == KPAL_EUCLIDEAN) return scaled ? std::sqrt(p0.s) : std::sqrt((double)(int64_t)p0.m);   // metrics.py:135,46
@@ -196,8 +198,8 @@ inline double finish_distance(int metric, bool scaled, const Partial &p0, const 
 }
 
 // Euclidean from the fp64 Gram matrix, valid while every |x|^2 < 2^53 (gram_kernels.hpp): *exact says whether these two are.
-inline bool gram_exact(double norm) { return norm < 9007199254740992.0; }   // 2^53
-inline double gram_distance(double norm_i, double norm_j, double dot, bool *exact)
+KPAL_MATRIX_HD bool gram_exact(double norm) { return norm < 9007199254740992.0; }   // 2^53
+KPAL_MATRIX_HD double gram_distance(double norm_i, double norm_j, double dot, bool *exact)
 {
     *exact = gram_exact(norm_i) && gram_exact(norm_j);
     if (!*exact) return 0.0;

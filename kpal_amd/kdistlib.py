@@ -13,7 +13,9 @@ a user-supplied callable cannot enter a kernel and keeps the reference's NumPy f
 Beyond the reference: :func:`cross_distances` / :func:`cross_distance_matrix` / :func:`nearest` -- the Q x R rectangle of
 distances between a left and a right set of profiles (``kpal_cross_distance_device``; with positive / scale / cosine
 ``kpal_cross_profile_distance_device``; with dynamic smoothing ``kpal_cross_smooth_distance_device``), a fixed number of
-launches per chunk of the right side.
+launches per chunk of the right side.  :func:`nearest_chunks` / :func:`nearest_profiles` -- the n nearest right profiles of
+every left profile without that rectangle on the host (``kpal_cross_nearest_device``: tiled over both sides, finished and
+selected on the device), the left side streamed.
 """
 import numpy as np
 
@@ -336,6 +338,124 @@ def nearest(values, n):
         raise ValueError('nearest needs a two-dimensional array')
     n = max(0, min(int(n), values.shape[1]))
     return np.argsort(values, axis=1, kind='stable')[:, :n]
+
+
+def _left_chunks(profiles, max_bytes):
+    """Lists of consecutive profiles of the iterable ``profiles`` of at most ``max_bytes`` of tables each (never less than one
+    profile).  A chunk that is so far one run of consecutive tables of a device batch ends in front of a device-resident
+    profile that does not continue the run: ``_DeviceSet`` then uses the run where it lies.  Reads one profile ahead."""
+    chunk, size, run = [], 0, None   # run: (context, address) the next table must have to continue the chunk's run
+    for p in profiles:
+        nbytes = 8 * 4 ** p.length
+        at = getattr(p, '_device_counts', lambda: None)()
+        if chunk and (size + nbytes > max_bytes or (run is not None and at is not None and at != run)):
+            yield chunk
+            chunk, size = [], 0
+        run = (at[0], at[1] + nbytes) if at is not None and (not chunk or run == at) else None
+        chunk.append(p)
+        size += nbytes
+    if chunk:
+        yield chunk
+
+
+def _merge_nearest(distances, indices, have, values, first, m):
+    """Columns ``[0, have)`` of ``distances`` / ``indices`` (every index below ``first``) merged with the block ``values`` of
+    right profiles ``first, first + 1, ...`` in the order of :func:`nearest`; returns how many columns are valid now."""
+    rows, count = values.shape
+    all_d = np.concatenate([distances[:, :have], values], axis=1)
+    all_i = np.concatenate([indices[:, :have], np.broadcast_to(np.arange(first, first + count, dtype=np.int64), (rows, count))],
+                           axis=1)
+    keep = min(m, have + count)
+    order = nearest(all_d, keep)    # stable: of equal distances the earlier column, which has the lower index
+    distances[:, :keep] = np.take_along_axis(all_d, order, axis=1)
+    indices[:, :keep] = np.take_along_axis(all_i, order, axis=1)
+    return keep
+
+
+def nearest_chunks(left_profiles, right_profiles, dist, n, max_bytes=None):
+    """The ``n`` nearest of ``right_profiles`` for every profile of ``left_profiles``: a generator of ``(chunk, indices,
+    distances)`` -- a list of consecutive left profiles, and for them an int64 and a float64 array of shape ``(len(chunk),
+    min(n, R))``: row q holds the positions in ``right_profiles`` of the nearest profiles of ``chunk[q]`` in the order of
+    :func:`nearest` (ascending distance, ties by the lower position, NaN last) and ``dist.distance`` to each.
+
+    ``left_profiles`` is any iterable, read once, a chunk of at most ``max_bytes`` of tables (default ``CROSS_MAX_BYTES``, never
+    less than one profile) at a time and at most one profile past the chunk being worked on; a chunk is not referenced by the
+    generator once the caller has come back for the next one, so the device batches behind the profiles of
+    ``Profile.from_fastq_by_record`` are freed as a scan goes.  ``right_profiles`` is a sequence (anything else is made a list):
+    when its tables fit ``max_bytes`` they are made resident once for the whole call, otherwise they are taken in chunks of
+    that size for every chunk of the left side.
+
+    With a ``dist`` made of built-ins over integer profiles of one k, and ``n <= _native.NEAREST_MAX``, the Q x R distances
+    never reach the host: ``kpal_cross_nearest_device`` cuts the rectangle into tiles, finishes every tile's distances on the
+    device and keeps the n best of every row there (dynamic smoothing: tile by tile through a host buffer).  A user-supplied
+    callable, a non-numeric threshold, mixed k, non-integer counts or a larger ``n`` are ``dist.distance`` pair by pair within
+    a chunk and :func:`nearest` over its rows."""
+    n = int(n)
+    if n < 1:
+        raise ValueError('nearest_chunks needs n >= 1')
+    if not (hasattr(right_profiles, '__len__') and hasattr(right_profiles, '__getitem__')):
+        right_profiles = list(right_profiles)
+    return _nearest_chunks(left_profiles, right_profiles, dist, n, CROSS_MAX_BYTES if max_bytes is None else max_bytes)
+
+
+def _nearest_chunks(left_profiles, right, dist, n, max_bytes):
+    R = len(right)
+    m = min(n, R)
+    options = dist._native_options() if n <= _native.NEAREST_MAX else None
+    bounds = cross_chunks(8 * 4 ** right[0].length, R, max_bytes) if R else []
+    whole = list(right[0:R]) if len(bounds) == 1 else None    # the right side when it is resident for the whole call
+    ctx = whole_set = None
+    try:
+        for chunk in _left_chunks(left_profiles, max_bytes):
+            rows, k = len(chunk), chunk[0].length
+            distances = np.full((rows, m), np.nan, dtype=np.float64)
+            indices = np.full((rows, m), -1, dtype=np.int64)
+            fast_left = options is not None and all(p.length == k and _integer_counts(p) for p in chunk)
+            have, lset = 0, None
+            try:
+                for start, stop in bounds:
+                    block = whole if whole is not None else list(right[start:stop])
+                    if fast_left and all(p.length == k and _integer_counts(p) for p in block):
+                        if ctx is None:
+                            ctx = _cross_context(chunk)
+                        if lset is None:
+                            lset = _DeviceSet(ctx, chunk)
+                        if whole is not None and whole_set is None:
+                            whole_set = _DeviceSet(ctx, whole)
+                        rset = whole_set if whole is not None else _DeviceSet(ctx, block)
+                        try:
+                            ctx.cross_nearest_device(k, rows, lset.ptr, stop - start, rset.ptr, options, m, right_first=start,
+                                                     have=have, dist=distances, index=indices)
+                        finally:
+                            if rset is not whole_set:
+                                rset.release()
+                        have = min(m, have + stop - start)
+                    else:
+                        # a mixed-k pair raises what dist.distance raises; other counts keep its formulation
+                        values = np.array([[dist.distance(l, r) for r in block] for l in chunk], dtype=np.float64)
+                        have = _merge_nearest(distances, indices, have, values.reshape(rows, stop - start), start, m)
+                    block = None
+            finally:
+                if lset is not None:
+                    lset.release()
+            yield chunk, indices, distances
+            chunk = lset = None
+    finally:
+        if whole_set is not None:
+            whole_set.release()
+
+
+def nearest_profiles(left_profiles, right_profiles, dist, n, max_bytes=None):
+    """:func:`nearest_chunks` over the whole left side: ``(indices, distances)``, an int64 and a float64 array of shape
+    ``(Q, min(n, R))``."""
+    if not (hasattr(right_profiles, '__len__') and hasattr(right_profiles, '__getitem__')):
+        right_profiles = list(right_profiles)
+    m = min(max(int(n), 0), len(right_profiles))
+    indices, distances = [np.zeros((0, m), dtype=np.int64)], [np.zeros((0, m), dtype=np.float64)]
+    for _, i, d in nearest_chunks(left_profiles, right_profiles, dist, n, max_bytes=max_bytes):
+        indices.append(i)
+        distances.append(d)
+    return np.concatenate(indices, axis=0), np.concatenate(distances, axis=0)
 
 
 def cross_distance_matrix(left_profiles, right_profiles, output, precision, dist, max_bytes=None):

@@ -390,6 +390,9 @@ def cross(input_handle_left, input_handle_right, output_handle, names_left=None,
         raise ValueError('--nearest needs a positive number')
     dist = _profile_distance(distance_function, pairwise, custom_pairwise, do_smooth, summary, custom_summary,
                              threshold, do_scale, down, do_positive, do_balance)
+    if nearest is not None:
+        _cross_nearest(input_handle_left, names_left, input_handle_right, names_right, output_handle, dist, precision, nearest)
+        return
     left = [klib.Profile.from_file(input_handle_left, name=name) for name in names_left]
 
     def right():
@@ -401,13 +404,53 @@ def cross(input_handle_left, input_handle_right, output_handle, names_left=None,
 
     if any(profile.length != left[0].length for profile in left):
         raise ValueError(LENGTH_ERROR)
-    if nearest is None:
-        kdistlib.cross_distance_matrix(left, right(), output_handle, precision, dist)
-        return
-    values = kdistlib.cross_distances(left, right(), dist)
-    for q, row in enumerate(kdistlib.nearest(values, nearest)):
-        for r in row:
-            print(names_left[q], names_right[r], _fixed(precision, values[q, r]), file=output_handle)
+    kdistlib.cross_distance_matrix(left, right(), output_handle, precision, dist)
+
+
+class _FileProfiles(object):
+    """The profiles ``names`` of an open k-mer file as a sequence that reads a profile when it is asked for it; ``lengths``:
+    a one-element list the first profile read puts its k-mer length in -- a profile of another length is LENGTH_ERROR."""
+
+    def __init__(self, handle, names, lengths):
+        self.handle, self.names, self.lengths = handle, names, lengths
+
+    def __len__(self):
+        return len(self.names)
+
+    def _read(self, name):
+        profile = klib.Profile.from_file(self.handle, name=name)
+        if not self.lengths:
+            self.lengths.append(profile.length)
+        if profile.length != self.lengths[0]:
+            raise ValueError(LENGTH_ERROR)
+        return profile
+
+    def __getitem__(self, item):
+        if isinstance(item, slice):
+            return [self._read(name) for name in self.names[item]]
+        return self._read(self.names[item])
+
+
+def _cross_nearest(input_handle_left, names_left, input_handle_right, names_right, output_handle, dist, precision, nearest):
+    """``left right distance`` lines of the ``nearest`` closest right profiles of every left profile.  The left file is read in
+    groups (``_profile_groups``) and the right file chunk by chunk when it does not fit the device at once; the distances are
+    selected on the device (``kdistlib.nearest_chunks``), so no Q x R rectangle is built."""
+    lengths = []
+
+    def left():
+        for group in _profile_groups(input_handle_left, names_left):
+            for profile in group:
+                if not lengths:
+                    lengths.append(profile.length)
+                if profile.length != lengths[0]:
+                    raise ValueError(LENGTH_ERROR)
+                yield profile
+
+    right = _FileProfiles(input_handle_right, names_right, lengths)
+    for chunk, indices, distances in kdistlib.nearest_chunks(left(), right, dist, nearest):
+        for profile, row, values in zip(chunk, indices, distances):
+            for r, value in zip(row, values):
+                print(profile.name, names_right[r], _fixed(precision, value), file=output_handle)
 
 
 def _parsers():
