@@ -5,7 +5,8 @@
 // take.  kpal_text.hip drives both with its pinned staging buffers and queues the copies and kernels per chunk;
 // tests/native/fasta_host_check.cpp drives the same classes with malloc'ed buffers under AddressSanitizer / ThreadSanitizer and
 // compares the chunks with the source, and the FASTA chunks, flattened by a restatement of the kernels' rules, with the text
-// flattened in one piece.
+// flattened in one piece.  The by-record scan of a file (kpal_records.hip) reads through FaSource and fa_read as well: its
+// gather / cut / carry loop is RecordScan in record_scan.hpp, with tests/native/record_scan_check.cpp as its own check.
 //
 // A FASTA chunk may be cut ANYWHERE.  What the kernels cannot see from inside a chunk travels with it:
 //   * state         what the chunk's first byte continues (0 line start, 1 inside a header line, 2 inside a sequence line);

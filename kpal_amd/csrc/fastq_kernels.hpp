@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "fasta_kernels.hpp"
+#include "fastq_mask.hpp"
 
 namespace kpal {
 
@@ -157,11 +158,6 @@ __device__ __forceinline__ uint64_t fq_block_exclusive_sum(uint32_t v, uint64_t 
     __syncthreads();
     return before;
 }
-
-struct FqMask {
-    int min_quality;   // < 0: no mask
-    int offset;        // 33 or 64
-};
 
 // Classify the thread's 16 bytes: bit j of `keep` set iff byte j is emitted, out[j] its value.  line0: the line byte i0 is in.
 // err != nullptr: report quality bytes outside [offset, '~'] under the mask (the first pass does, the scatter does not).

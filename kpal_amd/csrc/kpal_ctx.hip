@@ -1,8 +1,6 @@
 // kpal_ctx.hip -- errors, context, device memory helpers and the per-kernel timing API of the C-ABI.
 #include "kpal_host.hpp"
 
-#include <unistd.h>
-
 // ----------------------------------------------------------------------------------------------
 // errors
 // ----------------------------------------------------------------------------------------------
@@ -192,7 +190,6 @@ KPAL_API void kpal_ctx_destroy(kpal_ctx *ctx)
     if (ctx->fa_nflat_host) (void)hipHostFree(ctx->fa_nflat_host);
     if (ctx->fq_status_host) (void)hipHostFree(ctx->fq_status_host);
     if (ctx->fq_ev) (void)hipEventDestroy(ctx->fq_ev);
-    if (ctx->rec_fd >= 0) (void)close(ctx->rec_fd);
     for (void *p : ctx->host_allocs) (void)hipHostFree(p);
     for (int i = 0; i < 2; ++i) {
         if (ctx->pinned[i]) (void)hipHostFree(ctx->pinned[i]);
@@ -206,7 +203,7 @@ KPAL_API void kpal_ctx_destroy(kpal_ctx *ctx)
     for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-    delete ctx;
+    delete ctx;   // (an open by-record scan closes its file: RecordScan)
 }
 
 KPAL_API int kpal_sync(kpal_ctx *ctx)

@@ -27,6 +27,8 @@
 #include "host_pool.hpp"
 #include "quad_plan.hpp"
 #include "matrix_plan.hpp"
+#include "fastq_mask.hpp"
+#include "record_scan.hpp"
 
 #define KPAL_API extern "C" __attribute__((visibility("default")))
 
@@ -106,6 +108,16 @@ struct QuadFinalize {
     void clear() { pending = fresh = false; }
 };
 
+// The open by-record scan of a file (kpal_fasta_records_file_*): the range and the unfinished record carried between pieces
+// (record_scan.hpp) and, when the scan is one of FASTQ reads (kpal_fastq_records_file_open), its mask and the records its
+// pieces have indexed so far.
+struct RecordFileScan {
+    RecordScan scan;
+    bool fastq = false;
+    FqMask mask = {-1, 33};
+    uint64_t records = 0;
+};
+
 struct kpal_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -158,14 +170,8 @@ struct kpal_ctx {
     DevBuf rec_raw, rec_flat, rec_meta, rec_starts, rec_hdr;
     std::vector<uint64_t> rec_starts_host, rec_hdr_host;
     uint64_t rec_n = 0, rec_nf = 0;
-    // ... over a file the library reads itself (kpal_fasta_records_file_*): the open range, the unfinished record carried between pieces
-    int rec_fd = -1;
-    uint64_t rec_pos = 0, rec_end = 0, rec_piece_at = 0;
-    std::vector<uint8_t> rec_carry;
-    // ... the scan is one of FASTQ reads (kpal_fastq_records_file_open): its mask and the records its pieces have indexed so far
-    bool rec_fastq = false;
-    int rec_fq_min_quality = -1, rec_fq_offset = 33;
-    uint64_t rec_fq_records = 0;
+    // ... over a file the library reads itself (kpal_fasta_records_file_*)
+    RecordFileScan rec_scan;
     // ... cut into sliding windows (kpal_fasta_windows_*): first window and first tile of every record (R + 1 values each; on
     // the device one behind the other) for the (window, step) last asked for -- a new record index clears them -- and the
     // tile tables of the call in flight
@@ -181,7 +187,7 @@ struct kpal_ctx {
     // ... and the record a count's last FASTQ feed left unfinished (count_end_text ends it), with that feed's mask options
     std::vector<uint8_t> fq_carry;
     uint64_t fq_records = 0;                 // records of this count finished so far (error messages name record fq_records + r + 1)
-    int fq_min_quality = -1, fq_offset = 33;
+    FqMask fq_mask = {-1, 33};
     bool fq_open = false;                    // a FASTQ feed happened since kpal_count_begin or the last end of the text: count_end_text ends it
     std::vector<void *> host_allocs;         // kpal_host_alloc buffers still owned by callers (released with the context at the latest)
     size_t fa_chunk = kStage;                // text bytes per chunk (KPAL_FASTA_CHUNK: tests put the seams everywhere)
@@ -350,7 +356,6 @@ int quad_choose_steps(kpal_ctx *ctx, const Span &s, uint32_t *load, int buckets,
                       int *steps_out, std::vector<double> *fine = nullptr);   // kpal_quads.hip: sample a piece; ctx->tiles.hot_rows and the level-1 size (or kQuadsUseChunked)
 int quad2_finalize(kpal_ctx *ctx, bool balance);                          // kpal_quads2.hip: no-op unless a finalisation is pending
 int quad2_resolve_fresh(kpal_ctx *ctx);                                   // kpal_quads2.hip: a FRESH piece whose lists overflowed is counted again (the fed buffer is read)
-namespace kpal { struct FaSource; }   // fasta_host.hpp
 Span make_span(const uint8_t *addr, size_t n, size_t halo);               // kpal_count.hip: the k-mers ending in [addr, addr + n), `halo` readable bytes of the same feed left of addr
 int count_device_range(kpal_ctx *ctx, const uint8_t *addr, size_t n, size_t halo, int strategy = -1, size_t batch_bytes = 0);   // kpal_count.hip: a device range into the running count (strategy / batch_bytes: its own re-counts only)
 int ensure_pinned(kpal_ctx *ctx);                                         // kpal_count.hip: the two pinned staging buffers exist
@@ -361,8 +366,8 @@ int fa_flatten(kpal_ctx *ctx, const uint8_t *raw, uint64_t m, int state, int tai
                void **rest = nullptr);                                    // kpal_text.hip: the FASTA flattening of raw[0, m) into flat
 int open_text_range(const char *path, uint64_t begin, uint64_t end, FaSource &src);   // kpal_text.hip: a byte range of a regular file, opened for sequential reading
 // kpal_text.hip: the FASTQ tokeniser (fastq_kernels.hpp is compiled there alone), for the count path and the record index
-int fq_mask_options(const kpal_fastq_options *opt, int *min_quality, int *offset);   // the mask of a FASTQ call, checked (min_quality -1: none)
-int fq_tokenise(kpal_ctx *ctx, const uint8_t *raw, uint64_t n, bool fin, int min_quality, int offset, uint8_t *flat);   // one FASTQ chunk on the device -> flat stream, newline positions (fq_pos), status words
+int fq_mask_options(const kpal_fastq_options *opt, FqMask &m);           // the mask of a FASTQ call, checked (min_quality -1: none)
+int fq_tokenise(kpal_ctx *ctx, const uint8_t *raw, uint64_t n, bool fin, FqMask m, uint8_t *flat);   // one FASTQ chunk on the device -> flat stream, newline positions (fq_pos), status words
 int fq_tokenise_wait(kpal_ctx *ctx, uint64_t records, const unsigned long long **status);   // the status words of that chunk on the host; a malformed record is the error
 int fq_title_offsets(kpal_ctx *ctx, uint64_t R, uint64_t *dev_title);    // where the title lines of the R records that chunk finishes begin (device, queued)
 int fq_chunk_too_long(uint64_t records);                                  // kpal_text.hip: the error of a FASTQ chunk of 4 GiB

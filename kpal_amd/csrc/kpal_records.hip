@@ -1,15 +1,15 @@
 // kpal_records.hip -- one profile per record or per sliding window of a FASTA text, per read or per window of a read of a FASTQ
 // text: kpal_count_records, the record index over memory and over a file the library reads itself (kpal_fasta_records_*,
-// kpal_fastq_records_*: one index, filled by either format), the sliding windows (kpal_fasta_windows_*).
+// kpal_fastq_records_*: one index, filled by either format), the sliding windows (kpal_fasta_windows_*).  The scan of a file
+// -- gather, cut, index, carry -- is RecordScan (record_scan.hpp: free of HIP, driven under sanitizers by
+// tests/native/record_scan_check.cpp); this unit gives it the pinned staging buffer and the device index of either format.
 #include "kpal_host.hpp"
 
 #include "count_kernels.hpp"
 #include "count_plan.hpp"
 #include "fasta_kernels.hpp"
-#include "fasta_host.hpp"
+#include "record_scan.hpp"
 #include "window_kernels.hpp"
-
-#include <unistd.h>
 
 // one table per record: the k-mers of `s` into out[r], r the record (of the n that begin at starts[0 .. n]) their last byte lies in
 static int launch_count_records(kpal_ctx *ctx, int k, const Span &s, const uint64_t *starts, uint32_t n, unsigned long long *out)
@@ -84,6 +84,36 @@ static void records_index_clear(kpal_ctx *ctx)
     ctx->rec_hdr_host.clear();
 }
 
+// The end of both record indexes.  The caller has flattened the text into flat[0, nf), found R records in it and queued their R
+// header offsets into rec_hdr.  Here the record starts of the stream -- its '\n' bytes -- are counted, compared with R and only
+// then listed (the list has room for R of them and nf behind them); both lists come to the host and the index is the
+// context's.  offs, marks: scratch of one offset (+ 1) and one mark per kFaBlockBytes of the stream.  kIndexMismatch: the
+// stream holds *seps record starts, not R -- the caller says so in its own words; the context holds no index then.
+constexpr int kIndexMismatch = 1;
+static int records_index_finish(kpal_ctx *ctx, const uint8_t *flat, uint64_t nf, uint64_t R, uint64_t *offs, uint32_t *marks, uint64_t *seps)
+{
+    CHK(ensure(ctx, ctx->rec_starts, (size_t)(R + 1) * 8));
+    const uint32_t fblocks = (uint32_t)((nf + kFaBlockBytes - 1) / kFaBlockBytes);
+    LAUNCH(ctx, "fa_mark_count", (fa_mark_count_kernel<0>), dim3(fblocks), dim3(kFaThreads), flat, nf, marks);
+    LAUNCH(ctx, "fa_offset", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)marks, fblocks, offs);
+    *seps = 0;
+    HIPCHK(hipMemcpyAsync(seps, offs + fblocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (*seps != R) return kIndexMismatch;
+    LAUNCH(ctx, "fa_mark_scatter", (fa_mark_scatter_kernel<0>), dim3(fblocks), dim3(kFaThreads), flat, nf, (const uint64_t *)offs,
+           (uint64_t *)ctx->rec_starts.p);
+    HIPCHK(hipMemcpyAsync((uint64_t *)ctx->rec_starts.p + R, &nf, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    ctx->rec_hdr_host.resize((size_t)R);
+    ctx->rec_starts_host.resize((size_t)R + 1);
+    HIPCHK(hipMemcpyAsync(ctx->rec_hdr_host.data(), ctx->rec_hdr.p, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->rec_starts_host.data(), ctx->rec_starts.p, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->rec_starts_host[(size_t)R] = nf;
+    ctx->rec_n = R;
+    ctx->rec_nf = nf;
+    return KPAL_OK;
+}
+
 // in_pinned0: host_text lies in ctx->pinned[0] (records_upload)
 static int fasta_records_index_text(kpal_ctx *ctx, const uint8_t *host_text, size_t nbytes, bool in_pinned0, uint64_t *n_records, uint64_t *flat_bytes)
 {
@@ -115,28 +145,15 @@ static int fasta_records_index_text(kpal_ctx *ctx, const uint8_t *host_text, siz
     const uint64_t nf = sizes[0], R = sizes[1];
     if (R == 0 || nf < R) return set_err(KPAL_E_HIP, "record index: %llu records in %llu flattened bytes", (unsigned long long)R, (unsigned long long)nf);
     CHK(ensure(ctx, ctx->rec_hdr, (size_t)R * 8));
-    CHK(ensure(ctx, ctx->rec_starts, (size_t)(R + 1) * 8));
     LAUNCH(ctx, "fa_mark_scatter", (fa_mark_scatter_kernel<1>), dim3(nblocks), dim3(kFaThreads), (const uint8_t *)raw, (uint64_t)m, (const uint64_t *)offs2,
            (uint64_t *)ctx->rec_hdr.p);
-    // record starts of the flattened stream: its '\n' bytes (offs / marks are free again: the flattening is done)
-    const uint32_t fblocks = (uint32_t)((nf + kFaBlockBytes - 1) / kFaBlockBytes);   // <= nblocks
-    LAUNCH(ctx, "fa_mark_count", (fa_mark_count_kernel<0>), dim3(fblocks), dim3(kFaThreads), (const uint8_t *)flat, nf, marks);
-    LAUNCH(ctx, "fa_offset", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)marks, fblocks, offs);
-    LAUNCH(ctx, "fa_mark_scatter", (fa_mark_scatter_kernel<0>), dim3(fblocks), dim3(kFaThreads), (const uint8_t *)flat, nf, (const uint64_t *)offs,
-           (uint64_t *)ctx->rec_starts.p);
-    uint64_t seps = 0;
-    HIPCHK(hipMemcpyAsync(&seps, offs + fblocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync((uint64_t *)ctx->rec_starts.p + R, &nf, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    ctx->rec_hdr_host.resize((size_t)R);
-    ctx->rec_starts_host.resize((size_t)R + 1);
-    HIPCHK(hipMemcpyAsync(ctx->rec_hdr_host.data(), ctx->rec_hdr.p, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->rec_starts_host.data(), ctx->rec_starts.p, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (seps != R) return set_err(KPAL_E_HIP, "record index: %llu header lines but %llu separators", (unsigned long long)R, (unsigned long long)seps);
-    ctx->rec_starts_host[(size_t)R] = nf;
+    // (offs / marks are free again: the flattening is done; the stream is no longer than the text)
+    uint64_t seps;
+    const int rc = records_index_finish(ctx, flat, nf, R, offs, marks, &seps);
+    if (rc == kIndexMismatch)
+        return set_err(KPAL_E_HIP, "record index: %llu header lines but %llu separators", (unsigned long long)R, (unsigned long long)seps);
+    CHK(rc);
     for (uint64_t &h : ctx->rec_hdr_host) h += first;
-    ctx->rec_n = R;
-    ctx->rec_nf = nf;
     *n_records = R;
     *flat_bytes = nf;
     return KPAL_OK;
@@ -156,7 +173,7 @@ KPAL_API int kpal_fasta_records_begin(kpal_ctx *ctx, const uint8_t *host_text, s
 // rest begins (*consumed), the flattened size.  Title offsets come from the newline positions (fq_title_offsets_kernel), flat
 // starts from the '\n' bytes of the stream (fastq_kernels.hpp says why).  Everything that counts reads the index only.
 // ----------------------------------------------------------------------------------------------
-static int fastq_records_index_text(kpal_ctx *ctx, const uint8_t *host_text, size_t nbytes, bool in_pinned0, int min_quality, int offset, bool fin,
+static int fastq_records_index_text(kpal_ctx *ctx, const uint8_t *host_text, size_t nbytes, bool in_pinned0, FqMask mask, bool fin,
                                     uint64_t records_before, uint64_t *n_records, uint64_t *flat_bytes, uint64_t *consumed)
 {
     *n_records = *flat_bytes = *consumed = 0;
@@ -174,7 +191,7 @@ static int fastq_records_index_text(kpal_ctx *ctx, const uint8_t *host_text, siz
     uint64_t *offs = (uint64_t *)ctx->rec_meta.p;
     uint32_t *marks = (uint32_t *)(offs + nblocks + 1);
     CHK(records_upload(ctx, raw, host_text, n, in_pinned0));
-    CHK(fq_tokenise(ctx, raw, n, fin, min_quality, offset, flat));
+    CHK(fq_tokenise(ctx, raw, n, fin, mask, flat));
     const unsigned long long *hs;
     CHK(fq_tokenise_wait(ctx, records_before, &hs));
     const uint64_t R = hs[2], nf = hs[4], used = fin ? n : hs[3];
@@ -184,29 +201,13 @@ static int fastq_records_index_text(kpal_ctx *ctx, const uint8_t *host_text, siz
     *consumed = used;
     if (R == 0) return KPAL_OK;
     CHK(ensure(ctx, ctx->rec_hdr, (size_t)R * 8));
-    CHK(ensure(ctx, ctx->rec_starts, (size_t)(R + 1) * 8));
     CHK(fq_title_offsets(ctx, R, (uint64_t *)ctx->rec_hdr.p));
-    // record starts of the flattened stream: its '\n' bytes, counted before they are listed -- the list has room for R
-    const uint32_t fblocks = (uint32_t)((nf + kFaBlockBytes - 1) / kFaBlockBytes);   // <= nblocks
-    LAUNCH(ctx, "fa_mark_count", (fa_mark_count_kernel<0>), dim3(fblocks), dim3(kFaThreads), (const uint8_t *)flat, nf, marks);
-    LAUNCH(ctx, "fa_offset", fa_offset_kernel, dim3(1), dim3(256), (const uint32_t *)marks, fblocks, offs);
-    uint64_t seps = 0;
-    HIPCHK(hipMemcpyAsync(&seps, offs + fblocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (seps != R)
+    uint64_t seps;
+    const int rc = records_index_finish(ctx, flat, nf, R, offs, marks, &seps);
+    if (rc == kIndexMismatch)
         return set_err(KPAL_E_HIP, "FASTQ record index: the tokeniser reports %llu records but the stream holds %llu record starts",
                        (unsigned long long)R, (unsigned long long)seps);
-    LAUNCH(ctx, "fa_mark_scatter", (fa_mark_scatter_kernel<0>), dim3(fblocks), dim3(kFaThreads), (const uint8_t *)flat, nf, (const uint64_t *)offs,
-           (uint64_t *)ctx->rec_starts.p);
-    HIPCHK(hipMemcpyAsync((uint64_t *)ctx->rec_starts.p + R, &nf, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    ctx->rec_hdr_host.resize((size_t)R);
-    ctx->rec_starts_host.resize((size_t)R + 1);
-    HIPCHK(hipMemcpyAsync(ctx->rec_hdr_host.data(), ctx->rec_hdr.p, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->rec_starts_host.data(), ctx->rec_starts.p, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->rec_starts_host[(size_t)R] = nf;
-    ctx->rec_n = R;
-    ctx->rec_nf = nf;
+    CHK(rc);
     *n_records = R;
     *flat_bytes = nf;
     return KPAL_OK;
@@ -217,39 +218,36 @@ KPAL_API int kpal_fastq_records_begin(kpal_ctx *ctx, const uint8_t *host_text, s
 {
     CTX_ENTER(ctx);
     if (!n_records || !flat_bytes || !consumed || (nbytes && !host_text)) return set_err(KPAL_E_INVALID, "NULL pointer");
-    *n_records = *flat_bytes = *consumed = 0;
-    records_index_clear(ctx);
-    int min_quality, offset;
-    CHK(fq_mask_options(opt, &min_quality, &offset));
-    return fastq_records_index_text(ctx, host_text, nbytes, false, min_quality, offset, final != 0, records_before, n_records, flat_bytes, consumed);
+    FqMask mask;
+    if (int rc = fq_mask_options(opt, mask)) {   // (every other error leaves through fastq_records_index_text, which has cleared both by then)
+        *n_records = *flat_bytes = *consumed = 0;
+        records_index_clear(ctx);
+        return rc;
+    }
+    return fastq_records_index_text(ctx, host_text, nbytes, false, mask, final != 0, records_before, n_records, flat_bytes, consumed);
 }
 
-// ---- the same over a FILE the library reads itself (fa_read: the pool's threads pread into the pinned staging buffer; no byte of the text
-// passes through Python): every kpal_fasta_records_file_next indexes the next piece of WHOLE records -- up to the end of line
-// before the last header line of what fits the 64 MiB staging buffer; the unfinished record behind it is carried to the next
-// piece; a record longer than the buffer is gathered in pageable memory first.
-static void fasta_records_file_reset(kpal_ctx *ctx)
+// ---- the same over a FILE the library reads itself (no byte of the text passes through Python): every
+// kpal_fasta_records_file_next indexes the next piece of WHOLE records, or reads.  The scan -- what is gathered into the pinned
+// staging buffer, where either format is cut, what is carried to the next piece, how a record longer than the buffer is
+// gathered -- is RecordScan (record_scan.hpp, GPU-free; tests/native/record_scan_check.cpp drives it under sanitizers); here it
+// is given the buffer, its guard and the index of the scan's format.
+static int records_file_open(kpal_ctx *ctx, const char *path, uint64_t begin, uint64_t end)
 {
-    if (ctx->rec_fd >= 0) close(ctx->rec_fd);
-    ctx->rec_fd = -1;
-    ctx->rec_pos = ctx->rec_end = ctx->rec_piece_at = 0;
-    ctx->rec_carry.clear();
-    ctx->rec_carry.shrink_to_fit();
-    ctx->rec_fastq = false;
-    ctx->rec_fq_records = 0;
+    ctx->rec_scan.scan.close();
+    FaSource src;
+    CHK(open_text_range(path, begin, end, src));
+    ctx->rec_scan.scan.open(src);
+    ctx->rec_scan.fastq = false;
+    ctx->rec_scan.records = 0;
+    return KPAL_OK;
 }
 
 KPAL_API int kpal_fasta_records_file_open(kpal_ctx *ctx, const char *path, uint64_t begin, uint64_t end)
 {
     CTX_ENTER(ctx);
     if (!path) return set_err(KPAL_E_INVALID, "path is NULL");
-    fasta_records_file_reset(ctx);
-    FaSource src;
-    CHK(open_text_range(path, begin, end, src));
-    ctx->rec_fd = src.fd;
-    ctx->rec_pos = ctx->rec_piece_at = src.pos;
-    ctx->rec_end = src.end;
-    return KPAL_OK;
+    return records_file_open(ctx, path, begin, end);
 }
 
 // ... of FASTQ reads: kpal_fasta_records_file_next / _tell / _close serve the scan, piece by piece of whole reads
@@ -258,101 +256,13 @@ KPAL_API int kpal_fastq_records_file_open(kpal_ctx *ctx, const char *path, uint6
 {
     CTX_ENTER(ctx);
     if (!path) return set_err(KPAL_E_INVALID, "path is NULL");
-    int min_quality, offset;
-    CHK(fq_mask_options(opt, &min_quality, &offset));
-    fasta_records_file_reset(ctx);
-    FaSource src;
-    CHK(open_text_range(path, begin, end, src));
-    ctx->rec_fd = src.fd;
-    ctx->rec_pos = ctx->rec_piece_at = src.pos;
-    ctx->rec_end = src.end;
-    ctx->rec_fastq = true;
-    ctx->rec_fq_min_quality = min_quality;
-    ctx->rec_fq_offset = offset;
-    ctx->rec_fq_records = records_before;
+    FqMask mask;
+    CHK(fq_mask_options(opt, mask));
+    CHK(records_file_open(ctx, path, begin, end));
+    ctx->rec_scan.fastq = true;
+    ctx->rec_scan.mask = mask;
+    ctx->rec_scan.records = records_before;
     return KPAL_OK;
-}
-
-// index of the end-of-line byte before the LAST header line of buf[0, n) that begins at or after `from` (a '>' behind an
-// end of line), or n when there is none
-static size_t fasta_last_boundary(const uint8_t *buf, size_t n, size_t from)
-{
-    size_t i = n;
-    while (i > from + 1) {
-        const void *p = memrchr(buf + from + 1, '>', i - from - 1);
-        if (!p) break;
-        const size_t at = (size_t)((const uint8_t *)p - buf);
-        if (fa_host_is_eol(buf[at - 1])) return at - 1;
-        i = at;
-    }
-    return n;
-}
-
-// The next piece of a FASTQ scan.  Unlike a FASTA piece it cannot be cut on the host (a quality line may begin with '@'): the
-// carried rest + the next staging buffer's worth of the file are tokenised as they are, and the tokeniser says where the
-// records it finishes end; the rest is carried.  A text that finishes no record is gathered further -- without a device call
-// while it has fewer than the four line ends a record needs.
-// whether buf[0, n) holds the four line ends a FASTQ record needs
-static bool fastq_four_line_ends(const uint8_t *buf, size_t n)
-{
-    const uint8_t *p = buf, *const end = buf + n;
-    for (int i = 0; i < 4; ++i) {
-        p = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
-        if (!p) return false;
-        ++p;
-    }
-    return true;
-}
-
-static int fastq_records_file_next(kpal_ctx *ctx, uint64_t *n_records, uint64_t *flat_bytes, uint64_t *text_offset, int *done)
-{
-    const size_t stage = std::min<size_t>(kpal_ctx::kStage, ctx->fa_chunk);
-    FaSource src;
-    src.fd = ctx->rec_fd;
-    for (;;) {
-        *n_records = *flat_bytes = *text_offset = 0;
-        *done = 1;
-        if (ctx->rec_carry.empty() && ctx->rec_pos >= ctx->rec_end) {   // the end
-            fasta_records_file_reset(ctx);
-            return KPAL_OK;
-        }
-        const size_t c = ctx->rec_carry.size();
-        const bool fits = c < stage;
-        const size_t want = (size_t)std::min<uint64_t>(fits ? stage - c : stage, ctx->rec_end - ctx->rec_pos);
-        uint8_t *buf;
-        if (fits) {   // the carried rest + the next bytes of the file into the pinned buffer
-            CHK(pinned_wait(ctx, 0));
-            buf = (uint8_t *)ctx->pinned[0];
-            if (c) memcpy(buf, ctx->rec_carry.data(), c);
-        } else {      // a read longer than the staging buffer: gathered in pageable memory
-            ctx->rec_carry.resize(c + want);
-            buf = ctx->rec_carry.data();
-        }
-        if (want) {
-            if (int e = fa_read(src, buf + c, ctx->rec_pos, want)) return set_err(KPAL_E_IO, "reading the FASTQ input failed: %s", strerror(e));
-            ctx->rec_pos += want;
-        }
-        const size_t n = c + want;
-        const bool at_end = ctx->rec_pos >= ctx->rec_end;
-        uint64_t used = 0;
-        if (at_end || fastq_four_line_ends(buf, n)) {
-            const uint64_t at = ctx->rec_piece_at;
-            CHK(fastq_records_index_text(ctx, buf, n, fits, ctx->rec_fq_min_quality, ctx->rec_fq_offset, at_end, ctx->rec_fq_records, n_records, flat_bytes, &used));
-            *text_offset = at;
-        }
-        if (used == 0 && !at_end) {   // no read ends in this text: keep gathering
-            if (fits) ctx->rec_carry.assign(buf, buf + n);
-            continue;
-        }
-        // the unfinished read behind the piece is carried (the DMA out of the pinned buffer has been waited for: the index is complete)
-        std::vector<uint8_t> tail(buf + used, buf + n);
-        ctx->rec_carry.swap(tail);
-        ctx->rec_piece_at += used;
-        ctx->rec_fq_records += *n_records;
-        *done = 0;
-        if (*n_records == 0) continue;   // (empty lines at the end of the file only)
-        return KPAL_OK;
-    }
 }
 
 KPAL_API int kpal_fasta_records_file_next(kpal_ctx *ctx, uint64_t *n_records, uint64_t *flat_bytes, uint64_t *text_offset, int *done)
@@ -361,56 +271,35 @@ KPAL_API int kpal_fasta_records_file_next(kpal_ctx *ctx, uint64_t *n_records, ui
     if (!n_records || !flat_bytes || !text_offset || !done) return set_err(KPAL_E_INVALID, "NULL pointer");
     *n_records = *flat_bytes = *text_offset = 0;
     *done = 1;
-    if (ctx->rec_fd < 0) return set_err(KPAL_E_STATE, "kpal_fasta_records_file_next without kpal_fasta_records_file_open");
+    RecordFileScan &rs = ctx->rec_scan;
+    if (!rs.scan.is_open()) return set_err(KPAL_E_STATE, "kpal_fasta_records_file_next without kpal_fasta_records_file_open");
     CHK(ensure_pinned(ctx));
-    if (ctx->rec_fastq) return fastq_records_file_next(ctx, n_records, flat_bytes, text_offset, done);
     const size_t stage = std::min<size_t>(kpal_ctx::kStage, ctx->fa_chunk);   // (KPAL_FASTA_CHUNK: tests put the seams everywhere)
-    FaSource src;
-    src.fd = ctx->rec_fd;
-    for (;;) {
-        if (ctx->rec_carry.empty() && ctx->rec_pos >= ctx->rec_end) {   // the end
-            fasta_records_file_reset(ctx);
-            *n_records = *flat_bytes = *text_offset = 0;
-            *done = 1;
-            return KPAL_OK;
+    // the index of one piece: a FASTA piece is whole records, all of it; of a FASTQ piece the tokeniser says what its reads cover
+    const RecordScan::Index index = [&](const uint8_t *piece, size_t n, bool in_stage, bool at_end, uint64_t *records, size_t *used) {
+        if (!rs.fastq) {
+            *used = n;
+            return fasta_records_index_text(ctx, piece, n, in_stage, records, flat_bytes);
         }
-        const size_t c = ctx->rec_carry.size();
-        const bool fits = c < stage;
-        const size_t want = (size_t)std::min<uint64_t>(fits ? stage - c : stage, ctx->rec_end - ctx->rec_pos);
-        uint8_t *buf;
-        if (fits) {   // the carried tail + the next bytes of the file into the pinned buffer
-            CHK(pinned_wait(ctx, 0));
-            buf = (uint8_t *)ctx->pinned[0];
-            if (c) memcpy(buf, ctx->rec_carry.data(), c);
-        } else {      // a record longer than the staging buffer: gathered in pageable memory, 64 MiB at a time
-            ctx->rec_carry.resize(c + want);
-            buf = ctx->rec_carry.data();
-        }
-        if (want) {
-            if (int e = fa_read(src, buf + c, ctx->rec_pos, want)) return set_err(KPAL_E_IO, "reading the FASTA input failed: %s", strerror(e));
-            ctx->rec_pos += want;
-        }
-        const size_t n = c + want;
-        const bool at_end = ctx->rec_pos >= ctx->rec_end;
-        // whole records: up to the end of line before the last header line (searched in the new bytes only; a boundary is two bytes)
-        const size_t cut = at_end ? n : fasta_last_boundary(buf, n, c ? c - 1 : 0);
-        if (cut >= n && !at_end) {   // no record ends in this piece: keep gathering
-            if (fits) ctx->rec_carry.assign(buf, buf + n);
-            continue;
-        }
-        const size_t piece = at_end ? n : cut + 1;
-        const uint64_t at = ctx->rec_piece_at;
-        const int rc = fasta_records_index_text(ctx, buf, piece, fits, n_records, flat_bytes);
-        if (rc != KPAL_OK) return rc;
-        // the unfinished record behind the piece is carried (the DMA out of the pinned buffer has been waited for: the index is complete)
-        std::vector<uint8_t> tail(buf + piece, buf + n);
-        ctx->rec_carry.swap(tail);
-        ctx->rec_piece_at = at + piece;
-        *text_offset = at;
-        *done = 0;
-        if (*n_records == 0 && !(ctx->rec_carry.empty() && at_end)) continue;   // (text before the first header only: next piece)
+        uint64_t consumed = 0;
+        const int rc = fastq_records_index_text(ctx, piece, n, in_stage, rs.mask, at_end, rs.records, records, flat_bytes, &consumed);
+        *used = (size_t)consumed;
+        return rc;
+    };
+    ScanPiece piece;
+    const int got = rs.scan.next((uint8_t *)ctx->pinned[0], stage, [ctx] { return pinned_wait(ctx, 0); },
+                                 rs.fastq ? fastq_record_cut : fasta_record_cut, index, piece);
+    if (got == -1) return set_err(KPAL_E_IO, "reading the %s input failed: %s", rs.fastq ? "FASTQ" : "FASTA", strerror(rs.scan.io_errno()));
+    if (got == -2) return rs.scan.user_error();
+    if (got == 0) {   // the end: the scan is closed
+        *flat_bytes = 0;
         return KPAL_OK;
     }
+    rs.records += piece.records;
+    *n_records = piece.records;
+    *text_offset = piece.text_offset;
+    *done = 0;
+    return KPAL_OK;
 }
 
 // Where the scan stands: the file offset of the first byte that no piece has covered yet (the start of the carried,
@@ -420,15 +309,15 @@ KPAL_API int kpal_fasta_records_file_tell(kpal_ctx *ctx, uint64_t *offset)
 {
     CTX_ENTER(ctx);
     if (!offset) return set_err(KPAL_E_INVALID, "NULL pointer");
-    if (ctx->rec_fd < 0) return set_err(KPAL_E_STATE, "kpal_fasta_records_file_tell without an open scan");
-    *offset = ctx->rec_piece_at;
+    if (!ctx->rec_scan.scan.is_open()) return set_err(KPAL_E_STATE, "kpal_fasta_records_file_tell without an open scan");
+    *offset = ctx->rec_scan.scan.tell();
     return KPAL_OK;
 }
 
 KPAL_API int kpal_fasta_records_file_close(kpal_ctx *ctx)
 {
     CTX_ENTER(ctx);
-    fasta_records_file_reset(ctx);
+    ctx->rec_scan.scan.close();
     return KPAL_OK;
 }
 

@@ -196,7 +196,7 @@ static const char *fq_error_text(unsigned kind)
     }
 }
 
-static int fq_options(const kpal_fastq_options *opt, FqMask &m)
+int fq_mask_options(const kpal_fastq_options *opt, FqMask &m)
 {
     m.min_quality = opt ? opt->min_quality : -1;
     m.offset = opt ? opt->quality_offset : 33;
@@ -206,22 +206,12 @@ static int fq_options(const kpal_fastq_options *opt, FqMask &m)
     return KPAL_OK;
 }
 
-int fq_mask_options(const kpal_fastq_options *opt, int *min_quality, int *offset)
-{
-    FqMask m;
-    CHK(fq_options(opt, m));
-    *min_quality = m.min_quality;
-    *offset = m.offset;
-    return KPAL_OK;
-}
-
 // The tokenising of ONE chunk, shared by the count path (fastq_pipeline) and the record index (kpal_records.hip): raw[0, n) on
 // the device, beginning at a title line, n < 4 GiB - 64 -> flat; fin: the text ends with the chunk.  Queued on the context's
 // stream: the newline positions stay in fq_pos, the status words go to fq_status and from there to fq_status_host, and fq_ev is
 // recorded behind that copy -- the caller waits for it (fq_tokenise_wait) when it needs the words.
-int fq_tokenise(kpal_ctx *ctx, const uint8_t *raw, uint64_t n, bool fin, int min_quality, int offset, uint8_t *flat)
+int fq_tokenise(kpal_ctx *ctx, const uint8_t *raw, uint64_t n, bool fin, FqMask m, uint8_t *flat)
 {
-    const FqMask m = {min_quality, offset};
     if (!ctx->fq_status_host) {
         hipError_t e = hipHostMalloc((void **)&ctx->fq_status_host, kFqStatusWords * sizeof(unsigned long long), hipHostMallocDefault);
         if (e != hipSuccess) {
@@ -332,7 +322,7 @@ static int fastq_pipeline(kpal_ctx *ctx, FaSource &src, const std::vector<uint8_
         uint8_t *raw = (uint8_t *)ctx->fq_raw[slot].p;
         if (clen) HIPCHK(hipMemcpyAsync(raw, (const uint8_t *)ctx->fq_raw[cslot].p + cstart, clen, hipMemcpyDeviceToDevice, ctx->stream));
         if (m_bytes) CHK(pinned_h2d(ctx, slot, raw + clen, ck.data, m_bytes));
-        CHK(fq_tokenise(ctx, raw, n, fin, m.min_quality, m.offset, (uint8_t *)ctx->fq_flat[slot].p + pad));
+        CHK(fq_tokenise(ctx, raw, n, fin, m, (uint8_t *)ctx->fq_flat[slot].p + pad));
         CHK(consume());                          // the chunk before: its count runs behind this chunk's tokenising
         const unsigned long long *hs;
         CHK(fq_tokenise_wait(ctx, records, &hs));
@@ -369,8 +359,7 @@ void fq_reset(kpal_ctx *ctx)
 static int fastq_feed(kpal_ctx *ctx, FaSource &src, const FqMask &m)
 {
     ctx->fq_open = true;
-    ctx->fq_min_quality = m.min_quality;
-    ctx->fq_offset = m.offset;
+    ctx->fq_mask = m;
     const int rc = fastq_pipeline(ctx, src, ctx->fq_carry, false, m, ctx->fq_records, true, nullptr, nullptr, &ctx->fq_carry);
     if (rc != KPAL_OK) {
         fq_reset(ctx);
@@ -388,8 +377,7 @@ int count_end_text(kpal_ctx *ctx)
     int rc = KPAL_OK;
     if (!ctx->fq_carry.empty()) {
         FaSource src;
-        const FqMask m = {ctx->fq_min_quality, ctx->fq_offset};
-        rc = fastq_pipeline(ctx, src, ctx->fq_carry, true, m, ctx->fq_records, true, nullptr, nullptr, nullptr);
+        rc = fastq_pipeline(ctx, src, ctx->fq_carry, true, ctx->fq_mask, ctx->fq_records, true, nullptr, nullptr, nullptr);
     }
     fq_reset(ctx);
     if (rc != KPAL_OK) ctx->counting = false;
@@ -401,7 +389,7 @@ KPAL_API int kpal_count_feed_fastq(kpal_ctx *ctx, const uint8_t *host_buf, size_
     CTX_ENTER(ctx);
     if (!ctx->counting) return set_err(KPAL_E_STATE, "kpal_count_feed_fastq before kpal_count_begin");
     FqMask m;
-    CHK(fq_options(opt, m));
+    CHK(fq_mask_options(opt, m));
     if (nbytes == 0) return KPAL_OK;
     if (!host_buf) return set_err(KPAL_E_INVALID, "host_buf is NULL");
     FaSource src;
@@ -416,7 +404,7 @@ KPAL_API int kpal_count_feed_fastq_file(kpal_ctx *ctx, const char *path, uint64_
     if (!ctx->counting) return set_err(KPAL_E_STATE, "kpal_count_feed_fastq_file before kpal_count_begin");
     if (!path) return set_err(KPAL_E_INVALID, "path is NULL");
     FqMask m;
-    CHK(fq_options(opt, m));
+    CHK(fq_mask_options(opt, m));
     FaSource src;
     CHK(open_text_range(path, begin, end, src));
     const int rc = src.pos < src.end ? fastq_feed(ctx, src, m) : KPAL_OK;
@@ -431,7 +419,7 @@ KPAL_API int kpal_fastq_flatten(kpal_ctx *ctx, const uint8_t *host_buf, size_t n
     if (!n_out || (nbytes && (!host_buf || !host_out))) return set_err(KPAL_E_INVALID, "NULL pointer");
     *n_out = 0;
     FqMask m;
-    CHK(fq_options(opt, m));
+    CHK(fq_mask_options(opt, m));
     if (nbytes == 0) return KPAL_OK;
     FaSource src;
     src.mem = host_buf;

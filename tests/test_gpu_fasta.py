@@ -403,6 +403,61 @@ def test_fasta_records_c_abi(ctx, tmp_path):
         klib._RECORD_BATCH_BYTES = monkey_batch
 
 
+def test_fasta_records_file_pieces_in_a_row(tmp_path, monkeypatch):
+    """kpal_fasta_records_file_next called again and again on ONE open scan (klib opens, takes one piece and closes): what the
+    scan carries from piece to piece.  25 records in about 3 KB, one of them 700 bytes on one line -- at pieces of 64 bytes
+    it is gathered in pageable memory over many rounds -- and the file ends in a record without an end of line.  Every piece begins where the piece before said the scan stood; header offsets and record lengths are those of the
+    host tokeniser; a call after the end finds no scan open."""
+    import re
+    from kpal_amd import _native
+    rnd = random.Random(12)
+    lengths = [rnd.randint(0, 120) for _ in range(25)]
+    lengths[9], lengths[24] = 700, 40
+    parts = []
+    for i, n in enumerate(lengths):
+        seq = ''.join(rnd.choice('ACGTN') for _ in range(n))
+        width = 10 ** 9 if i == 9 else 60
+        parts.append('>rec%d some title\n' % i + ''.join(seq[j:j + width] + '\n' for j in range(0, n, width)))
+    text = ''.join(parts).rstrip('\n')
+    assert 2500 < len(text) < 3500 and text[-1] in 'ACGTN'
+    recs = seqio_records(text)
+    headers, at = [], 0                                                       # the lines that begin with '>'
+    for line in re.split('(\r\n|\r|\n)', text):
+        if line[:1] == '>':
+            headers.append(at)
+        at += len(line)
+    assert len(recs) == len(headers) == 25
+    path = tmp_path / 'row.fa'
+    path.write_bytes(text.encode('latin-1'))
+    for chunk in (64, 257):
+        monkeypatch.setenv('KPAL_FASTA_CHUNK', str(chunk))
+        ctx2 = _native.Context(_native.default_device())
+        monkeypatch.delenv('KPAL_FASTA_CHUNK')
+        try:
+            ctx2.fasta_records_file_open(str(path))
+            tell, pieces, got_headers, got_lengths = 0, 0, [], []
+            while True:
+                piece = ctx2.fasta_records_file_next()
+                if piece is None:
+                    break
+                n, nf, off = piece
+                assert off == tell and n > 0, (chunk, pieces)
+                hdr, starts = ctx2.fasta_records_index()
+                assert hdr.size == n and starts[0] == 0 and starts[-1] == nf
+                got_headers += (hdr + np.uint64(off)).tolist()
+                got_lengths += (np.diff(starts) - np.uint64(1)).tolist()
+                tell = ctx2.fasta_records_file_tell()
+                pieces += 1
+            assert pieces > 3 and tell == len(text), (chunk, pieces, tell)
+            assert got_headers == headers, chunk
+            assert got_lengths == [len(seq) for _, seq in recs], chunk
+            assert len(got_headers) == 25
+            with pytest.raises(RuntimeError, match='without kpal_fasta_records_file_open'):
+                ctx2.fasta_records_file_next()
+        finally:
+            ctx2.close()
+
+
 def test_by_record_generators_interleaved_on_files(tmp_path, monkeypatch):
     """Two (and three) from_fasta_by_record generators over DIFFERENT files advanced in turns -- zip(), one nested in the other,
     one abandoned half-way -- on the process-wide context, with pieces of 300 bytes (every file is many pieces) and two records

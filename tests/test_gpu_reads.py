@@ -160,6 +160,48 @@ def test_index_numbers_a_malformed_record_over_the_whole_text(ctx):
     assert whole_index(ctx, good)[0] == 20
 
 
+@pytest.mark.parametrize('chunk', [64, 257])
+def test_file_pieces_in_a_row(tmp_path, monkeypatch, chunk):
+    """kpal_fasta_records_file_next called again and again on ONE open scan of reads (klib opens, takes one piece and closes):
+    what the scan carries from piece to piece.  25 reads in about 3 KB, one of 700 bases -- 1400 bytes, gathered in pageable
+    memory over many rounds -- and the file ends in a read.  Every piece begins where the piece before said the scan stood;
+    title offsets and read lengths are those of the host tokeniser; a call after the end finds no scan open."""
+    rnd = random.Random(chunk)
+    lengths = [rnd.randint(0, 30) for _ in range(25)]
+    lengths[9] = 700
+    text = make_text(rnd, lengths)
+    assert 2500 < len(text) < 3500
+    reads = fastq_reads(text)
+    titles = [s for s, _ in line_spans(text)[0::4]]
+    assert len(reads) == len(titles) == 25
+    path = tmp_path / 'row.fq'
+    path.write_bytes(text)
+    ctx2 = context_with_chunk(monkeypatch, chunk)
+    try:
+        ctx2.fastq_records_file_open(str(path))
+        tell, pieces, got_titles, got_lengths = 0, 0, [], []
+        while True:
+            piece = ctx2.fasta_records_file_next()
+            if piece is None:
+                break
+            n, nf, off = piece
+            assert off == tell and n > 0, pieces
+            hdr, starts = ctx2.fasta_records_index()
+            assert hdr.size == n and starts[0] == 0 and starts[-1] == nf
+            got_titles += (hdr + np.uint64(off)).tolist()
+            got_lengths += (np.diff(starts) - np.uint64(1)).tolist()
+            tell = ctx2.fasta_records_file_tell()
+            pieces += 1
+        assert pieces > 3 and tell == len(text), (pieces, tell)
+        assert got_titles == titles
+        assert got_lengths == [len(r) for r in reads]
+        assert len(got_titles) == 25
+        with pytest.raises(RuntimeError, match='without kpal_fasta_records_file_open'):
+            ctx2.fasta_records_file_next()
+    finally:
+        ctx2.close()
+
+
 # ---- by read -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('chunk', [17, 300, 4096, None])
 @pytest.mark.parametrize('k', [1, 4, 8])

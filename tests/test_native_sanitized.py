@@ -1,6 +1,7 @@
 """The product's own GPU-free host code under AddressSanitizer + UBSan and ThreadSanitizer (CPU only: sanitizers are not
 available on the GPU pool): the pool of copy threads (kpal_amd/csrc/host_pool.hpp), the host side of the FASTA ingest --
-source, read-ahead, chunk cutting, the state carried across chunk seams (kpal_amd/csrc/fasta_host.hpp) -- and the copy phase
+source, read-ahead, chunk cutting, the state carried across chunk seams (kpal_amd/csrc/fasta_host.hpp) --, the by-record scan
+of a FASTA or FASTQ file -- gather, cut, carry (kpal_amd/csrc/record_scan.hpp) -- and the copy phase
 of the CPython gatherer behind Profile.from_sequences (kpal_amd/csrc/kpal_join_core.h), and the stream / event schedule of the
 pipelined multi-GPU table reduce (kpal_amd/csrc/comm_schedule.hpp) driven by a fake runtime.  The harnesses are tests/native/*."""
 import os
@@ -21,6 +22,7 @@ CASES = [
     # (harness, compiler, language flags, pool sizes to run with)
     ('host_pool_check.cpp', 'g++', ['-std=c++17'], ['1', '2', '16']),
     ('fasta_host_check.cpp', 'g++', ['-std=c++17'], ['1', '5']),
+    ('record_scan_check.cpp', 'g++', ['-std=c++17'], ['1', '5']),   # kpal_amd/csrc/record_scan.hpp: the by-record scan of a file
     ('join_check.c', 'gcc', ['-std=c11'], ['']),
     ('gather_check.c', 'gcc', ['-std=c11'], ['']),      # kpal_amd/csrc/kpal_gather_core.h: walk AND copies on several threads
     # the stream / event schedule of the pipelined multi-GPU reduce on a fake runtime: ranks, streams and events as threads
