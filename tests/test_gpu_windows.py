@@ -247,8 +247,12 @@ def test_launch_structure_and_determinism(ctx):
     assert m2 == m16 == many
     _, m1, _ = launches(ctx, long_, 4, 200, 200)
     assert m1 == {'window_tiles': 1, 'window_trim': 1}
-    _, long_tiles, _ = launches(ctx, long_, 7, 5000, 2500)      # steps past 2048 bases: eight waves per tile, the same names
+    n_long, long_tiles, tables = launches(ctx, long_, 7, 5000, 2500)      # steps past 2048 bases: eight waves per tile, the same names
     assert long_tiles == many
+    want = expected([('l', long_[3:-1])], 7, 5000, 2500)
+    assert n_long == len(want) == 8
+    for row, (name, table) in zip(tables, want):
+        np.testing.assert_array_equal(row, table, err_msg=name)
     text8 = '>l\n' + bases(rnd, 64 + 99 * 16) + '\n'
     n8, k8, a = launches(ctx, text8, 8, 64, 16)
     _, k8_again, b = launches(ctx, text8, 8, 64, 16)
