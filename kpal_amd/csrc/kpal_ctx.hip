@@ -131,6 +131,8 @@ static int ctx_init(kpal_ctx *ctx, int device)
     }
     if (const char *e = getenv("KPAL_QUAD_STEPS")) ctx->quad_steps_forced = atoi(e);
     if (const char *e = getenv("KPAL_QUAD_STEPS2")) ctx->quad_steps2_forced = atoi(e);
+    if (const char *e = getenv("KPAL_QUAD_WORKGROUPS")) ctx->quad_workgroups_max = atoi(e);   // tests: long runs per scatter workgroup
+    if (const char *e = getenv("KPAL_K12_STAGED")) ctx->k12_staged = atoi(e) != 0;
     if (const char *e = getenv("KPAL_QUAD_VERBOSE")) ctx->quad_verbose = atoi(e) != 0;
     if (const char *e = getenv("KPAL_QUAD_REPEAT")) ctx->quad_repeat_forced = atoi(e) != 0 ? 1 : 0;
     if (const char *e = getenv("KPAL_HIST_PACKED")) ctx->quad_hist_unpacked = atoi(e) == 0;

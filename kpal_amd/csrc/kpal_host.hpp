@@ -142,6 +142,10 @@ struct kpal_ctx {
     uint32_t *quad_error_word = nullptr;
     bool chunk_error_armed = false;
     int quad_steps_forced = 0, quad_steps2_forced = 0;   // KPAL_QUAD_STEPS / KPAL_QUAD_STEPS2 at context creation (tests, A/B): tile sizes of the quad scatters
+    int quad_workgroups_max = 0;             // KPAL_QUAD_WORKGROUPS (tests): the quad plans are made for this many CUs (0: the device's) -- few
+                                             // scatter workgroups write long runs, the shapes the histogram's run stream is tested on
+    int quad_cus() const { return quad_workgroups_max > 0 && quad_workgroups_max < num_cu ? quad_workgroups_max : num_cu; }
+    bool k12_staged = true;                  // KPAL_K12_STAGED=0: the k = 12 histogram merges into the table with atomics (A/B, tests)
     bool quad_verbose = false;               // KPAL_QUAD_VERBOSE
     int quad_repeat_forced = -1;             // KPAL_QUAD_REPEAT=0 / 1: the scatter instantiation without / with the repeat lanes' shortcut (-1: by the sample)
     // what the last piece of the last feed took (kpal_count_last_plan): strategy, wave-steps per wave and tile of level 1 / level 2

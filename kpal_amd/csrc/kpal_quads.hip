@@ -84,7 +84,7 @@ int launch_partition_quads(kpal_ctx *ctx, const Span &s)
     ctx->plan_steps1 = steps;
     ctx->plan_steps2 = 0;
     // ---- check
-    const Quad1Geometry geo = quad1_geometry(total_steps, steps, ctx->num_cu);
+    const Quad1Geometry geo = quad1_geometry(total_steps, steps, ctx->quad_cus());
     if (geo.too_large) return set_err(KPAL_E_INVALID, "quad partition: batch too large");
     if (geo.pool_bytes > ctx->quad_pool_max && s.nchunks > 64) return kSplitBatch;   // (heavily skewed 16 GiB piece: small tiles)
     const uint32_t G = geo.G;
@@ -100,9 +100,8 @@ int launch_partition_quads(kpal_ctx *ctx, const Span &s)
     // pass when kpal_count_balance asks (the pending finalisation: kpal_quads2.hip).  A form count >= 256 goes to the table
     // directly; the mean per form is bytes / (4 x 4^12), so pieces whose mean could pass 240 (16 GB of unbroken sequence) keep the
     // atomic merge.  KPAL_K12_STAGED=0: the atomic merge everywhere (A/B, tests).
-    static const bool allow_staged = [] { const char *e = getenv("KPAL_K12_STAGED"); return !e || atoi(e) != 0; }();
     uint32_t *stage = nullptr;
-    if (ctx->k == 12 && allow_staged && (double)feed_bytes <= 240.0 * 4.0 * (double)ctx->bins) {
+    if (ctx->k == 12 && ctx->k12_staged && (double)feed_bytes <= 240.0 * 4.0 * (double)ctx->bins) {
         CHK(ensure(ctx, ctx->residuals, (size_t)ctx->bins * 4 * sizeof(quad2_stage_t)));
         stage = (uint32_t *)ctx->residuals.p;
     }

@@ -36,12 +36,12 @@ int launch_partition2_quads(kpal_ctx *ctx, const Span &s, bool fresh)
     const bool repeat1 = tile1.repeat;
     if (tile1.counted) ++ctx->stat_repeat_pieces;
     // ---- check.  A piece that is refused or halved here has been sampled but leaves no tile sizes behind: its halves sample again.
-    const Quad2Level1 l1 = quad2_level1(ctx->k, total_steps, steps1, ctx->num_cu);
+    const Quad2Level1 l1 = quad2_level1(ctx->k, total_steps, steps1, ctx->quad_cus());
     if (l1.too_large) return set_err(KPAL_E_INVALID, "quad partition: batch too large");
     if (l1.pool1_bytes > ctx->quad_pool_max && s.nchunks > 64) return kSplitBatch;
     int steps2 = cached ? ctx->tiles.steps2 : quad_walk_level2(fine, steps1);
     const int forced2 = quad_forced_steps(ctx->quad_steps2_forced, kQuadCandidates2, sizeof(kQuadCandidates2) / sizeof(kQuadCandidates2[0]));
-    const Quad2Level2 l2 = quad2_level2(l1, forced2 ? forced2 : steps2, ctx->num_cu);
+    const Quad2Level2 l2 = quad2_level2(l1, forced2 ? forced2 : steps2, ctx->quad_cus());
     if (l2.too_large) return set_err(KPAL_E_INVALID, "quad partition: batch too large");
     if (!cached) ctx->tiles.store(steps1, steps2, feed_bytes);
     if (forced2) steps2 = forced2;               // (KPAL_QUAD_STEPS2: applied after the sizes are kept, so never kept itself)

@@ -1282,7 +1282,7 @@ __global__ __launch_bounds__(1024) void quad_hist_kernel(const uint32_t *__restr
     asm volatile("" : "+v"(plane_base[0]), "+v"(plane_base[1]));
     constexpr bool kUnits = !PACKED;                    // plane i holds counts << unit_shift(i)
     auto unit_shift = [](int i) -> int { return kUnits ? 3 - i : 0; };
-    auto add_item = [&](uint32_t it, auto guard_tag) {
+    auto add_item = [&](uint32_t it, auto guard_tag) __attribute__((always_inline)) {   // (a call would put everything the lambdas capture into scratch memory)
         constexpr bool GUARD = decltype(guard_tag)::value;
         // bin of k-mer i in its form: the low 6-2i bits of hi6 above the top L-6+2i bits of low -- with the item laid out
         // hi6 | low | mask4 that is ONE bit-field of the item: L bits from bit 10 - 2i
@@ -1369,7 +1369,7 @@ __global__ __launch_bounds__(1024) void quad_hist_kernel(const uint32_t *__restr
         const uint32_t first = __builtin_amdgcn_readfirstlane(it);
         return first != 0u && __popcll(__builtin_amdgcn_ballot_w64(it == first)) >= 8;   // wave-uniform
     };
-    auto add4 = [&](const uint4 q, const bool skew) {
+    auto add4 = [&](const uint4 q, const bool skew) __attribute__((always_inline)) {
         if constexpr (C::kItem3) {   // four 3-byte items + a fifth in the top bytes
             // (the bit-fields add_item reads lie below bit 23: the rider's byte above an item does not matter; an item is
             // null iff its mask nibble is zero)
@@ -1407,23 +1407,111 @@ __global__ __launch_bounds__(1024) void quad_hist_kernel(const uint32_t *__restr
     // run g of the bucket = the records workgroup g of the scatter wrote for it.  With at least 16 runs a wave takes
     // whole runs; with fewer (the two-level path at k = 15, 16: 4 runs, 1 run) 16 / G waves share a run, 256 vectors
     // at a time each -- otherwise only G of the 16 waves would have loads in flight.
+    //   The runs a wave takes are ONE stream to it: batches of 256 vectors (four 16-byte loads per lane), the next batch
+    // requested before the current one is counted -- across run boundaries too, so only a wave's very first batch is waited
+    // for cold (a loop per run began every run with a fully exposed memory latency: sixteen per wave and bucket at G = 256).
+    // What a run leaves over after its whole batches (nvec % 256 vectors) rides in ONE batch with the head of the wave's next
+    // run that wrote anything: slot s of that batch reads the old run while s < `ra`, the new run's vector s - ra otherwise.
+    // (As an iteration of its own the remainder cost the whole add4 skeleton for 8 vectors of 256 at the headline shape.)
+    //   Every vector is addressed by a 32-bit BYTE offset from the row's first run -- a row's runs lie within
+    // G x rounds_cap pieces, a 1/512 th of the pool or less: far below 4 GiB for any pool that fits the device -- kept per lane and
+    // slot: a whole batch within a run costs one add per load (no clamp, no index arithmetic, nothing to zero); the offsets
+    // are worked out afresh only where a batch is ragged (once per run), and only such a batch zeroes the slots it does not fill.
+    const uint32_t wave_u = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
     const uint32_t parts = G >= 16u ? 1u : 16u / G;            // waves per run
-    const uint32_t g_first = G >= 16u ? (uint32_t)wave : (uint32_t)wave % G;
-    const uint32_t part = G >= 16u ? 0u : (uint32_t)wave / G;
-    for (uint32_t g = g_first; g < G && part < parts; g += 16) {   // wave-uniform
-        // PACK3: the run of (row, g) is one 192-byte record (16 vectors of 12 bytes) in every 384-byte piece of its row pair
-        const uint32_t *src3 = pool + ((uint64_t)((row_linear >> 1) * G + g) * rounds_cap) * (uint64_t)(2 * kQuadPackedRecordBytes / 4) +
-                               (row_linear & 1u) * (uint32_t)(kQuadPackedRecordBytes / 4);
-        const uint4 *src = C::kPairRows
-                               ? reinterpret_cast<const uint4 *>(pool + ((uint64_t)((row_linear >> 1) * G + g) * rounds_cap) * (2 * S) + (row_linear & 1u) * S)
-                               : reinterpret_cast<const uint4 *>(pool + ((uint64_t)(row_linear * G + g) * rounds_cap) * S);
+    const uint32_t g_first = G >= 16u ? wave_u : wave_u % G;
+    const uint32_t part = G >= 16u ? 0u : wave_u / G;
+    // PACK3: the run of (row, g) is one 192-byte record (16 vectors of 12 bytes) in every 384-byte piece of its row pair;
+    // kPairRows: the row's half of every 128-byte line
+    constexpr uint32_t PIECE = PACK3 ? 2u * (uint32_t)kQuadPackedRecordBytes : (C::kPairRows ? 2u : 1u) * (uint32_t)(S * 4);   // bytes per round and run
+    constexpr uint32_t BATCH = PACK3 ? 16u * PIECE : (C::kPairRows ? 8192u : 4096u);                                           // ... per 256 vectors
+    const char *rowbase = reinterpret_cast<const char *>(pool) +
+                          ((PACK3 || C::kPairRows) ? ((uint64_t)(row_linear >> 1) * G * rounds_cap) * (uint64_t)PIECE + (row_linear & 1u) * (PIECE / 2u)
+                                                   : ((uint64_t)row_linear * G * rounds_cap) * (uint64_t)PIECE);
+    const uint32_t run_bytes = rounds_cap * PIECE;
+    auto vec_off = [](uint32_t a) -> uint32_t {                // byte offset of vector a of a run
+        if constexpr (PACK3) return (a >> 4) * PIECE + (a & 15u) * 12u;
+        return C::kPairRows ? (a >> 2) * 128u + (a & 3u) * 16u : a * 16u;
+    };
+    auto run_vectors = [&](uint32_t g) -> uint32_t {
+#if defined(KPAL_AB_POOL_FILL)   // (... and read: six sevenths of the vectors, i.e. fewer null items to test AND fewer real ones: an upper bound of the gain)
+        return nrounds[g] * (uint32_t)(S / 4) / 7u * 6u;
+#else
+        return nrounds[g] * (uint32_t)(S / 4);
+#endif
+    };
+    auto load = [&](uint32_t o) -> uint4 {
+        if constexpr (PACK3) {
+            const QuadPacked w = *reinterpret_cast<const QuadPacked *>(rowbase + o);
+            return quad_unpack3(w.a, w.b, w.c);
+        } else {
+            return *reinterpret_cast<const uint4 *>(rowbase + o);
+        }
+    };
+    // the stream's cursor (wave-uniform): the run being read has nA vectors, slot 0 of the next batch is its vector pa; gn: the
+    // next run to look at.  With fewer than 16 runs a wave has ONE run and every `parts`-th batch of it, from batch `part` on.
+    uint32_t nA = 0, pa = 0, gn = part < parts ? g_first : G;
+    uint32_t off[4] = {0u, 0u, 0u, 0u};                        // per lane: where slot lane + 64 j of the next batch lies
+    // Requests the next batch.  Returns 0: the stream has ended (the loads went to the row's first vector: nothing to count),
+    // 1: a whole batch of one run, 2: a ragged batch -- bit j of `ok` says whether slot lane + 64 j holds a vector.
+    // The loads are UNCONDITIONAL and stand in the loop's own block (what differs between the kinds of batch is arithmetic
+    // before and after them): predicated ones sit in basic blocks of their own, the compiler then waits with vmcnt(0) before
+    // the first use -- for the four just requested as well, so every iteration paid a full memory latency and the LDS idled
+    // 43 % of the time.
+    auto request = [&](uint4 &n0, uint4 &n1, uint4 &n2, uint4 &n3, uint32_t &ok) __attribute__((always_inline)) -> int {
+        const bool whole = pa + 256u <= nA;                    // wave-uniform
+        uint32_t ra = 0, nB = 0, gB = 0;
+        if (!whole) {
+            ra = nA > pa ? nA - pa : 0u;                       // (< 256) vectors the run still has
+#if defined(KPAL_AB_HIST_NO_RIDE)   // A/B timing builds (same counts): what a run leaves over gets a batch of its own, the next run starts a new one
+            if (ra == 0u)
+#endif
+            while (gn < G) {                                   // the next run that holds anything (wave-uniform: scalar loads)
+                nB = run_vectors(gn);
+                if (nB) break;
+                gn += 16u;
+            }
+            gB = gn;
+#if defined(KPAL_AB_HIST_NO_RIDE)
+            if (ra == 0u)
+#endif
+            gn += 16u;
+            const uint32_t offB = gB * run_bytes;              // (unused while nB == 0)
+            ok = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t s = (uint32_t)lane + 64u * (uint32_t)j;
+                const uint32_t b = part * 256u + s - ra;       // vector of the new run (s >= ra)
+                const bool in_a = s < ra, in_b = !in_a && b < nB;
+                off[j] = in_a ? off[j] : (in_b ? offB + vec_off(b) : 0u);
+                ok |= (in_a || in_b ? 1u : 0u) << j;
+            }
+        }
+        n0 = load(off[0]);
+        n1 = load(off[1]);
+        n2 = load(off[2]);
+        n3 = load(off[3]);
+        if (whole) {
+            pa += parts * 256u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) off[j] += parts * BATCH;
+            return 1;
+        }
+        if (nB == 0u) {                                        // no further run
+            nA = pa = 0;
+            return ra ? 2 : 0;
+        }
+        nA = nB;
+        pa = part * 256u + parts * 256u - ra;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) off[j] = gB * run_bytes + vec_off(pa + (uint32_t)lane + 64u * (uint32_t)j);
 #if !defined(KPAL_QUAD_NO_PRIO)   // A/B builds
         // The wave that is behind in its runs goes first (quad_tile_priority: the arbiter's oldest-first order let the waves of a SIMD
         // finish one after the other, and the LDS idled under the last ones): k = 12 3.79 -> 3.58 ms, k = 11 3.35 -> 3.19, k = 13
         // 3.85 -> 3.63.  Not when waves SHARE a run (G < 16; k = 15, 16): g then says nothing about progress, and the same switch
         // cost that histogram 8 %.
         if (parts == 1u) {
-            switch (g * 4u / G) {
+            switch (gB * 4u / G) {
             case 0: __builtin_amdgcn_s_setprio(3); break;
             case 1: __builtin_amdgcn_s_setprio(2); break;
             case 2: __builtin_amdgcn_s_setprio(1); break;
@@ -1431,38 +1519,23 @@ __global__ __launch_bounds__(1024) void quad_hist_kernel(const uint32_t *__restr
             }
         }
 #endif
-#if defined(KPAL_AB_POOL_FILL)   // (... and read: six sevenths of the vectors, i.e. fewer null items to test AND fewer real ones: an upper bound of the gain)
-        const uint32_t nvec = nrounds[g] * (uint32_t)(S / 4) / 7u * 6u;
-#else
-        const uint32_t nvec = nrounds[g] * (uint32_t)(S / 4);
-#endif
-        if (nvec == 0u) continue;                  // wave-uniform: this scatter workgroup wrote nothing
-        // four 16-byte loads per lane in flight; the next four are requested before these are counted.  The loads are
-        // UNCONDITIONAL (index clamped, value zeroed afterwards): predicated ones sit in basic blocks of their own, the
-        // compiler then waits with vmcnt(0) before the first use -- for the four just requested as well, so every
-        // iteration paid a full memory latency and the LDS idled 43 % of the time.
-        auto fetch = [&](uint32_t at) -> uint4 {
-            const uint32_t a = min(at, nvec - 1u);
-            uint4 r;
-            if constexpr (PACK3) {
-                const uint32_t *p3 = src3 + (a >> 4) * (uint32_t)(2 * kQuadPackedRecordBytes / 4) + (a & 15u) * 3u;
-                const QuadPacked w = *reinterpret_cast<const QuadPacked *>(p3);
-                r = quad_unpack3(w.a, w.b, w.c);
-            } else {
-                r = src[C::kPairRows ? ((a >> 2) * 8u + (a & 3u)) : a];   // (pairs: the row's half of every 128-byte line)
+        return 2;
+    };
+    {
+        uint4 q0, q1, q2, q3;
+        uint32_t q_ok = 0;
+        int kind = request(q0, q1, q2, q3, q_ok);
+        while (kind) {                                         // wave-uniform
+            uint4 n0, n1, n2, n3;
+            uint32_t n_ok = 0;
+            const int n_kind = request(n0, n1, n2, n3, n_ok);
+            if (kind == 2) {                                   // ragged: the slots that hold no vector count nothing
+                const uint32_t k0 = 0u - (q_ok & 1u), k1 = 0u - ((q_ok >> 1) & 1u), k2 = 0u - ((q_ok >> 2) & 1u), k3 = 0u - ((q_ok >> 3) & 1u);
+                q0.x &= k0, q0.y &= k0, q0.z &= k0, q0.w &= k0;
+                q1.x &= k1, q1.y &= k1, q1.z &= k1, q1.w &= k1;
+                q2.x &= k2, q2.y &= k2, q2.z &= k2, q2.w &= k2;
+                q3.x &= k3, q3.y &= k3, q3.z &= k3, q3.w &= k3;
             }
-            const uint32_t keep = at < nvec ? 0xFFFFFFFFu : 0u;
-            r.x &= keep;
-            r.y &= keep;
-            r.z &= keep;
-            r.w &= keep;
-            return r;
-        };
-        uint32_t v = part * 256u + lane;
-        uint4 q0 = fetch(v), q1 = fetch(v + 64u), q2 = fetch(v + 128u), q3 = fetch(v + 192u);
-        while (v < nvec) {
-            v += parts * 256u;
-            const uint4 n0 = fetch(v), n1 = fetch(v + 64u), n2 = fetch(v + 128u), n3 = fetch(v + 192u);
 #if defined(KPAL_AB_HIST_NO_ADD)     // A/B timing builds (wrong counts): the record stream alone
             asm volatile("" ::"v"(q0.x ^ q0.y ^ q0.z ^ q0.w ^ q1.x ^ q1.y ^ q1.z ^ q1.w ^ q2.x ^ q2.y ^ q2.z ^ q2.w ^ q3.x ^ q3.y ^ q3.z ^ q3.w));
 #else
@@ -1476,6 +1549,8 @@ __global__ __launch_bounds__(1024) void quad_hist_kernel(const uint32_t *__restr
             q1 = n1;
             q2 = n2;
             q3 = n3;
+            q_ok = n_ok;
+            kind = n_kind;
         }
     }
 #if !defined(KPAL_QUAD_NO_PRIO)
