@@ -302,7 +302,10 @@ uint64_t kpal_reverse_complement(uint64_t number, int k);
  * even, 4^k/2 when odd; *n_out receives that length. */
 int kpal_split(kpal_ctx *ctx, int k, const int64_t *host_counts, int64_t *host_forward,
                int64_t *host_reverse, uint64_t *n_out);
-/* kmer.get_balance score, kmer.py:243-245: multiset(*split(), pairwise) fused in one pass. */
+/* kmer.get_balance score, kmer.py:243-245: multiset(*split(), pairwise) fused in one pass.  This is
+ * kpal_strand_balance_set (below) with one table: the same kernels, the same bits.  KPAL_E_INVALID: k outside
+ * 1..KPAL_MAX_K, a NULL pointer, a pairwise other than prod or sum, host_counts not 8-byte aligned (the last was
+ * undefined behaviour before it was checked). */
 int kpal_strand_balance(kpal_ctx *ctx, int k, const int64_t *host_counts, int pairwise, double *out);
 
 /* metrics.multiset (metrics.py:101-123) with pairwise prod/sum, and metrics.euclidean
@@ -446,7 +449,8 @@ int kpal_stats_set_device(kpal_ctx *ctx, size_t n_tables, size_t bins, const int
 int kpal_stats_set(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *host_tables,
                    kpal_profile_stats *host_out);
 /* kmer.get_balance scores (kpal/kmer.py:243-245) of n_tables consecutive 4^k tables, replacing a loop of kpal_strand_balance
- * calls: the fused split + multiset kernel over tiles x profiles and one reduction per pass.  KPAL_E_INVALID: k outside
+ * calls (each of which is this entry with n_tables = 1): the fused split + multiset kernel over tiles x profiles and one
+ * reduction per pass.  KPAL_E_INVALID: k outside
  * 1..KPAL_MAX_K, a NULL pointer, n_tables == 0, a pairwise other than prod or sum, tables not 8-byte aligned. */
 int kpal_strand_balance_set_device(kpal_ctx *ctx, int k, size_t n_tables, const int64_t *dev_tables /* n_tables x 4^k */,
                                    int pairwise, double *host_out /* n_tables */);

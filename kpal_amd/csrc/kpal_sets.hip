@@ -1,6 +1,6 @@
 // kpal_sets.hip -- the part of the C-ABI that works on a whole SET of count vectors lying one behind the other: the summaries
 // and the strand balance of every profile, in a number of launches that does not grow with the set (planned by stat_plan.hpp,
-// the kernels in stat_set_kernels.hpp).
+// the kernels in stat_set_kernels.hpp).  The strand balance of ONE vector is here too: a set of one table, no other implementation.
 #include "kpal_host.hpp"
 
 #include "stat_set_kernels.hpp"
@@ -143,4 +143,10 @@ KPAL_API int kpal_strand_balance_set(kpal_ctx *ctx, int k, size_t n_tables, cons
         CHK(kpal_strand_balance_set_device(ctx, k, (size_t)c.count, (const int64_t *)ctx->scratch[0].p, pairwise, host_out + c.first));
     }
     return KPAL_OK;
+}
+
+// One vector is a set of one table: the same checks with the same texts, the same kernels on the same grid, the same bits.
+KPAL_API int kpal_strand_balance(kpal_ctx *ctx, int k, const int64_t *host_counts, int pairwise, double *out)
+{
+    return kpal_strand_balance_set(ctx, k, 1, host_counts, pairwise, out);
 }

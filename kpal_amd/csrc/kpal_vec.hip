@@ -1,5 +1,5 @@
-// kpal_vec.hip -- everything of the C-ABI that works on ONE count vector: balance, split, strand balance, the reduction of
-// (sum, count) partials every distance ends with, profile summaries, merge and shrink.
+// kpal_vec.hip -- everything of the C-ABI that works on ONE count vector: balance, split, the reduction of (sum, count)
+// partials every distance ends with, profile summaries, merge and shrink.  (The strand balance of one vector: kpal_sets.hip.)
 #include "kpal_host.hpp"
 
 #include "vec_kernels.hpp"
@@ -156,32 +156,6 @@ double finish_value(int metric, const Partial &p, int64_t *aux)
 {
     if (aux) *aux = (int64_t)p.m;
     return finish_distance(metric, false, p, p, p);
-}
-
-KPAL_API int kpal_strand_balance(kpal_ctx *ctx, int k, const int64_t *host_counts, int pairwise, double *out)
-{
-    CTX_ENTER(ctx);
-    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
-    if (!host_counts || !out) return set_err(KPAL_E_INVALID, "NULL pointer");
-    if (pairwise != KPAL_PAIRWISE_PROD && pairwise != KPAL_PAIRWISE_SUM) return set_err(KPAL_E_INVALID, "pairwise must be prod or sum");
-    const uint64_t n = 1ULL << (2 * k);
-    CHK(ensure(ctx, ctx->scratch[0], n * 8));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, host_counts, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    const unsigned grid = k >= 6 ? (1u << (2 * (k - 6))) : stream_grid(ctx, n);
-    CHK(ensure(ctx, ctx->partials, (size_t)grid * sizeof(Partial)));
-    const int64_t *dc = (const int64_t *)ctx->scratch[0].p;
-    Partial *pp = (Partial *)ctx->partials.p;
-    if (k >= 6) {
-        if (pairwise == KPAL_PAIRWISE_PROD) LAUNCH(ctx, "strand_balance_tiled", (strand_balance_tiled_kernel<0>), dim3(grid), dim3(1024), dc, k, pp);
-        else LAUNCH(ctx, "strand_balance_tiled", (strand_balance_tiled_kernel<1>), dim3(grid), dim3(1024), dc, k, pp);
-    } else {
-        if (pairwise == KPAL_PAIRWISE_PROD) LAUNCH(ctx, "strand_balance", (strand_balance_kernel<0>), dim3(grid), dim3(256), dc, k, n, pp);
-        else LAUNCH(ctx, "strand_balance", (strand_balance_kernel<1>), dim3(grid), dim3(256), dc, k, n, pp);
-    }
-    std::vector<Partial> res;
-    CHK(finish_partials(ctx, 1, grid, res));
-    *out = finish_value(pairwise, res[0], nullptr);
-    return KPAL_OK;
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -49,7 +49,8 @@ inline uint64_t stat_scratch_bytes(uint64_t bins)
     return stat_slices(bins) * kStatPartialBytes + kStatHistBytes + kStatStateBytes + kStatOutBytes;
 }
 
-// The strand balance of a set: workgroups per profile (one per 64 x 64 tile of the LDS-tiled form, k >= 6; one per 256 bins
+// The strand balance of a set (one profile, kpal_strand_balance, is a set of one): workgroups per profile (one per 64 x 64 tile
+// of the LDS-tiled form, k >= 6; one per 256 bins
 // below that) and a (sum, count) partial for each.
 inline uint64_t balance_set_grid(int k) { return k >= 6 ? 1ULL << (2 * (k - 6)) : (k >= 4 ? 1ULL << (2 * (k - 4)) : 1ULL); }
 inline uint64_t balance_set_scratch_bytes(int k) { return balance_set_grid(k) * sizeof(Partial); }

@@ -11,6 +11,11 @@
 //   T6  select_pick_set_kernel   the digit that holds rank (bins - 1) / 2, per profile; extends its prefix; clears hist[p]
 //   T7  select_next_set_kernel   the smallest key above the lower middle one, where the upper middle one is another value
 //   T8  median_set_kernel        median = ((double)v0 + (double)v1) / 2
+//   B1  strand_balance_set_kernel<PW>         k < 6: fused split + multiset, a (sum, count) partial per 256 bins
+//   B2  strand_balance_tiled_set_kernel<PW>   k >= 6: the same over 64 x 64 LDS tiles, a partial per tile
+//
+// B1 and B2 are the only strand balance kernels: kpal_strand_balance runs them on a set of one table.  (The summaries of one
+// table still have kernels of their own, stat_kernels.hpp: at k = 15 the set pass on one table is slower, docs/NOTEBOOK.md.)
 //
 // A profile whose smallest and largest key agree in a byte (and in every byte above it) has the same digit there in every
 // entry: T5 and T6 leave it alone at that byte (StatSetState::top) -- the digit is the smallest key's, which the prefix starts
@@ -19,7 +24,7 @@
 #pragma once
 #include "stat_kernels.hpp"
 #include "stat_plan.hpp"
-#include "vec_kernels.hpp"
+#include "matrix_common.hpp"
 
 namespace kpal {
 
@@ -235,21 +240,86 @@ static __global__ __launch_bounds__(256) void median_set_kernel(const StatSetSta
     out[p].median = ((double)v0 + (double)v1) / 2.0;
 }
 
-// ---- strand balance of a set: the bodies of vec_kernels.hpp, the profile from blockIdx.y ----
+// ---- strand balance: multiset(*split()) fused, the profile from blockIdx.y.  A single profile (kpal_strand_balance) is a set of
+// one: these are the only strand balance kernels. ----
+// k < 6: the workgroups of blockIdx.x stride through the n bins of the profile.
 template <int PW>
 __global__ __launch_bounds__(256) void strand_balance_set_kernel(const int64_t *__restrict__ tables, int k, uint64_t n,
                                                                  Partial *__restrict__ partials)
 {
-    const Partial p = strand_balance_body<PW>(tables + (uint64_t)blockIdx.y * n, k, n);
+    const int64_t *c = tables + (uint64_t)blockIdx.y * n;
+    Partial p = {0.0, 0ULL};
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t r = revcomp(i, k);
+        if (i > r) continue;
+        int64_t f, v;
+        if (i < r) {
+            f = (int64_t)((uint64_t)c[i] * 2ULL);
+            v = (int64_t)((uint64_t)c[r] * 2ULL);
+        } else {
+            f = v = c[i];
+        }
+        if (f != 0 || v != 0) {
+            p.s += PW == 0 ? pw_prod(f, v) : pw_sum(f, v);
+            p.m += 1;
+        }
+    }
+    p = block_reduce(p);
     if (threadIdx.x == 0) partials[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = p;
 }
 
+// k >= 6: kmer.get_balance score (kpal/kmer.py:243-245) with the split halves never materialised: every
+// unordered pair {i, rc(i)} is visited once -- from the tile of the smaller M, or, inside a
+// self-paired tile, from its smaller index (palindromes contribute f = r = c[i], klib.py:322-323).
+// Tile M = blockIdx.x.
 template <int PW>
 __global__ __launch_bounds__(1024) void strand_balance_tiled_set_kernel(const int64_t *__restrict__ tables, int k,
                                                                         Partial *__restrict__ partials)
 {
     __shared__ unsigned long long A[64][65], B[64][65];
-    const Partial p = strand_balance_tiled_body<PW>(tables + ((uint64_t)blockIdx.y << (2 * k)), k, A, B);
+    constexpr int T = 3, S = 64;
+    const int64_t *c = tables + ((uint64_t)blockIdx.y << (2 * k));
+    const int md = k - 2 * T;
+    const uint64_t M = blockIdx.x;
+    const uint64_t Mr = md > 0 ? revcomp(M, md) : 0;
+    Partial p = {0.0, 0ULL};
+    if (M <= Mr) {
+        const bool self = M == Mr;
+        const uint64_t rowstride = 1ULL << (2 * (k - T));
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        const unsigned long long *uc = reinterpret_cast<const unsigned long long *>(c);
+        for (int h = w; h < S; h += 16) {
+            A[h][lane] = uc[(uint64_t)h * rowstride + M * S + lane];
+            if (!self) B[h][lane] = uc[(uint64_t)h * rowstride + Mr * S + lane];
+        }
+        __syncthreads();
+        const int rl = (int)revcomp((uint64_t)lane, T);
+        for (int h = w; h < S; h += 16) {
+            const int rh = (int)revcomp((uint64_t)h, T);
+            const unsigned long long mine = A[h][lane];
+            const unsigned long long other = self ? A[rl][rh] : B[rl][rh];
+            int64_t f, v;
+            bool take = true;
+            if (self) {
+                const int i_loc = h * S + lane, r_loc = rl * S + rh;   // order inside the tile == global order
+                take = i_loc <= r_loc;
+                if (i_loc == r_loc) {
+                    f = v = (int64_t)mine;
+                } else {
+                    f = (int64_t)(mine * 2ULL);
+                    v = (int64_t)(other * 2ULL);
+                }
+            } else {
+                f = (int64_t)(mine * 2ULL);
+                v = (int64_t)(other * 2ULL);
+            }
+            if (take && (f != 0 || v != 0)) {
+                p.s += PW == 0 ? pw_prod(f, v) : pw_sum(f, v);
+                p.m += 1;
+            }
+        }
+    }
+    p = block_reduce(p);
     if (threadIdx.x == 0) partials[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = p;
 }
 

@@ -1,16 +1,14 @@
 // vec_kernels.hpp -- streaming kernels over 4^k int64 count vectors (gfx950).
 //   balance            Profile.balance            kpal/klib.py:285-298
 //   split              Profile.split              kpal/klib.py:300-327
-//   strand balance     kmer.get_balance score     kpal/kmer.py:243-245
 //   pair distance      metrics.multiset/euclidean kpal/metrics.py:101-135
 // All are HBM-bandwidth kernels.  (The distance matrix, kdistlib.distance_matrix, is fp64-VALU bound and lives in
 // cross_kernels.hpp -- the triangle is a set crossed with itself -- and matrix_all_kernels.hpp; what those share with the
-// pair kernels here is matrix_common.hpp.)
+// pair kernels here is matrix_common.hpp.  The strand balance, kmer.get_balance, of one profile or of a set: stat_set_kernels.hpp.)
 // fp64 sums are reduced in a FIXED order (per-thread serial, wave shuffle tree, block tree,
 // then a single-workgroup pass over the per-block partials) so results are run-to-run
 // reproducible; they agree with NumPy's pairwise summation to ~1e-15 relative.
-// Three units include this header (kpal_vec.hip; kpal_pair.hip for the pair kernels; kpal_sets.hip for the strand balance bodies): the
-// kernels that are no templates are static.
+// Two units include this header (kpal_vec.hip; kpal_pair.hip for the pair kernels): the kernels that are no templates are static.
 #pragma once
 #include "matrix_common.hpp"
 
@@ -171,39 +169,6 @@ static __global__ __launch_bounds__(256) void split_write_kernel(const int64_t *
     }
 }
 
-// ---- strand balance: multiset(*split()) fused ------------------------------------------------
-// The body serves one profile (strand_balance_kernel) and the profiles of a set (strand_balance_set_kernel, stat_set_kernels.hpp:
-// the profile from blockIdx.y): the workgroups of blockIdx.x stride through the n bins of `c`; the reduced partial is valid in thread 0.
-template <int PW>
-__device__ __forceinline__ Partial strand_balance_body(const int64_t *__restrict__ c, int k, uint64_t n)
-{
-    Partial p = {0.0, 0ULL};
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t r = revcomp(i, k);
-        if (i > r) continue;
-        int64_t f, v;
-        if (i < r) {
-            f = (int64_t)((uint64_t)c[i] * 2ULL);
-            v = (int64_t)((uint64_t)c[r] * 2ULL);
-        } else {
-            f = v = c[i];
-        }
-        if (f != 0 || v != 0) {
-            p.s += PW == 0 ? pw_prod(f, v) : pw_sum(f, v);
-            p.m += 1;
-        }
-    }
-    return block_reduce(p);
-}
-
-template <int PW>
-__global__ __launch_bounds__(256) void strand_balance_kernel(const int64_t *__restrict__ c, int k, uint64_t n,
-                                                             Partial *__restrict__ partials)
-{
-    const Partial p = strand_balance_body<PW>(c, k, n);
-    if (threadIdx.x == 0) partials[blockIdx.x] = p;
-}
-
 // ---- pair distance --------------------------------------------------------------------------
 // METRIC 0/1: multiset prod/sum (metrics.py:121-123); 2: euclidean (int64 dot, metrics.py:135,46).
 template <int METRIC, typename T>
@@ -352,67 +317,6 @@ __global__ __launch_bounds__(1024) void pair_distance_balanced_kernel(const int6
 {
     __shared__ unsigned long long A[64][65], B[64][65];
     pair_distance_balanced_body<METRIC, true>(l, r, k, canon, ncanon, partials, A, B);
-}
-
-// kmer.get_balance score (kpal/kmer.py:243-245) with the split halves never materialised: every
-// unordered pair {i, rc(i)} is visited once -- from the tile of the smaller M, or, inside a
-// self-paired tile, from its smaller index (palindromes contribute f = r = c[i], klib.py:322-323).
-// (The body: tile M = blockIdx.x of profile `c`, for strand_balance_tiled_kernel and strand_balance_tiled_set_kernel; the reduced
-// partial is valid in thread 0.)
-template <int PW>
-__device__ __forceinline__ Partial strand_balance_tiled_body(const int64_t *__restrict__ c, int k, unsigned long long (*A)[65], unsigned long long (*B)[65])
-{
-    constexpr int T = 3, S = 64;
-    const int md = k - 2 * T;
-    const uint64_t M = blockIdx.x;
-    const uint64_t Mr = md > 0 ? revcomp(M, md) : 0;
-    Partial p = {0.0, 0ULL};
-    if (M <= Mr) {
-        const bool self = M == Mr;
-        const uint64_t rowstride = 1ULL << (2 * (k - T));
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        const unsigned long long *uc = reinterpret_cast<const unsigned long long *>(c);
-        for (int h = w; h < S; h += 16) {
-            A[h][lane] = uc[(uint64_t)h * rowstride + M * S + lane];
-            if (!self) B[h][lane] = uc[(uint64_t)h * rowstride + Mr * S + lane];
-        }
-        __syncthreads();
-        const int rl = (int)revcomp((uint64_t)lane, T);
-        for (int h = w; h < S; h += 16) {
-            const int rh = (int)revcomp((uint64_t)h, T);
-            const unsigned long long mine = A[h][lane];
-            const unsigned long long other = self ? A[rl][rh] : B[rl][rh];
-            int64_t f, v;
-            bool take = true;
-            if (self) {
-                const int i_loc = h * S + lane, r_loc = rl * S + rh;   // order inside the tile == global order
-                take = i_loc <= r_loc;
-                if (i_loc == r_loc) {
-                    f = v = (int64_t)mine;
-                } else {
-                    f = (int64_t)(mine * 2ULL);
-                    v = (int64_t)(other * 2ULL);
-                }
-            } else {
-                f = (int64_t)(mine * 2ULL);
-                v = (int64_t)(other * 2ULL);
-            }
-            if (take && (f != 0 || v != 0)) {
-                p.s += PW == 0 ? pw_prod(f, v) : pw_sum(f, v);
-                p.m += 1;
-            }
-        }
-    }
-    return block_reduce(p);
-}
-
-template <int PW>
-__global__ __launch_bounds__(1024) void strand_balance_tiled_kernel(const int64_t *__restrict__ c, int k,
-                                                                    Partial *__restrict__ partials)
-{
-    __shared__ unsigned long long A[64][65], B[64][65];
-    const Partial p = strand_balance_tiled_body<PW>(c, k, A, B);
-    if (threadIdx.x == 0) partials[blockIdx.x] = p;
 }
 
 // Final fixed-order reduction of per-block partials: out[q] = sum over blocks of partials[q*nblocks + b].

@@ -24,7 +24,7 @@ Every call states the kernels it must launch, with their counts, read off the di
 LAUNCH in kpal_host.hpp), so that a dispatch change cannot route around the path under test:
   balance (k >= 6)            balance_tiled
   split                       split_count + split_write
-  strand balance (k >= 6)     strand_balance_tiled + reduce_partials
+  strand balance (k >= 6)     strand_balance_tiled_set + reduce_partials (the single entry is the set entry with one table)
   pair distance               pair_distance (do_balance: pair_distance_balanced) + reduce_partials
   options                     balance_tiled x 2, positive, smooth_level x k + smooth_apply, totals + reduce_partials,
                               option_distance + reduce_partials -- each as the options ask; without positive, smoothing and
@@ -172,7 +172,7 @@ def test_balance_split_strand_and_pair_distance_vs_dense_oracle(k):
             if b is None:
                 continue
             for pw, code in (('prod', 0), ('sum', 1)):
-                got = run(ctx, {'strand_balance_tiled': 1, 'reduce_partials': 1}, lambda: ctx.strand_balance(a, k, code), what)
+                got = run(ctx, {'strand_balance_tiled_set': 1, 'reduce_partials': 1}, lambda: ctx.strand_balance(a, k, code), what)
                 assert lk.close(got, oracle.strand_balance(a, k, pw), RTOL), (what, pw)
             bb = oracle.balance(b, k)
             for name in ('prod', 'sum', 'euclidean'):

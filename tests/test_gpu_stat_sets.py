@@ -224,6 +224,32 @@ def test_host_pointer_entries_equal_the_device_entries(ctx):
     assert (got.total, got.non_zero, got.min, got.max, got.median, got.mean) == (one.total, one.non_zero, one.min, one.max, one.median, one.mean)
 
 
+def test_single_strand_balance_is_the_set_entry_with_one_table(ctx):
+    """kpal_strand_balance is kpal_strand_balance_set with one table: the same bits as the table alone in a set and as its row
+    in a set of five, for both pairwise codes -- k = 1 to 5 untiled (one workgroup up to k = 4, four at k = 5), k = 6 one tile,
+    k = 7 four tiles, k = 8 sixteen; a table of zeros at k = 3 and k = 6 -- and the same launches."""
+    for k in range(1, 9):
+        rs = np.random.RandomState(40 + k)
+        tables = rs.poisson(rs.choice([0.3, 2.0, 40.0]), (5, 4 ** k)).astype(np.int64)
+        if k in (3, 6):
+            tables[2] = 0
+        for native in (0, 1):
+            five = ctx.strand_balance_set(tables, k, native)
+            for i in (0, 2, 4):
+                v = tables[i]
+                one, seen = launches(ctx, lambda: ctx.strand_balance(v, k, native))
+                alone, seen_set = launches(ctx, lambda: ctx.strand_balance_set(v[None], k, native))
+                assert np.float64(one).tobytes() == alone.tobytes() == five[i:i + 1].tobytes(), (k, native, i, one, alone, five[i])
+                assert seen == seen_set == {'strand_balance_tiled_set' if k >= 6 else 'strand_balance_set': 1, 'reduce_partials': 1}
+    # the single entry refuses what the set entry refuses, before anything is launched: a table that is not 8-byte aligned
+    from kpal_amd import _native
+    raw = np.zeros(8 * 16 + 16, dtype=np.uint8)
+    at = raw.ctypes.data + (4 if raw.ctypes.data % 8 == 0 else 8 - raw.ctypes.data % 8 + 4)
+    out = ctypes.c_double(0.0)
+    rc, seen = launches(ctx, lambda: ctx._L.kpal_strand_balance(ctx._h, 2, at, 0, ctypes.byref(out)))
+    assert rc == _native._E_INVALID and seen == {}
+
+
 def test_errors(ctx):
     """Every misuse is KPAL_E_INVALID (a ValueError), decided before anything is launched."""
     from kpal_amd import _native
@@ -318,7 +344,7 @@ def test_summaries_of_device_profiles(ctx, record_profiles, which):
     assert len(ps) == 70 and all(p._device_counts() is not None for p in ps)
     (got, scores), seen = launches(ctx, lambda: (klib.summaries(ps), klib.strand_balances(ps)))
     assert all(p._device_counts() is not None for p in ps)                           # nothing was downloaded
-    assert not any(name in seen for name in SINGLE_STATS_KERNELS + ('strand_balance', 'strand_balance_tiled')), seen
+    assert not any(name in seen for name in SINGLE_STATS_KERNELS), seen
     batches = len(set(id(p._device[0]) for p in ps))                                 # (a batch per piece of the text the scan took)
     assert seen['stats_set'] == batches <= 2 and seen['strand_balance_set'] == 1, seen   # one set call per batch; one gathered set
     want = [klib.Profile(p.counts.copy()).summary() for p in copies]
@@ -403,13 +429,15 @@ def test_commands_print_the_single_profile_lines(ctx, record_profiles):
     assert len(names) == 70
     singles = [klib.Profile.from_file(handle, name=name) for name in names]
 
-    def run(command, **kwargs):
+    def run(command, balance_calls=0, **kwargs):
+        """The command's lines; it made one set call for all 70 profiles where it scores the balance, and none per profile."""
         out = io.StringIO()
         _, seen = launches(ctx, lambda: command(handle, out, **kwargs))
-        assert not any(name in seen for name in SINGLE_STATS_KERNELS + ('strand_balance', 'strand_balance_tiled')), seen
+        assert not any(name in seen for name in SINGLE_STATS_KERNELS), seen
+        assert seen.get('strand_balance_set', 0) + seen.get('strand_balance_tiled_set', 0) == balance_calls, seen
         return out.getvalue().split('\n')
 
-    lines = run(kmer.get_balance, precision=10)
+    lines = run(kmer.get_balance, balance_calls=1, precision=10)
     assert len(lines) == 71 and lines[-1] == ''
     assert lines[:70] == ['%s %.10f' % (name, ctx.strand_balance(p.counts, 4, 0)) for name, p in zip(names, singles)]
     lines = run(kmer.get_stats, precision=10)

@@ -1,6 +1,8 @@
 """The summaries and the strand balance of whole sets of profiles against the per-profile entries, in one process, on the same
 tables in HBM: kpal_stats_set_device against a loop of kpal_stats_device, kpal_strand_balance_set_device against a loop of
-kpal_strand_balance (which uploads its table: the only single-profile entry there is).  Shapes: 20 000 x k = 6, 4 000 x k = 8
+kpal_strand_balance (which uploads its table: the only single-profile entry there is; it is kpal_strand_balance_set with one
+table, so that "loop" column loops the set entry at n = 1 -- the committed profiles/sets/setbench.json was taken when it still had
+kernels of its own, on the same grid).  Shapes: 20 000 x k = 6, 4 000 x k = 8
 with the Poisson counts 10 kb reads give, 64 x k = 12.  One warm-up of either side, then alternating repeats, host clock around
 calls that end in a device synchronise, the median; the kernel-time share of one more, profiled run of each (kpal_prof_*).
 Then the public API: ``[p.summary() for p in batch]`` on a fresh Profile.from_fastq_by_record batch of generated reads, against
