@@ -456,6 +456,22 @@ int kpal_strand_balance_set_device(kpal_ctx *ctx, int k, size_t n_tables, const 
                                    int pairwise, double *host_out /* n_tables */);
 int kpal_strand_balance_set(kpal_ctx *ctx, int k, size_t n_tables, const int64_t *host_tables, int pairwise,
                             double *host_out);
+/* metrics.distribution (kpal/metrics.py:22-33) of every one of n_tables int64 vectors of `bins` entries lying one behind the
+ * other -- the count-of-counts spectrum: for table t the pairs offsets[t] .. offsets[t+1]-1, values ascending (signed order),
+ * number >= 1, the numbers of a table summing to bins.  Exact for every int64 input (values are compared as order-preserving
+ * uint64 keys, every counter is 64-bit).  Without a sort: per pass six launches, one more if any entry lies past its table's
+ * dense window (spectrum_plan.hpp: the keys [min, min + W) of a table, W = min(widest spread of the pass, bins, 2^20)), and
+ * three synchronisations, whatever n_tables is; the entries past the window are sorted on the host.  A table's pairs do not
+ * depend on the set it is in, on its place there, or on where the passes are cut (scratch budget, 65535 tables;
+ * KPAL_STAT_SET_PROFILES, read on every call, lowers the tables of a pass).  The pairs stay with the context until the next
+ * distribution call or kpal_ctx_destroy; kpal_distribution_fetch copies pairs [first_pair, first_pair + n_pairs) out, in
+ * as many pieces as the caller likes.  KPAL_E_INVALID: a NULL pointer, n_tables == 0, bins == 0, tables not 8-byte aligned;
+ * fetch with no distribution pending or with a range past the last pair.  The host variant uploads through the context's
+ * scratch.  One table is a set of one. */
+int kpal_distribution_set_device(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *dev_tables /* n_tables x bins */,
+                                 uint64_t *host_offsets /* n_tables + 1 */);
+int kpal_distribution_set(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *host_tables, uint64_t *host_offsets);
+int kpal_distribution_fetch(kpal_ctx *ctx, uint64_t first_pair, uint64_t n_pairs, int64_t *host_values, uint64_t *host_numbers);
 
 /* Profile.merge(profile, merger) for the built-in metrics.mergers (kpal/metrics.py:174-179,
  * kpal/klib.py:269-283): out = merger(left, right); out may be left or right. */

@@ -157,6 +157,9 @@ SIGNATURES = {
     'kpal_stats_device': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _statp]),
     'kpal_stats_set': (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _statp]),
     'kpal_stats_set_device': (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _statp]),
+    'kpal_distribution_set': (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
+    'kpal_distribution_set_device': (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
+    'kpal_distribution_fetch': (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp]),
     'kpal_strand_balance_set': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_size_t, _vp, ctypes.c_int, _f64p]),
     'kpal_strand_balance_set_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_size_t, _vp, ctypes.c_int, _f64p]),
     'kpal_merge': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, _vp]),
@@ -859,6 +862,28 @@ class Context(object):
         out = (ProfileStats * t.shape[0])()
         _check(self._L.kpal_stats_set(self._h, t.shape[0], t.shape[1], t.ctypes.data, out))
         return out
+
+    def distribution_fetch(self, first_pair, n_pairs):
+        """Pairs [first_pair, first_pair + n_pairs) of the last distribution call -> (values int64[], numbers uint64[])."""
+        values = np.empty(int(n_pairs), dtype=np.int64)
+        numbers = np.empty(int(n_pairs), dtype=np.uint64)
+        _check(self._L.kpal_distribution_fetch(self._h, int(first_pair), int(n_pairs), values.ctypes.data, numbers.ctypes.data))
+        return values, numbers
+
+    def distribution_set_device(self, dev_ptr, n_tables, bins):
+        """metrics.distribution of n_tables consecutive int64 vectors of ``bins`` entries at a device address -> (offsets
+        uint64[n_tables + 1], values int64[], numbers uint64[]): the pairs of table t are offsets[t] .. offsets[t + 1] - 1,
+        values ascending (kpal_distribution_set_device: launches that do not grow with n_tables)."""
+        offsets = np.zeros(int(n_tables) + 1, dtype=np.uint64)
+        _check(self._L.kpal_distribution_set_device(self._h, int(n_tables), int(bins), _vp(dev_ptr), offsets.ctypes.data))
+        return (offsets,) + self.distribution_fetch(0, int(offsets[-1]))
+
+    def distribution_set(self, tables_2d):
+        """distribution_set_device for a host array of shape (n_tables, bins)."""
+        t = _as_i64_2d(tables_2d)
+        offsets = np.zeros(t.shape[0] + 1, dtype=np.uint64)
+        _check(self._L.kpal_distribution_set(self._h, t.shape[0], t.shape[1], t.ctypes.data, offsets.ctypes.data))
+        return (offsets,) + self.distribution_fetch(0, int(offsets[-1]))
 
     def strand_balance_set_device(self, k, n_tables, dev_ptr, pairwise=PAIRWISE_PROD):
         """The strand balance of n_tables consecutive 4**k tables at a device address -> float64[n_tables]."""

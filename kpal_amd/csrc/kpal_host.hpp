@@ -4,7 +4,8 @@
 // round-1 pipelines; kpal_text.hip: FASTA and FASTQ ingest; kpal_records.hip: one profile per record / per sliding window;
 // kpal_quads.hip / kpal_quads2.hip: the quad record pipelines, planned by quad_plan.hpp; kpal_vec.hip: one vector -- balance,
 // split, summaries, merge, shrink; kpal_sets.hip: the summaries and the strand balance of a whole set of vectors, planned by
-// stat_plan.hpp, and the strand balance of one vector, which is a set of one; kpal_pair.hip: the distance of one pair, plain and
+// stat_plan.hpp, and the strand balance of one vector, which is a set of one; kpal_spectrum.hip: the count-of-counts spectrum of
+// every vector of a set, planned by spectrum_plan.hpp; kpal_pair.hip: the distance of one pair, plain and
 // with options; kpal_cross.hip: the distances
 // of sets of profiles, triangle and rectangle, planned by matrix_plan.hpp; kpal_nearest.hip: the nearest n of a rectangle,
 // tiled by nearest_plan.hpp; kpal_multi.hip: multi-GPU entry points over RCCL.)
@@ -207,6 +208,11 @@ struct kpal_ctx {
     // scratch for vector ops
     DevBuf scratch[4];
     DevBuf partials, result;
+    // the (value, number) pairs of the last kpal_distribution_set / _set_device, table after table (kpal_spectrum.hip): what
+    // kpal_distribution_fetch hands out
+    std::vector<int64_t> spec_values;
+    std::vector<uint64_t> spec_numbers;
+    bool spec_pending = false;
     DevBuf opt_l, opt_r, opt_levels, opt_profiles;   // ProfileDistance option pipeline
     DevBuf near_dist, near_best;             // kpal_nearest.hip: the finished distances of one tile (and the word of the Gram test behind them); the n best of a band's rows
     // the canonical tile pairs of the LDS-tiled balance kernels for the k they were last built for (kpal_vec.hip: canon_tiles)

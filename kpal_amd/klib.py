@@ -545,6 +545,30 @@ def strand_balances(profiles, pairwise='prod'):
     return out
 
 
+def distributions(profiles):
+    """``[metrics.distribution(p.counts) for p in profiles]`` -- the count-of-counts spectrum of every profile as a list of
+    ``(value, number)`` pairs of Python ints, values ascending -- with the integer profiles taken as SETS
+    (``kpal_distribution_set_device``: no sort, a number of launches that does not grow with the set) under the rules of
+    ``summaries``: a table that is still in HBM is used where it lies and stays there, host counts of one k-mer length are
+    uploaded in groups of at most ``_RECORD_BATCH_BYTES``, lengths may be mixed.  Profiles that are not integer counts
+    (scaled ones) take the ``Counter`` route of ``metrics.distribution``."""
+    profiles = list(profiles)
+    out = [None] * len(profiles)
+    sets = []
+    for i, p in enumerate(profiles):
+        # (uint64 counts would be ordered as int64 on the device: they keep the host route)
+        if _set_counts(p) and (p._device_counts() or np.asanyarray(p.counts).dtype != np.uint64):
+            sets.append(i)
+        else:
+            out[i] = metrics.distribution(p.counts)
+    for group, ctx, ptr, k in _device_sets(profiles, sets):
+        offsets, values, numbers = ctx.distribution_set_device(ptr, len(group), 4 ** k)
+        offsets, values, numbers = offsets.tolist(), values.tolist(), numbers.tolist()
+        for j, i in enumerate(group):
+            out[i] = list(zip(values[offsets[j]:offsets[j + 1]], numbers[offsets[j]:offsets[j + 1]]))
+    return out
+
+
 class Profile(object):
     """A k-mer profile: ``counts[i]`` is the count of the k-mer whose 2-bit big-endian encoding
     (A=0, C=1, G=2, T=3) is ``i`` (kpal/klib.py:26-61).

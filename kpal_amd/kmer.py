@@ -196,11 +196,10 @@ def get_stats(input_handle, output_handle, precision=10, names=None):
 def distribution(input_handle, output_handle, names=None):
     """Calculate the distribution of the values in k-mer profiles: ``name count number-of-k-mers`` lines.
 
-    (kpal/kmer.py:274-295.)"""
-    for name in _profile_names(input_handle, names):
-        profile = klib.Profile.from_file(input_handle, name=name)
-        print('\n'.join('{0} {1} {2}'.format(name, value, number)
-                        for value, number in metrics.distribution(profile.counts)), file=output_handle)
+    (kpal/kmer.py:274-295.)  The spectra of a group of profiles come from one set call on the device."""
+    for group in _profile_groups(input_handle, _profile_names(input_handle, names)):
+        for profile, pairs in zip(group, klib.distributions(group)):
+            print('\n'.join('{0} {1} {2}'.format(profile.name, value, number) for value, number in pairs), file=output_handle)
 
 
 def info(input_handle, output_handle, names=None):

@@ -18,7 +18,16 @@ from . import _native
 
 
 def distribution(vector):
-    """Sorted ``(value, count)`` pairs of ``vector`` (kpal/metrics.py:22-33)."""
+    """Sorted ``(value, count)`` pairs of ``vector`` (kpal/metrics.py:22-33).
+
+    A one-dimensional integer ``ndarray`` is counted on the GPU as a set of one table (``kpal_distribution_set``); the values
+    come back as scalars of the array's type, as ``Counter`` has them, the numbers as Python ints.  Everything else --
+    lists, float arrays, uint64 (whose order is not int64's) -- keeps the reference's ``Counter``.
+    """
+    if isinstance(vector, np.ndarray) and vector.ndim == 1 and vector.size and (
+            vector.dtype.kind in 'ib' or (vector.dtype.kind == 'u' and vector.dtype.itemsize < 8)):
+        _, values, numbers = _native.context().distribution_set(vector.reshape(1, -1))
+        return list(zip(values.astype(vector.dtype), numbers.tolist()))
     return sorted(Counter(vector).items())
 
 
