@@ -490,6 +490,30 @@ int kpal_merge_device(kpal_ctx *ctx, size_t n, const int64_t *dev_left, const in
 int kpal_shrink(kpal_ctx *ctx, int k, int factor, const int64_t *host_counts, int64_t *host_out);
 int kpal_shrink_device(kpal_ctx *ctx, int k, int factor, const int64_t *dev_counts, int64_t *dev_out);
 
+/* ---- new tables out of whole sets of tables in HBM: balance, shrink, pool ---- */
+/* Every entry takes n_tables tables lying one behind the other on the device, queues its launches on the context's stream
+ * and returns without waiting, like kpal_balance_device.  KPAL_E_INVALID, with nothing launched: a NULL pointer, n_tables == 0,
+ * k outside 1..KPAL_MAX_K, bins == 0, a pointer that is not 8-byte aligned, more bytes than a size_t counts, and an output that
+ * overlaps the input in a way the entry does not allow.  (The merge of two sets is kpal_merge_device over all their entries.)
+ *
+ * Profile.balance (kpal/klib.py:285-298) of every table: out[t][i] = in[t][i] + in[t][rc(i)], replacing a loop of
+ * kpal_balance_device calls by ONE launch -- for k >= 6 persistent workgroups over the flat list of (table, canonical tile
+ * pair), for k <= 5 one index over all bins.  dev_out == dev_in is allowed; any other overlap is KPAL_E_INVALID.  A table's
+ * result does not depend on the set it is in. */
+int kpal_balance_set_device(kpal_ctx *ctx, int k, size_t n_tables, const int64_t *dev_in /* n_tables x 4^k */,
+                            int64_t *dev_out /* n_tables x 4^k */);
+/* Profile.shrink(factor) (kpal/klib.py:329-352) of every table in one launch (from k = 12 on, where one launch over the whole
+ * set was measured to lose, in one per table: transform_plan.hpp): 1 <= factor < k (else KPAL_E_INVALID with the reference's
+ * ValueError text); dev_out has n_tables x 4^(k - factor) entries and must not overlap the input. */
+int kpal_shrink_set_device(kpal_ctx *ctx, int k, int factor, size_t n_tables, const int64_t *dev_in /* n_tables x 4^k */,
+                           int64_t *dev_out);
+/* Profile.merge with the sum merger (kpal/klib.py:269-283; kpal/metrics.py:174) folded over the set: out[j] = the sum over t
+ * of tables[t][j], int64 wrap; accumulate != 0: added onto what dev_out holds.  At most two launches whatever n_tables is: the
+ * tables are cut into slices (transform_plan.hpp) whose partial rows, in the context's scratch, a second launch adds.  dev_out
+ * has `bins` entries and must not overlap the tables. */
+int kpal_pool_set_device(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *dev_tables /* n_tables x bins */,
+                         int accumulate, int64_t *dev_out /* bins */);
+
 /* ---- per-kernel timing with HIP events on the ctx stream (bench.py roofline leg) ---- */
 int kpal_prof_enable(kpal_ctx *ctx, int on);
 int kpal_prof_reset(kpal_ctx *ctx);

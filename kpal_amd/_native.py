@@ -166,6 +166,9 @@ SIGNATURES = {
     'kpal_merge_device': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp, ctypes.c_int, _vp]),
     'kpal_shrink': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     'kpal_shrink_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    'kpal_balance_set_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_size_t, _vp, _vp]),
+    'kpal_shrink_set_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, _vp, _vp]),
+    'kpal_pool_set_device': (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_int, _vp]),
     'kpal_prof_enable': (ctypes.c_int, [_vp, ctypes.c_int]),
     'kpal_prof_reset': (ctypes.c_int, [_vp]),
     'kpal_prof_count': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
@@ -928,6 +931,21 @@ class Context(object):
     def shrink_device(self, k, factor, dev_in, dev_out):
         """kpal_shrink from 4**k int64 entries at dev_in into 4**(k-factor) at dev_out, both on the device."""
         _check(self._L.kpal_shrink_device(self._h, int(k), int(factor), _vp(dev_in), _vp(dev_out)))
+
+    def balance_set_device(self, k, n_tables, dev_in, dev_out):
+        """Profile.balance of n_tables consecutive 4**k tables at dev_in into dev_out (dev_out == dev_in: in place), one launch;
+        queued on the context's stream."""
+        _check(self._L.kpal_balance_set_device(self._h, int(k), int(n_tables), _vp(dev_in), _vp(dev_out)))
+
+    def shrink_set_device(self, k, factor, n_tables, dev_in, dev_out):
+        """Profile.shrink(factor) of n_tables consecutive 4**k tables at dev_in into n_tables x 4**(k-factor) entries at dev_out,
+        one launch; queued."""
+        _check(self._L.kpal_shrink_set_device(self._h, int(k), int(factor), int(n_tables), _vp(dev_in), _vp(dev_out)))
+
+    def pool_set_device(self, n_tables, bins, dev_tables, dev_out, accumulate=False):
+        """dev_out[j] (+)= the sum of n_tables consecutive int64 vectors of ``bins`` entries at dev_tables (int64 wrap), at most
+        two launches; queued."""
+        _check(self._L.kpal_pool_set_device(self._h, int(n_tables), int(bins), _vp(dev_tables), int(bool(accumulate)), _vp(dev_out)))
 
     def profile_distance_matrix(self, profiles, k, options):
         arrs = [_as_i64(p) for p in profiles]

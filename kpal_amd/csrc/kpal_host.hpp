@@ -5,7 +5,8 @@
 // kpal_quads.hip / kpal_quads2.hip: the quad record pipelines, planned by quad_plan.hpp; kpal_vec.hip: one vector -- balance,
 // split, summaries, merge, shrink; kpal_sets.hip: the summaries and the strand balance of a whole set of vectors, planned by
 // stat_plan.hpp, and the strand balance of one vector, which is a set of one; kpal_spectrum.hip: the count-of-counts spectrum of
-// every vector of a set, planned by spectrum_plan.hpp; kpal_pair.hip: the distance of one pair, plain and
+// every vector of a set, planned by spectrum_plan.hpp; kpal_transform.hip: the balance, the shrink and the pool of a whole set of
+// vectors, planned by transform_plan.hpp; kpal_pair.hip: the distance of one pair, plain and
 // with options; kpal_cross.hip: the distances
 // of sets of profiles, triangle and rectangle, planned by matrix_plan.hpp; kpal_nearest.hip: the nearest n of a rectangle,
 // tiled by nearest_plan.hpp; kpal_multi.hip: multi-GPU entry points over RCCL.)

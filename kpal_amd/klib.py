@@ -57,6 +57,7 @@ class _DeviceBatch(object):
 
     def __init__(self, ctx, nbytes, n_tables):
         self.ctx, self.nbytes, self.n_tables = ctx, int(nbytes), int(n_tables)
+        self.ptr = None            # (an allocation that raises leaves a batch that never counted: __del__)
         pool = getattr(ctx, '_table_pool', None)
         if pool and pool.get(self.nbytes):
             self.ptr = pool[self.nbytes].pop()
@@ -87,6 +88,8 @@ class _DeviceBatch(object):
 
     def __del__(self):
         try:
+            if self.ptr is None:
+                return
             _DeviceBatch.live_bytes -= self.nbytes
             ctx = self.ctx
             if getattr(ctx, '_h', None):           # (a context that has been closed took its allocations with it)
@@ -569,6 +572,211 @@ def distributions(profiles):
     return out
 
 
+# ---- new profiles out of whole sets: balance, shrink, merge, pool -------------------------------------------------------------
+# A result lives where its table lived.  A profile that is still in HBM gets row j of a NEW batch (the tables of a batch are
+# never written: copies and other rows share them, and _DeviceBatch._stats caches their summaries) and is re-pointed to it;
+# a profile with host integer counts is uploaded with its group, transformed and downloaded.  Everything else -- non-integer
+# counts, user mergers, shapes that do not match -- takes the method of the profile.
+def _no_repeats(profiles, who):
+    if len(set(id(p) for p in profiles)) != len(profiles):
+        raise ValueError('%s: a profile appears twice' % who)
+
+
+def _fresh_batch(ctx, n_tables, bins):
+    """A new batch of ``n_tables`` tables of ``bins`` entries on ``ctx``, or None when the budget of live device tables or the
+    allocation itself says no: the caller then takes the per-profile route."""
+    nbytes = 8 * bins * n_tables
+    if not _DEVICE_PROFILE_BYTES or _DeviceBatch.live_bytes + nbytes > _DEVICE_PROFILE_BYTES:
+        return None
+    try:
+        return _DeviceBatch(ctx, nbytes, n_tables)
+    except MemoryError:
+        return None
+
+
+def _repoint(profiles, group, batch, length):
+    for j, i in enumerate(group):
+        p = profiles[i]
+        p._counts, p._device, p.length = None, (batch, j, False), length
+
+
+def _by_placement(profiles, usable=_set_counts):
+    """Places of the profiles whose table is in HBM, of those with host integer counts, and of the rest."""
+    resident, host, other = [], [], []
+    for i, p in enumerate(profiles):
+        (resident if p._device_counts() else host if usable(p) else other).append(i)
+    return resident, host, other
+
+
+def balance_profiles(profiles):
+    """``for p in profiles: p.balance()`` with the integer profiles balanced as SETS (``kpal_balance_set_device``: one launch
+    per group) under the rules of ``summaries``: lengths may be mixed, groups hold at most ``_RECORD_BATCH_BYTES``.  A profile
+    that is still in HBM stays there, as a row of a new batch; host counts are written into the array the profile holds.  A
+    profile that appears twice is a ``ValueError``."""
+    profiles = list(profiles)
+    _no_repeats(profiles, 'balance_profiles')
+    resident, host, other = _by_placement(profiles)
+    for i in other:
+        profiles[i].balance()
+    for group, ctx, ptr, k in _device_sets(profiles, resident):
+        batch = _fresh_batch(ctx, len(group), 4 ** k)
+        if batch is None:
+            for i in group:
+                profiles[i].counts        # (downloaded: balance() takes the host route from here)
+                profiles[i].balance()
+            continue
+        ctx.balance_set_device(k, len(group), ptr, batch.ptr)
+        _repoint(profiles, group, batch, k)
+    for group, ctx, ptr, k in _device_sets(profiles, host):
+        ctx.balance_set_device(k, len(group), ptr, ptr)      # (host counts are gathered into an allocation of the group's own)
+        tables = np.empty((len(group), 4 ** k), dtype=np.int64)
+        ctx.d2h(tables, ptr)
+        for j, i in enumerate(group):
+            profiles[i].counts[...] = tables[j]
+
+
+def _shrink_arguments(length, factor):
+    if length <= factor:
+        raise ValueError('Reduction factor should be smaller than k-mer size.')
+    if factor < 0:    # the reference fails in range() with a float step (4 ** factor)
+        raise TypeError("'float' object cannot be interpreted as an integer")
+
+
+def shrink_profiles(profiles, factor=1):
+    """``for p in profiles: p.shrink(factor)`` with the integer profiles shrunk as SETS (``kpal_shrink_set_device``: one
+    launch per group) under the rules of ``balance_profiles``.  The errors of ``shrink`` are raised before any profile is
+    changed."""
+    profiles = list(profiles)
+    _no_repeats(profiles, 'shrink_profiles')
+    for p in profiles:
+        _shrink_arguments(p.length, factor)
+    if not isinstance(factor, (int, np.integer)) or factor == 0:
+        for p in profiles:
+            p.shrink(factor)
+        return
+    factor = int(factor)
+    resident, host, other = _by_placement(profiles)
+    for i in other:
+        profiles[i].shrink(factor)
+    for group, ctx, ptr, k in _device_sets(profiles, resident):
+        batch = _fresh_batch(ctx, len(group), 4 ** (k - factor))
+        if batch is None:
+            for i in group:
+                profiles[i].counts
+                profiles[i].shrink(factor)
+            continue
+        ctx.shrink_set_device(k, factor, len(group), ptr, batch.ptr)
+        _repoint(profiles, group, batch, k - factor)
+    for group, ctx, ptr, k in _device_sets(profiles, host):
+        tables = np.empty((len(group), 4 ** (k - factor)), dtype=np.int64)
+        out = ctx.alloc(tables.nbytes)
+        try:
+            ctx.shrink_set_device(k, factor, len(group), ptr, out)
+            ctx.d2h(tables, out)
+        finally:
+            ctx.free(out)
+        for j, i in enumerate(group):
+            profiles[i].counts = tables[j]       # (rows of one array, as the tables of a downloaded batch are)
+            profiles[i].length = k - factor
+
+
+def merge_profiles(profiles, others, merger=metrics.mergers['sum']):
+    """``for p, o in zip(profiles, others): p.merge(o, merger)`` for two lists of one length, the pairs of integer profiles
+    of one k-mer length merged as SETS (``kpal_merge_device`` over all entries of a group: one launch) under the rules of
+    ``balance_profiles``.  The result of a pair that is in HBM on both sides stays there.  User callables and pairs that do not
+    match in shape or are no integer counts take ``Profile.merge``."""
+    profiles, others = list(profiles), list(others)
+    if len(profiles) != len(others):
+        raise ValueError('merge_profiles: %d profiles, %d partners' % (len(profiles), len(others)))
+    _no_repeats(profiles, 'merge_profiles')
+    code = metrics.merger_code(merger)
+    if code is None or set(id(p) for p in profiles) & set(id(o) for o in others):
+        # (a partner that is itself merged into: the order of the loop is part of the result)
+        for p, o in zip(profiles, others):
+            p.merge(o, merger)
+        return
+    resident, host = {}, {}
+    for i, (p, o) in enumerate(zip(profiles, others)):
+        if not (_set_counts(p) and _set_counts(o) and p.length == o.length):
+            p.merge(o, merger)
+        elif p._device_counts() and o._device_counts():
+            resident.setdefault(p.length, []).append(i)
+        else:
+            host.setdefault(p.length, []).append(i)
+    for in_hbm, by_length in ((True, resident), (False, host)):
+        for k, places in sorted(by_length.items()):
+            bins, per = 4 ** k, max(1, _RECORD_BATCH_BYTES // (8 * 4 ** k))
+            for at in range(0, len(places), per):
+                group = places[at:at + per]
+                left, right = [profiles[i] for i in group], [others[i] for i in group]
+                ctx = kdistlib._cross_context(left + right)
+                batch = _fresh_batch(ctx, len(group), bins) if in_hbm else None
+                if in_hbm and batch is None:
+                    for p, o in zip(left, right):
+                        p.counts
+                        p.merge(o, merger)
+                    continue
+                lset = kdistlib._DeviceSet(ctx, left)
+                try:
+                    rset = kdistlib._DeviceSet(ctx, right)
+                    try:
+                        if in_hbm:
+                            ctx.merge_device(len(group) * bins, lset.ptr, rset.ptr, code, batch.ptr)
+                            _repoint(profiles, group, batch, k)
+                        else:
+                            # one side at least was gathered into an allocation of the group's own: the result goes there
+                            out = lset.ptr if lset.owned is not None else rset.ptr
+                            assert lset.owned is not None or rset.owned is not None
+                            ctx.merge_device(len(group) * bins, lset.ptr, rset.ptr, code, out)
+                            tables = np.empty((len(group), bins), dtype=np.int64)
+                            ctx.d2h(tables, out)
+                            for j, i in enumerate(group):
+                                profiles[i].counts = tables[j]
+                    finally:
+                        rset.release()
+                finally:
+                    lset.release()
+
+
+def pooled(profiles, name=None):
+    """A new profile: the sum of the tables of ``profiles`` (int64 wrap, as repeated ``merge`` with the sum merger), integer
+    profiles summed as SETS (``kpal_pool_set_device``: at most two launches per group of at most ``_RECORD_BATCH_BYTES``).
+    The per-record or per-read profiles of a file add up to the file's profile: no k-mer spans two records.  When every
+    profile is still in HBM, so is the result.  An empty list and mixed k-mer lengths are a ``ValueError``."""
+    profiles = list(profiles)
+    if not profiles:
+        raise ValueError('pooled: no profiles')
+    k = profiles[0].length
+    if any(p.length != k for p in profiles):
+        raise ValueError('pooled: profiles of different k-mer lengths')
+    if not all(_set_counts(p) for p in profiles):
+        total = np.array(profiles[0].counts)
+        for p in profiles[1:]:
+            total = metrics.mergers['sum'](total, p.counts)
+        return Profile(total, name=name)
+    bins = 4 ** k
+    ctx = kdistlib._cross_context(profiles)
+    batch = _fresh_batch(ctx, 1, bins) if all(p._device_counts() for p in profiles) else None
+    out = batch.ptr if batch is not None else ctx.alloc(8 * bins)
+    try:
+        per = max(1, _RECORD_BATCH_BYTES // (8 * bins))
+        for at in range(0, len(profiles), per):
+            members = profiles[at:at + per]
+            dset = kdistlib._DeviceSet(ctx, members)
+            try:
+                ctx.pool_set_device(len(members), bins, dset.ptr, out, accumulate=at > 0)
+            finally:
+                dset.release()
+        if batch is not None:
+            return Profile._from_device(batch, 0, k, name)
+        total = np.empty(bins, dtype=np.int64)
+        ctx.d2h(total, out)
+        return Profile(total, name=name)
+    finally:
+        if batch is None:
+            ctx.free(out)
+
+
 class Profile(object):
     """A k-mer profile: ``counts[i]`` is the count of the k-mer whose 2-bit big-endian encoding
     (A=0, C=1, G=2, T=3) is ``i`` (kpal/klib.py:26-61).
@@ -1025,6 +1233,10 @@ class Profile(object):
     def merge(self, profile, merger=metrics.mergers['sum']):
         """Merge another profile into this one with a vectorised merger (kpal/klib.py:269-283)."""
         code = metrics.merger_code(merger)
+        if (code is not None and profile is not self and self._device_counts() and profile._device_counts()
+                and self.length == profile.length):
+            merge_profiles([self], [profile], merger)             # both tables in HBM: a set of one pair, the result stays there
+            return
         l, r = np.asanyarray(self.counts), np.asanyarray(profile.counts)
         if code is not None and l.dtype.kind in 'iub' and r.dtype.kind in 'iub' and l.shape == r.shape and l.ndim == 1:
             self.counts = _native.context().merge(l, r, code)     # built-in merger: one HIP kernel
@@ -1046,7 +1258,11 @@ class Profile(object):
         """``counts[i] += counts[rc(i)]`` for every k-mer, palindromes doubled, in place
         (kpal/klib.py:285-298) -- one HIP kernel for integer counts.  Non-integer counts (a scaled
         profile) cannot enter the integer kernel: they take the same sums as one NumPy expression, in
-        the dtype of ``counts`` like the reference's loop."""
+        the dtype of ``counts`` like the reference's loop.  A table that is still in HBM is balanced there, as a set of one
+        (``balance_profiles``), and stays there."""
+        if self._device_counts():
+            balance_profiles([self])
+            return
         c = np.asanyarray(self.counts)
         if c.dtype.kind not in 'iub':
             c[...] = c + c[self._rc_index()]
@@ -1075,10 +1291,10 @@ class Profile(object):
     # ---- container helpers ----------------------------------------------------------------------
     def shrink(self, factor=1):
         """Reduce k by ``factor`` by summing groups of ``4**factor`` bins (kpal/klib.py:329-352)."""
-        if self.length <= factor:
-            raise ValueError('Reduction factor should be smaller than k-mer size.')
-        if factor < 0:    # the reference fails in range() with a float step (4 ** factor)
-            raise TypeError("'float' object cannot be interpreted as an integer")
+        _shrink_arguments(self.length, factor)
+        if self._device_counts() and isinstance(factor, (int, np.integer)) and factor > 0:
+            shrink_profiles([self], factor)                       # still in HBM: a set of one, the result stays there
+            return
         c = np.asanyarray(self.counts)
         if factor == 0:   # groups of one: a fresh int64 copy
             self.counts = np.array(c, dtype='int64')

@@ -156,11 +156,11 @@ def merge(input_handle_left, input_handle_right, output_handle, names_left=None,
 
 
 def balance(input_handle, output_handle, names=None):
-    """Balanced copies of the profiles of a file (kpal/kmer.py:203-219)."""
-    for name in _profile_names(input_handle, names):
-        profile = klib.Profile.from_file(input_handle, name=name)
-        profile.balance()
-        profile.save(output_handle)
+    """Balanced copies of the profiles of a file (kpal/kmer.py:203-219), a group of profiles balanced by one launch."""
+    for group in _profile_groups(input_handle, _profile_names(input_handle, names)):
+        klib.balance_profiles(group)
+        for profile in group:
+            profile.save(output_handle)
 
 
 def _profile_groups(input_handle, names):
@@ -287,11 +287,11 @@ def scale(input_handle_left, input_handle_right, output_handle_left, output_hand
 def shrink(input_handle, output_handle, factor, names=None):
     """Shrink k-mer profiles, effectively reducing k.
 
-    (kpal/kmer.py:447-464.)"""
-    for name in _profile_names(input_handle, names):
-        profile = klib.Profile.from_file(input_handle, name=name)
-        profile.shrink(factor)
-        profile.save(output_handle)
+    (kpal/kmer.py:447-464.)  A group of profiles is shrunk by one launch."""
+    for group in _profile_groups(input_handle, _profile_names(input_handle, names)):
+        klib.shrink_profiles(group, factor)
+        for profile in group:
+            profile.save(output_handle)
 
 
 def shuffle(input_handle, output_handle, names=None):
