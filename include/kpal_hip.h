@@ -419,6 +419,31 @@ int kpal_cross_smooth_distance_device(kpal_ctx *ctx, int k, int Q, const int64_t
                                       double *out /* host, Q x R, row-major */);
 int kpal_smooth_distance_matrix_device(kpal_ctx *ctx, int P, int k, const int64_t *dev_profiles /* P x 4^k */,
                                        const kpal_distance_options *opt, double *out_lower);
+/* The distances of the LINKED pairs of two sets: out[i] = ProfileDistance.distance(left[i], right[i]) (kdistlib.py:126-161)
+ * for all i -- the loop of `kpal distance` (kmer.py:541-620) over two files, or over one set against itself shifted by a lag.
+ * N consecutive 16-byte aligned tables a side.  A chunk of pairs is a fixed number of launches whatever N is: one metric
+ * kernel over all (pair, slice) items and one reduction; with scale a totals kernel (masked under positive) and its
+ * reduction before them, the pairs' factors derived on the device; with do_balance one launch of the set balance per
+ * distinct input range before those, into the context's scratch.  The two ranges may alias or overlap in any way and are
+ * never written: when they are the same range, or lie a whole number of tables apart (right == left +- lag * 4^k * 8
+ * bytes: successive windows), the union of the two ranges is balanced once and both sides point into it.  A set against
+ * itself gives zeros (NaN where the pair entry gives NaN).
+ *   A slice is a fixed run of bins and a pair's slices are added in slice order: the value of a pair depends on its two
+ * tables and the options alone -- the same bits in a set of 1 or of 10^5, at any position, under any chunk_pairs.  Unscaled
+ * euclidean and cosine are int64 sums, bit for bit what kpal_profile_distance_device returns; everything else is within 1e-9
+ * relative of the reference (exactly 0, the same NaN and the same infinity where it gives them).
+ *   chunk_pairs: 0 takes the plan's chunk (with do_balance: as many pairs as keep the balanced copies within 32 GiB, never
+ * less than one); > 0 only lowers it.
+ *   With do_smooth the pair pipeline of kpal_profile_distance_device runs once per pair on the once-balanced tables -- exactly
+ * what kpal_cross_profile_distance_device does for its pairs; a smoothed pair kernel over per-profile pyramids is not here.
+ *   The host variant uploads both sides through the context's scratch, as kpal_cross_profile_distance does.
+ * KPAL_E_INVALID, before anything is launched: N < 1, k outside 1 .. KPAL_MAX_K, a NULL pointer, tables not 16-byte aligned,
+ * options kpal_profile_distance refuses, chunk_pairs < 0, byte sizes that do not fit. */
+int kpal_paired_distance_device(kpal_ctx *ctx, int k, int64_t N, const int64_t *dev_left /* N x 4^k */,
+                                const int64_t *dev_right /* N x 4^k */, const kpal_distance_options *opt,
+                                int64_t chunk_pairs /* 0: the plan's; > 0 only lowers it */, double *out /* host, N */);
+int kpal_paired_distance(kpal_ctx *ctx, int k, int64_t N, const int64_t *const *host_left,
+                         const int64_t *const *host_right, const kpal_distance_options *opt, double *out /* host, N */);
 
 /* ---- profile summaries, merge, shrink ---- */
 /* Profile.total / non_zero / mean / median / std (kpal/klib.py:193-225) of one int64 vector in two

@@ -153,6 +153,9 @@ SIGNATURES = {
     'kpal_cross_smooth_distance_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, _optp,
                                                          _f64p]),
     'kpal_smooth_distance_matrix_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _optp, _f64p]),
+    'kpal_paired_distance': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _optp,
+                                            _f64p]),
+    'kpal_paired_distance_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _optp, ctypes.c_int64, _f64p]),
     'kpal_stats': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _statp]),
     'kpal_stats_device': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _statp]),
     'kpal_stats_set': (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _statp]),
@@ -778,6 +781,30 @@ class Context(object):
         out = np.zeros((int(Q), int(R)), dtype=np.float64)
         _check(self._L.kpal_cross_smooth_distance_device(self._h, int(k), int(Q), _vp(dev_left), int(R), _vp(dev_right),
                                                          ctypes.byref(options), out.ctypes.data_as(_f64p)))
+        return out
+
+    def paired_distance(self, left, right, k, options):
+        """paired_distance_device for two equally long lists of int64[4**k] host vectors."""
+        la, ra = [_as_i64(p) for p in left], [_as_i64(p) for p in right]
+        if len(la) != len(ra):
+            raise ValueError('%d left profiles against %d right profiles' % (len(la), len(ra)))
+        for a in la + ra:
+            if a.size != 4 ** k:
+                raise ValueError('profile length %d != 4**%d' % (a.size, k))
+        N = len(la)
+        out = np.zeros(N, dtype=np.float64)
+        lp = (_vp * N)(*[a.ctypes.data for a in la])
+        rp = (_vp * N)(*[a.ctypes.data for a in ra])
+        _check(self._L.kpal_paired_distance(self._h, int(k), N, lp, rp, ctypes.byref(options), out.ctypes.data_as(_f64p)))
+        return out
+
+    def paired_distance_device(self, k, N, dev_left, dev_right, options, chunk_pairs=0):
+        """dev_left, dev_right: N consecutive tables each (device addresses; they may alias) -> float64[N], [i] =
+        ProfileDistance.distance(left[i], right[i]) for a DistanceOptions, a number of launches that does not grow with N.
+        ``chunk_pairs`` > 0 only lowers the pairs the library takes at a time."""
+        out = np.zeros(int(N), dtype=np.float64)
+        _check(self._L.kpal_paired_distance_device(self._h, int(k), int(N), _vp(dev_left), _vp(dev_right), ctypes.byref(options),
+                                                   int(chunk_pairs), out.ctypes.data_as(_f64p)))
         return out
 
     @staticmethod

@@ -17,25 +17,9 @@
 // kOptTotals: the two masked totals (int64).
 #pragma once
 #include "cross_kernels.hpp"
+#include "option_term.hpp"   // kOptTotals, cross_opt_scale, the mask and the term of a bin
 
 namespace kpal {
-
-constexpr int kOptTotals = 4;   // MODE of the masked-totals pass (0 .. 3: KPAL_PAIRWISE_PROD .. KPAL_COSINE)
-
-// metrics.get_scale (metrics.py:49-72: int64 totals, true division) and metrics.scale_down (metrics.py:75-86), evaluated
-// as profile_distance_pair does on the host.
-__device__ __forceinline__ void cross_opt_scale(int64_t tl, int64_t tr, bool down, double &ls, double &rs)
-{
-    ls = 1.0;
-    rs = 1.0;
-    if (tl < tr) ls = (double)tr / (double)tl;
-    else rs = (double)tl / (double)tr;
-    if (down) {
-        const double top = ls > rs ? ls : rs;
-        ls /= top;
-        rs /= top;
-    }
-}
 
 template <int MODE, bool SCALED, bool POSITIVE>
 struct OptAcc {
@@ -84,50 +68,15 @@ struct OptAcc {
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 int64_t xi = x[a], yi = y[b];
-                if constexpr (POSITIVE || MODE == kOptTotals) {
-                    const bool both = xi != 0 && yi != 0;
-                    xi = both ? xi : 0;
-                    yi = both ? yi : 0;
-                }
+                opt_mask<POSITIVE || MODE == kOptTotals>(xi, yi);
                 term(a, b, xi, yi);
             }
     }
     // the term of pair (a, b) for the counts (xi, yi) that are left of a bin
     __device__ __forceinline__ void term(int a, int b, int64_t xi, int64_t yi)
     {
-        if constexpr (MODE == kOptTotals) {
-            m[0][a][b] += (uint64_t)xi;
-            m[1][a][b] += (uint64_t)yi;
-        } else if constexpr (SCALED) {
-            const double xd = (double)xi * ls[a][b], yd = (double)yi * rs[a][b];
-            if constexpr (MODE <= 1) {
-                if (xd != 0.0 || yd != 0.0) {
-                    s[0][a][b] += MODE == 0 ? pw_prod(xd, yd) : pw_sum(xd, yd);
-                    m[0][a][b] += 1;
-                }
-            } else if constexpr (MODE == 2) {
-                const double d = xd - yd;
-                s[0][a][b] += d * d;
-            } else {
-                s[0][a][b] += xd * yd;
-                s[1][a][b] += xd * xd;
-                s[2][a][b] += yd * yd;
-            }
-        } else {
-            if constexpr (MODE <= 1) {
-                if (xi != 0 || yi != 0) {
-                    s[0][a][b] += MODE == 0 ? pw_prod(xi, yi) : pw_sum(xi, yi);
-                    m[0][a][b] += 1;
-                }
-            } else if constexpr (MODE == 2) {
-                const uint64_t d = (uint64_t)xi - (uint64_t)yi;
-                m[0][a][b] += d * d;
-            } else {
-                m[0][a][b] += (uint64_t)xi * (uint64_t)yi;
-                m[1][a][b] += (uint64_t)xi * (uint64_t)xi;
-                m[2][a][b] += (uint64_t)yi * (uint64_t)yi;
-            }
-        }
+        constexpr int n1 = NACC > 1 ? 1 : 0, n2 = NACC - 1;   // (the accumulators a MODE lacks: one it has, untouched)
+        opt_term<MODE, SCALED>(xi, yi, ls[a][b], rs[a][b], s[0][a][b], s[n1][a][b], s[n2][a][b], m[0][a][b], m[n1][a][b], m[n2][a][b]);
     }
     __device__ __forceinline__ void finish() {}
     __device__ __forceinline__ Partial partial(int n, int a, int b) const { return Partial{s[n][a][b], m[n][a][b]}; }

@@ -8,7 +8,8 @@
 // every vector of a set, planned by spectrum_plan.hpp; kpal_transform.hip: the balance, the shrink and the pool of a whole set of
 // vectors, planned by transform_plan.hpp; kpal_pair.hip: the distance of one pair, plain and
 // with options; kpal_cross.hip: the distances
-// of sets of profiles, triangle and rectangle, planned by matrix_plan.hpp; kpal_nearest.hip: the nearest n of a rectangle,
+// of sets of profiles, triangle and rectangle, planned by matrix_plan.hpp; kpal_paired.hip: the distances of the linked pairs of
+// two sets, planned by pair_set_plan.hpp; kpal_nearest.hip: the nearest n of a rectangle,
 // tiled by nearest_plan.hpp; kpal_multi.hip: multi-GPU entry points over RCCL.)
 #pragma once
 #include "../../include/kpal_hip.h"
@@ -388,6 +389,7 @@ int count_end_text(kpal_ctx *ctx);                                        // kpa
 int table_ready(kpal_ctx *ctx);                                           // kpal_quads2.hip: zeros materialised, pending finalisation done: the table is the table
 int launch_balance(kpal_ctx *ctx, int k, const int64_t *in, int64_t *out);   // kpal_vec.hip
 int canon_tiles(kpal_ctx *ctx, int k, int per_cu, const uint32_t **list, uint32_t *count, unsigned *grid);   // kpal_vec.hip: the canonical tile pairs of the LDS-tiled balance family (k >= 6), the grid for per_cu workgroups on a CU
+int balance_set_launch(kpal_ctx *ctx, int k, size_t n_tables, const int64_t *dev_in, int64_t *dev_out);   // kpal_transform.hip: the one launch behind kpal_balance_set_device (nothing checked)
 int check_options(const kpal_distance_options *opt);                       // kpal_pair.hip
 int profile_distance_pair(kpal_ctx *ctx, int k, const int64_t *dl, const int64_t *dr, const kpal_distance_options *opt, bool balanced,
                           double *out);   // kpal_pair.hip: the option pipeline of one pair of 16-byte aligned device tables (balanced: do_balance is not applied again)

@@ -18,13 +18,10 @@ static int transform_set_check(int k, size_t n_tables, const int64_t *in, const 
     return KPAL_OK;
 }
 
-KPAL_API int kpal_balance_set_device(kpal_ctx *ctx, int k, size_t n_tables, const int64_t *dev_in, int64_t *dev_out)
+// The balance of n_tables consecutive tables (checked by the caller; dev_out the input itself or disjoint from it): one launch.
+int balance_set_launch(kpal_ctx *ctx, int k, size_t n_tables, const int64_t *dev_in, int64_t *dev_out)
 {
-    CTX_ENTER(ctx);
-    CHK(transform_set_check(k, n_tables, dev_in, dev_out));
     const uint64_t total = (uint64_t)n_tables << (2 * k);
-    if (transform_overlap((uint64_t)(uintptr_t)dev_in, total * 8, (uint64_t)(uintptr_t)dev_out, total * 8) == kTransformPartial)
-        return set_err(KPAL_E_INVALID, "balance of a set: the output overlaps the input without being the input");
     if (k <= kBalanceSetSmallMaxK) {
         LAUNCH(ctx, "balance_set", balance_set_kernel, dim3(stream_grid(ctx, total)), dim3(256), dev_in, dev_out, k, total);
         return KPAL_OK;
@@ -37,6 +34,16 @@ KPAL_API int kpal_balance_set_device(kpal_ctx *ctx, int k, size_t n_tables, cons
     const uint64_t grid = balance_set_workgroups(items, balance_set_slots((uint64_t)ctx->num_cu));
     LAUNCH(ctx, "balance_tiled_set", balance_tiled_set_kernel, dim3((unsigned)grid), dim3(kBalanceSetThreads), dev_in, dev_out, k, canon, ncanon, items);
     return KPAL_OK;
+}
+
+KPAL_API int kpal_balance_set_device(kpal_ctx *ctx, int k, size_t n_tables, const int64_t *dev_in, int64_t *dev_out)
+{
+    CTX_ENTER(ctx);
+    CHK(transform_set_check(k, n_tables, dev_in, dev_out));
+    const uint64_t total = (uint64_t)n_tables << (2 * k);
+    if (transform_overlap((uint64_t)(uintptr_t)dev_in, total * 8, (uint64_t)(uintptr_t)dev_out, total * 8) == kTransformPartial)
+        return set_err(KPAL_E_INVALID, "balance of a set: the output overlaps the input without being the input");
+    return balance_set_launch(ctx, k, n_tables, dev_in, dev_out);
 }
 
 KPAL_API int kpal_shrink_set_device(kpal_ctx *ctx, int k, int factor, size_t n_tables, const int64_t *dev_in, int64_t *dev_out)

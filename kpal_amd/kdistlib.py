@@ -15,7 +15,9 @@ distances between a left and a right set of profiles (``kpal_cross_distance_devi
 ``kpal_cross_profile_distance_device``; with dynamic smoothing ``kpal_cross_smooth_distance_device``), a fixed number of
 launches per chunk of the right side.  :func:`nearest_chunks` / :func:`nearest_profiles` -- the n nearest right profiles of
 every left profile without that rectangle on the host (``kpal_cross_nearest_device``: tiled over both sides, finished and
-selected on the device), the left side streamed.
+selected on the device), the left side streamed.  :func:`paired_distances` / :func:`successive_distances` -- the distances of the
+LINKED pairs of two sets, ``left[i]`` against ``right[i]``, or of one set against itself ``lag`` profiles on
+(``kpal_paired_distance_device``: a number of launches that does not grow with the number of pairs).
 """
 import numpy as np
 
@@ -328,6 +330,81 @@ def cross_distances(left_profiles, right_profiles, dist, max_bytes=None):
     if not blocks:
         return np.zeros((len(left), 0), dtype=np.float64)
     return np.concatenate(blocks, axis=1)
+
+
+def _paired_options(dist, profiles):
+    """The ``kpal_distance_options`` of ``dist`` when the set entries can serve ``profiles`` -- built-ins only, one k, integer
+    counts or tables in HBM -- else None."""
+    options = dist._native_options()
+    if options is None or not profiles:
+        return None
+    k = profiles[0].length
+    if not all(p.length == k and _integer_counts(p) for p in profiles):
+        return None
+    return options
+
+
+def paired_distances(left_profiles, right_profiles, dist, max_bytes=None):
+    """``values[i] = dist.distance(left_profiles[i], right_profiles[i])`` as a float64 array of shape (N,): what ``kpal
+    distance`` prints for two files of N profiles each.  Sides of unequal length raise ``ValueError``.
+
+    With a ``dist`` made of built-ins over integer profiles of one k this is ``kpal_paired_distance_device``: per group of pairs
+    one metric kernel over all pairs and one reduction (with scale a totals kernel and its reduction before them, with
+    ``do_balance`` one set balance per side), whatever the number of pairs; a pair's value is the same bits in any set, at any
+    position.  Tables that are consecutive in one device batch are used where they lie; anything else is gathered (host counts
+    uploaded) in groups of at most ``max_bytes`` of tables over both sides (default ``CROSS_MAX_BYTES``, never less than one
+    pair).  Dynamic smoothing runs the pair pipeline once per pair inside the library.  A user-supplied callable, a non-numeric
+    threshold, mixed k or non-integer counts are ``dist.distance`` pair by pair -- and so is a single pair, which keeps the
+    route and the bits of ``dist.distance``."""
+    left, right = list(left_profiles), list(right_profiles)
+    if len(left) != len(right):
+        raise ValueError('paired_distances needs as many left as right profiles ({0} against {1})'.format(len(left), len(right)))
+    options = _paired_options(dist, left + right) if len(left) > 1 else None
+    if options is None:
+        return np.array([dist.distance(l, r) for l, r in zip(left, right)], dtype=np.float64).reshape(len(left))
+    k = left[0].length
+    per = _chunk_tables(2 * 8 * 4 ** k, CROSS_MAX_BYTES if max_bytes is None else max_bytes)
+    ctx = _cross_context(left + right)
+    blocks = []
+    for at in range(0, len(left), per):
+        lgroup, rgroup = left[at:at + per], right[at:at + per]
+        lset = _DeviceSet(ctx, lgroup)
+        try:
+            rset = lset if all(a is b for a, b in zip(lgroup, rgroup)) else _DeviceSet(ctx, rgroup)
+            try:
+                blocks.append(ctx.paired_distance_device(k, len(lgroup), lset.ptr, rset.ptr, options))
+            finally:
+                if rset is not lset:
+                    rset.release()
+        finally:
+            lset.release()
+    return np.concatenate(blocks)
+
+
+def successive_distances(profiles, dist, lag=1):
+    """``values[i] = dist.distance(profiles[i], profiles[i + lag])`` as a float64 array of shape (N - lag,): the compositional
+    breakpoint scan over the windows of ``Profile.from_fasta_by_window``.  ``lag < 1`` and ``lag >= N`` raise ``ValueError``.
+
+    Under the conditions of :func:`paired_distances` the profiles are made ONE set (used where they lie when they are consecutive
+    tables of one device batch) and the library is given that set and the same set ``lag`` tables on: with ``do_balance`` it
+    balances the N tables once, not the two sides of N - ``lag`` each."""
+    profiles = list(profiles)
+    lag = int(lag)
+    if lag < 1:
+        raise ValueError('successive_distances needs lag >= 1')
+    if lag >= len(profiles):
+        raise ValueError('successive_distances needs more than lag = {0} profiles ({1} given)'.format(lag, len(profiles)))
+    pairs = len(profiles) - lag
+    options = _paired_options(dist, profiles) if pairs > 1 else None
+    if options is None:
+        return np.array([dist.distance(profiles[i], profiles[i + lag]) for i in range(pairs)], dtype=np.float64)
+    k = profiles[0].length
+    ctx = _cross_context(profiles)
+    pset = _DeviceSet(ctx, profiles)
+    try:
+        return ctx.paired_distance_device(k, pairs, pset.ptr, pset.ptr + lag * 8 * 4 ** k, options)
+    finally:
+        pset.release()
 
 
 def nearest(values, n):

@@ -338,19 +338,36 @@ def distance(input_handle_left, input_handle_right, output_handle, names_left=No
              custom_summary=None, threshold=0, do_scale=False, down=False, do_positive=False, do_balance=False,
              precision=10):
     """``left right distance`` lines for the profiles of two files, linked pairwise
-    (kpal/kmer.py:541-620)."""
+    (kpal/kmer.py:541-620).  Both files are read in groups of at most ``klib._RECORD_BATCH_BYTES`` of counts over both sides;
+    a group's distances come from one set call on the device."""
     names_left = _profile_names(input_handle_left, names_left)
     names_right = _profile_names(input_handle_right, names_right)
     if len(names_left) != len(names_right):
         raise ValueError(PAIRED_NAMES_COUNT_ERROR)
     dist = _profile_distance(distance_function, pairwise, custom_pairwise, do_smooth, summary, custom_summary,
                              threshold, do_scale, down, do_positive, do_balance)
+    names, lefts, rights, size = [], [], [], 0
+
+    def flush():
+        # a group of pairs is one set call (kdistlib.paired_distances); the lines are those of the loop over dist.distance
+        for pair, value in zip(names, kdistlib.paired_distances(lefts, rights, dist)):
+            print(pair[0], pair[1], _fixed(precision, value), file=output_handle)
+        del names[:], lefts[:], rights[:]
+
     for name_left, name_right in zip(names_left, names_right):
         left = klib.Profile.from_file(input_handle_left, name=name_left)
         right = klib.Profile.from_file(input_handle_right, name=name_right)
         if left.length != right.length:
+            flush()      # the lines of all earlier pairs are written before the error, as the pair-by-pair loop wrote them
             raise ValueError(LENGTH_ERROR)
-        print(name_left, name_right, _fixed(precision, dist.distance(left, right)), file=output_handle)
+        names.append((name_left, name_right))
+        lefts.append(left)
+        rights.append(right)
+        size += np.asanyarray(left.counts).nbytes + np.asanyarray(right.counts).nbytes
+        if size >= klib._RECORD_BATCH_BYTES:
+            flush()
+            size = 0
+    flush()
 
 
 def distance_matrix(input_handle, output_handle, names=None, distance_function='default', pairwise='prod',
