@@ -435,7 +435,8 @@ int kpal_smooth_distance_matrix_device(kpal_ctx *ctx, int P, int k, const int64_
  *   chunk_pairs: 0 takes the plan's chunk (with do_balance: as many pairs as keep the balanced copies within 32 GiB, never
  * less than one); > 0 only lowers it.
  *   With do_smooth the pair pipeline of kpal_profile_distance_device runs once per pair on the once-balanced tables -- exactly
- * what kpal_cross_profile_distance_device does for its pairs; a smoothed pair kernel over per-profile pyramids is not here.
+ * what kpal_cross_profile_distance_device does for its pairs; the smoothed pair kernel over per-profile pyramids is
+ * kpal_paired_smooth_distance_device, below.
  *   The host variant uploads both sides through the context's scratch, as kpal_cross_profile_distance does.
  * KPAL_E_INVALID, before anything is launched: N < 1, k outside 1 .. KPAL_MAX_K, a NULL pointer, tables not 16-byte aligned,
  * options kpal_profile_distance refuses, chunk_pairs < 0, byte sizes that do not fit. */
@@ -444,6 +445,35 @@ int kpal_paired_distance_device(kpal_ctx *ctx, int k, int64_t N, const int64_t *
                                 int64_t chunk_pairs /* 0: the plan's; > 0 only lowers it */, double *out /* host, N */);
 int kpal_paired_distance(kpal_ctx *ctx, int k, int64_t N, const int64_t *const *host_left,
                          const int64_t *const *host_right, const kpal_distance_options *opt, double *out /* host, N */);
+/* kpal_paired_distance[_device] for an option set WITH dynamic smoothing in a number of launches that does not grow with N:
+ * same arguments, same checks with the same messages, same values.  Without do_smooth, and with do_positive (the masks come
+ * first: node sums depend on the partner), the call is handed to kpal_paired_distance_device.  Otherwise, per chunk of pairs:
+ * with do_balance the set balance exactly as that entry runs it; the pyramids of node sums and codes of the chunk's DISTINCT
+ * tables (kpal_cross_smooth_distance_device) -- when the ranges are the same range or lie a whole number of tables apart,
+ * of their union once, so successive windows build N pyramids; ranges that alias in any other way are read as they lie --
+ * in k + 1 launches; ONE metric kernel over all (pair, slice) items -- a pair's bin slices, then the slices of its two
+ * pyramids -- and ONE reduction.  No totals pass under scale: smoothing conserves totals and the roots are the totals.
+ *   A pair's slices depend on k alone and are added in slice order: the bits of a pair depend on its two tables and the
+ * options, not on N, its position, chunk_pairs or the aliasing.  Unscaled euclidean and cosine are int64 sums, bit for bit
+ * what kpal_profile_distance_device returns; everything else within 1e-9 relative of the reference (exactly 0, the same NaN
+ * and infinity).  chunk_pairs: the chunk of kpal_paired_distance_device, cut further so that the pyramids of a chunk stay
+ * within 32 GiB (never below one pair); > 0 only lowers it. */
+int kpal_paired_smooth_distance_device(kpal_ctx *ctx, int k, int64_t N, const int64_t *dev_left /* N x 4^k */,
+                                       const int64_t *dev_right /* N x 4^k */, const kpal_distance_options *opt,
+                                       int64_t chunk_pairs, double *out /* host, N */);
+int kpal_paired_smooth_distance(kpal_ctx *ctx, int k, int64_t N, const int64_t *const *host_left,
+                                const int64_t *const *host_right, const kpal_distance_options *opt,
+                                double *out /* host, N */);
+/* The effect of ProfileDistance.dynamic_smooth(left[i], right[i]) (kdistlib.py:53-124) on copies, for all i: the pyramids
+ * as above, then ONE kernel that writes both smoothed sets -- a bin no node above which collapses keeps its count, the first
+ * bin of a collapsed node holds the node's sum (wrapping int64), every other bin is 0.  The inputs may alias in any way and
+ * are never written (table j under a lag is smoothed differently as the left of pair j and as the right of pair j - lag:
+ * hence two whole output sets).  Queued on the context's stream.  KPAL_E_INVALID before any launch: what
+ * kpal_paired_distance_device refuses, summary outside KPAL_SUMMARY_*, outputs that are not 16-byte aligned or that overlap
+ * each other or an input. */
+int kpal_paired_smooth_device(kpal_ctx *ctx, int k, int64_t N, const int64_t *dev_left /* N x 4^k */,
+                              const int64_t *dev_right /* N x 4^k */, int summary, double threshold, int64_t chunk_pairs,
+                              int64_t *dev_out_left /* N x 4^k */, int64_t *dev_out_right /* N x 4^k */);
 
 /* ---- profile summaries, merge, shrink ---- */
 /* Profile.total / non_zero / mean / median / std (kpal/klib.py:193-225) of one int64 vector in two

@@ -156,6 +156,12 @@ SIGNATURES = {
     'kpal_paired_distance': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _optp,
                                             _f64p]),
     'kpal_paired_distance_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _optp, ctypes.c_int64, _f64p]),
+    'kpal_paired_smooth_distance': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _optp,
+                                                   _f64p]),
+    'kpal_paired_smooth_distance_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _optp, ctypes.c_int64,
+                                                          _f64p]),
+    'kpal_paired_smooth_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, ctypes.c_int, ctypes.c_double,
+                                                 ctypes.c_int64, _vp, _vp]),
     'kpal_stats': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _statp]),
     'kpal_stats_device': (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _statp]),
     'kpal_stats_set': (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _statp]),
@@ -806,6 +812,35 @@ class Context(object):
         _check(self._L.kpal_paired_distance_device(self._h, int(k), int(N), _vp(dev_left), _vp(dev_right), ctypes.byref(options),
                                                    int(chunk_pairs), out.ctypes.data_as(_f64p)))
         return out
+
+    def paired_smooth_distance(self, left, right, k, options):
+        """paired_smooth_distance_device for two equally long lists of int64[4**k] host vectors."""
+        la, ra = [_as_i64(p) for p in left], [_as_i64(p) for p in right]
+        if len(la) != len(ra):
+            raise ValueError('%d left profiles against %d right profiles' % (len(la), len(ra)))
+        for a in la + ra:
+            if a.size != 4 ** k:
+                raise ValueError('profile length %d != 4**%d' % (a.size, k))
+        N = len(la)
+        out = np.zeros(N, dtype=np.float64)
+        lp = (_vp * N)(*[a.ctypes.data for a in la])
+        rp = (_vp * N)(*[a.ctypes.data for a in ra])
+        _check(self._L.kpal_paired_smooth_distance(self._h, int(k), N, lp, rp, ctypes.byref(options), out.ctypes.data_as(_f64p)))
+        return out
+
+    def paired_smooth_distance_device(self, k, N, dev_left, dev_right, options, chunk_pairs=0):
+        """paired_distance_device with dynamic smoothing from one pyramid per distinct table: launches that do not grow with N
+        (positive + smoothing keeps that entry's pair pipeline per pair; without do_smooth the call is that entry's)."""
+        out = np.zeros(int(N), dtype=np.float64)
+        _check(self._L.kpal_paired_smooth_distance_device(self._h, int(k), int(N), _vp(dev_left), _vp(dev_right), ctypes.byref(options),
+                                                          int(chunk_pairs), out.ctypes.data_as(_f64p)))
+        return out
+
+    def paired_smooth_device(self, k, N, dev_left, dev_right, summary, threshold, dev_out_left, dev_out_right, chunk_pairs=0):
+        """The tables ProfileDistance.dynamic_smooth(left[i], right[i]) leaves, for all i, into two disjoint device sets of N
+        tables each (queued); the inputs (device addresses; they may alias) are not written."""
+        _check(self._L.kpal_paired_smooth_device(self._h, int(k), int(N), _vp(dev_left), _vp(dev_right), int(summary), float(threshold),
+                                                 int(chunk_pairs), _vp(dev_out_left), _vp(dev_out_right)))
 
     @staticmethod
     def _nearest_buffers(Q, n, dist, index):

@@ -497,13 +497,34 @@ static int launch_smooth_pass(kpal_ctx *ctx, bool staged, bool scaled, const Cro
     return scaled ? launch_cross<SmoothAcc<MODE, true>>(ctx, name, staged, o, g, pp) : launch_cross<SmoothAcc<MODE, false>>(ctx, name, staged, o, g, pp);
 }
 
+// The pyramids of the nprof profiles of c (smooth_set_kernels.hpp: left 0 .. Q-1, then right; nprof = Q reads the left set
+// alone) in the context's opt_levels, their roots in scratch[3]: k level launches and the codes launch.
+int smooth_set_pyramids(kpal_ctx *ctx, int k, const CrossSets &c, uint32_t nprof, int summary, double threshold, SmoothPyramids *out)
+{
+    const uint64_t stride = smooth_stride(k), elements = (uint64_t)nprof * stride;
+    CHK(ensure(ctx, ctx->opt_levels, (size_t)smooth_scratch_bytes(k, nprof)));
+    CHK(ensure(ctx, ctx->scratch[3], (size_t)nprof * sizeof(Partial)));
+    int64_t *sums = (int64_t *)ctx->opt_levels.p;
+    uint8_t *codes = (uint8_t *)(sums + elements);
+    Partial *totals = (Partial *)ctx->scratch[3].p;
+    const SmoothSet set = {c, nprof, k, stride, sums, codes, codes + elements, totals};
+    for (int h = 0; h < k; ++h) {
+        const uint32_t per = option_totals_gx(ctx->num_cu, nprof, smooth_level_nodes(k, h));
+        LAUNCH(ctx, "smooth_set_level", smooth_set_level_kernel, dim3(nprof * per), dim3(256), set, h, per, summary, threshold);
+    }
+    const uint32_t per = option_totals_gx(ctx->num_cu, nprof, stride);
+    LAUNCH(ctx, "smooth_set_codes", smooth_set_codes_kernel, dim3(nprof * per), dim3(256), set, per);
+    *out = SmoothPyramids{sums, codes, totals, stride};
+    return KPAL_OK;
+}
+
 // Every pair of c (c.tri: below the diagonal) with dynamic smoothing and no positive step, from tables that are already
 // balanced and are not written.  out: Q x R row-major, or the lower triangle in distance_matrix order.
 static int cross_smooth_core(kpal_ctx *ctx, int k, const CrossSets &c, const kpal_distance_options *opt, double *out)
 {
     const bool scaled = opt->do_scale != 0, tri = c.tri != 0;
     const uint32_t nprof = tri ? (uint32_t)c.Q : (uint32_t)c.Q + (uint32_t)c.R;
-    const uint64_t stride = smooth_stride(k), elements = (uint64_t)nprof * stride;
+    const uint64_t stride = smooth_stride(k);
     // both passes take the kernel kind and the grid of the bins: groups without a chunk of the (three times shorter) pyramids
     // write zeros, and the pyramid pass is `nacc` accumulators more of ONE partial layout
     const bool staged = cross_staged(c.Q, c.R, c.n);
@@ -511,19 +532,12 @@ static int cross_smooth_core(kpal_ctx *ctx, int k, const CrossSets &c, const kpa
     const uint32_t nacc = option_nacc(opt->metric), gx = g.gx;
     const uint64_t slots = g.slots;
     if (partials_too_many(slots * nacc * 2, gx)) return set_err(KPAL_E_INVALID, "cross distance: %d x %d profiles are too many for one call", c.Q, c.R);
-    CHK(ensure(ctx, ctx->opt_levels, (size_t)smooth_scratch_bytes(k, nprof)));
-    CHK(ensure(ctx, ctx->scratch[3], (size_t)nprof * sizeof(Partial)));
     CHK(ensure(ctx, ctx->partials, (size_t)slots * nacc * 2 * gx * sizeof(Partial)));
-    int64_t *sums = (int64_t *)ctx->opt_levels.p;
-    uint8_t *codes = (uint8_t *)(sums + elements);
-    Partial *pp = (Partial *)ctx->partials.p, *totals = (Partial *)ctx->scratch[3].p;
-    const SmoothSet set = {c, nprof, k, stride, sums, codes, codes + elements, totals};
-    for (int h = 0; h < k; ++h) {
-        const uint32_t per = option_totals_gx(ctx->num_cu, nprof, smooth_level_nodes(k, h));
-        LAUNCH(ctx, "smooth_set_level", smooth_set_level_kernel, dim3(nprof * per), dim3(256), set, h, per, opt->summary, opt->threshold);
-    }
-    const uint32_t per = option_totals_gx(ctx->num_cu, nprof, stride);
-    LAUNCH(ctx, "smooth_set_codes", smooth_set_codes_kernel, dim3(nprof * per), dim3(256), set, per);
+    SmoothPyramids pyr;
+    CHK(smooth_set_pyramids(ctx, k, c, nprof, opt->summary, opt->threshold, &pyr));
+    int64_t *sums = pyr.sums;
+    uint8_t *codes = pyr.codes;
+    Partial *pp = (Partial *)ctx->partials.p, *totals = pyr.totals;
     const uint8_t *rcodes = tri ? codes : codes + (uint64_t)c.Q * stride;
     const CrossCodeOpt bins = {{c, opt->down ? 1 : 0, totals, tri ? 0u : (uint32_t)c.Q, (uint32_t)slots}, codes, rcodes, stride, 2};
     const CrossSets pyramids = {sums, tri ? sums : sums + (uint64_t)c.Q * stride, c.Q, c.R, stride, c.tri};

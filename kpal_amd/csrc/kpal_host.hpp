@@ -9,7 +9,8 @@
 // vectors, planned by transform_plan.hpp; kpal_pair.hip: the distance of one pair, plain and
 // with options; kpal_cross.hip: the distances
 // of sets of profiles, triangle and rectangle, planned by matrix_plan.hpp; kpal_paired.hip: the distances of the linked pairs of
-// two sets, planned by pair_set_plan.hpp; kpal_nearest.hip: the nearest n of a rectangle,
+// two sets, planned by pair_set_plan.hpp; kpal_paired_smooth.hip: those with dynamic smoothing and the smoothed tables of the
+// pairs, planned by pair_smooth_plan.hpp; kpal_nearest.hip: the nearest n of a rectangle,
 // tiled by nearest_plan.hpp; kpal_multi.hip: multi-GPU entry points over RCCL.)
 #pragma once
 #include "../../include/kpal_hip.h"
@@ -408,6 +409,14 @@ int upload_rectangle(kpal_ctx *ctx, uint64_t n, int Q, const int64_t *const *hos
 int cross_gram_launch(kpal_ctx *ctx, const CrossSets &c, CrossGramLayout *lay);
 int cross_pairs_launch(kpal_ctx *ctx, const CrossSets &c, int metric, bool staged, bool recip, CrossGrid *grid);
 int cross_option_launch(kpal_ctx *ctx, const CrossSets &c, const kpal_distance_options *opt, CrossGrid *grid);
+struct SmoothPyramids {   // smooth_plan.hpp: one pyramid per profile, in the context's workspace
+    int64_t *sums;
+    uint8_t *codes;
+    Partial *totals;   // .m: the root of every pyramid, its table's np.sum
+    uint64_t stride;
+};
+int smooth_set_pyramids(kpal_ctx *ctx, int k, const CrossSets &c, uint32_t nprof, int summary, double threshold,
+                        SmoothPyramids *out);   // kpal_cross.hip: the k level launches and the codes launch of dynamic smoothing over sets
 int reduce_partials(kpal_ctx *ctx, const Partial *partials, uint32_t nq, uint32_t nblocks, Partial *out);   // kpal_vec.hip: nq groups of nblocks device partials added in a fixed order
 int finish_partials(kpal_ctx *ctx, uint32_t nq, uint32_t nblocks, std::vector<Partial> &out, bool allreduce = false);   // kpal_vec.hip: reduce nq groups of nblocks partials, fetch them
 double finish_value(int metric, const Partial &p, int64_t *aux);         // kpal_vec.hip: the distance of one reduced partial of a plain metric (aux: its count / wrapping dot)

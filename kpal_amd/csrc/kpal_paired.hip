@@ -6,7 +6,8 @@
 //   scale             the totals kernel (masked under positive), a reduction, the metric kernel, a reduction
 //   do_balance        before them one launch of the set balance per distinct input range, into context scratch: the union of
 //                     the two ranges once when they are the same range or lie a whole number of tables apart
-//   do_smooth         the pair pipeline (kpal_pair.hip) once per pair on the once-balanced tables
+//   do_smooth         the pair pipeline (kpal_pair.hip) once per pair on the once-balanced tables (the smoothed pair kernel over
+//                     per-profile pyramids is kpal_paired_smooth_distance_device, kpal_paired_smooth.hip)
 // The inputs are never written and may alias in any way.
 #include "kpal_host.hpp"
 

@@ -17,7 +17,8 @@ launches per chunk of the right side.  :func:`nearest_chunks` / :func:`nearest_p
 every left profile without that rectangle on the host (``kpal_cross_nearest_device``: tiled over both sides, finished and
 selected on the device), the left side streamed.  :func:`paired_distances` / :func:`successive_distances` -- the distances of the
 LINKED pairs of two sets, ``left[i]`` against ``right[i]``, or of one set against itself ``lag`` profiles on
-(``kpal_paired_distance_device``: a number of launches that does not grow with the number of pairs).
+(``kpal_paired_distance_device``, with dynamic smoothing ``kpal_paired_smooth_distance_device``: a number of launches that
+does not grow with the number of pairs).
 """
 import numpy as np
 
@@ -353,7 +354,9 @@ def paired_distances(left_profiles, right_profiles, dist, max_bytes=None):
     ``do_balance`` one set balance per side), whatever the number of pairs; a pair's value is the same bits in any set, at any
     position.  Tables that are consecutive in one device batch are used where they lie; anything else is gathered (host counts
     uploaded) in groups of at most ``max_bytes`` of tables over both sides (default ``CROSS_MAX_BYTES``, never less than one
-    pair).  Dynamic smoothing runs the pair pipeline once per pair inside the library.  A user-supplied callable, a non-numeric
+    pair).  Dynamic smoothing is ``kpal_paired_smooth_distance_device``: one pyramid of node sums and codes per distinct table
+    (k + 1 launches), one metric kernel over the bins and nodes live for each pair and one reduction, whatever the number of
+    pairs; only positive + smoothing runs the pair pipeline once per pair inside the library.  A user-supplied callable, a non-numeric
     threshold, mixed k or non-integer counts are ``dist.distance`` pair by pair -- and so is a single pair, which keeps the
     route and the bits of ``dist.distance``."""
     left, right = list(left_profiles), list(right_profiles)
@@ -372,7 +375,8 @@ def paired_distances(left_profiles, right_profiles, dist, max_bytes=None):
         try:
             rset = lset if all(a is b for a, b in zip(lgroup, rgroup)) else _DeviceSet(ctx, rgroup)
             try:
-                blocks.append(ctx.paired_distance_device(k, len(lgroup), lset.ptr, rset.ptr, options))
+                entry = ctx.paired_smooth_distance_device if options.do_smooth else ctx.paired_distance_device
+                blocks.append(entry(k, len(lgroup), lset.ptr, rset.ptr, options))
             finally:
                 if rset is not lset:
                     rset.release()
@@ -387,7 +391,8 @@ def successive_distances(profiles, dist, lag=1):
 
     Under the conditions of :func:`paired_distances` the profiles are made ONE set (used where they lie when they are consecutive
     tables of one device batch) and the library is given that set and the same set ``lag`` tables on: with ``do_balance`` it
-    balances the N tables once, not the two sides of N - ``lag`` each."""
+    balances the N tables once, not the two sides of N - ``lag`` each, and with ``do_smooth`` it builds the N pyramids of
+    the set once (``kpal_paired_smooth_distance_device``)."""
     profiles = list(profiles)
     lag = int(lag)
     if lag < 1:
@@ -402,7 +407,8 @@ def successive_distances(profiles, dist, lag=1):
     ctx = _cross_context(profiles)
     pset = _DeviceSet(ctx, profiles)
     try:
-        return ctx.paired_distance_device(k, pairs, pset.ptr, pset.ptr + lag * 8 * 4 ** k, options)
+        entry = ctx.paired_smooth_distance_device if options.do_smooth else ctx.paired_distance_device
+        return entry(k, pairs, pset.ptr, pset.ptr + lag * 8 * 4 ** k, options)
     finally:
         pset.release()
 

@@ -738,6 +738,68 @@ def merge_profiles(profiles, others, merger=metrics.mergers['sum']):
                     lset.release()
 
 
+def _smooth_counts(profile):
+    """Whether ``profile`` can be one table of a smoothed set: in HBM, or int64 counts that can be written in place."""
+    return bool(profile._device_counts()) or (kdistlib._plain_int64(profile._counts) and profile._counts.size == 4 ** profile.length)
+
+
+def smooth_profiles(profiles, others, dist):
+    """``for p, o in zip(profiles, others): dist.dynamic_smooth(p, o)`` for two lists of one length, the pairs of integer
+    profiles of one k-mer length smoothed as SETS (``kpal_paired_smooth_device``: one pyramid of node sums and codes per table
+    and one kernel that writes both smoothed sets, per group of at most ``_RECORD_BATCH_BYTES`` over both sides) under the rules
+    of ``merge_profiles`` and ``balance_profiles``: a profile that is still in HBM stays there, as a row of a new batch; host
+    int64 counts are written into the array the profile holds.  A profile that appears twice anywhere over both sides, and
+    lists of unequal length, are a ``ValueError``.  A custom summary, a non-numeric threshold, counts that are no int64
+    array, pairs of mixed k and a batch that is refused take ``dist.dynamic_smooth`` pair by pair."""
+    profiles, others = list(profiles), list(others)
+    if len(profiles) != len(others):
+        raise ValueError('smooth_profiles: %d profiles, %d partners' % (len(profiles), len(others)))
+    _no_repeats(profiles + others, 'smooth_profiles')
+    code = metrics.summary_code(dist._function)
+    by_length = {}
+    for i, (p, o) in enumerate(zip(profiles, others)):
+        if code is None or not kdistlib._is_number(dist._threshold) or not (_smooth_counts(p) and _smooth_counts(o) and p.length == o.length):
+            dist.dynamic_smooth(p, o)
+        else:
+            by_length.setdefault(p.length, []).append(i)
+    for k, places in sorted(by_length.items()):
+        bins, per = 4 ** k, max(1, _RECORD_BATCH_BYTES // (2 * 8 * 4 ** k))
+        for at in range(0, len(places), per):
+            group = places[at:at + per]
+            n = len(group)
+            both = [profiles[i] for i in group] + [others[i] for i in group]
+            resident = [j for j, p in enumerate(both) if p._device_counts()]
+            ctx = kdistlib._cross_context(both)
+            # the two smoothed sets, left first: rows of a new batch when a profile stays in HBM, else an allocation of the group's
+            batch = _fresh_batch(ctx, 2 * n, bins) if resident else None
+            if resident and batch is None:
+                for p, o in zip(both[:n], both[n:]):
+                    dist.dynamic_smooth(p, o)
+                continue
+            out = batch.ptr if batch is not None else ctx.alloc(2 * n * 8 * bins)
+            try:
+                lset = kdistlib._DeviceSet(ctx, both[:n])
+                try:
+                    rset = kdistlib._DeviceSet(ctx, both[n:])
+                    try:
+                        ctx.paired_smooth_device(k, n, lset.ptr, rset.ptr, code, dist._threshold, out, out + n * 8 * bins)
+                        if len(resident) < 2 * n:
+                            tables = np.empty((2 * n, bins), dtype=np.int64)
+                            ctx.d2h(tables, out)
+                            for j in sorted(set(range(2 * n)) - set(resident)):
+                                both[j]._counts[...] = tables[j]
+                    finally:
+                        rset.release()
+                finally:
+                    lset.release()
+            finally:
+                if batch is None:
+                    ctx.sync()
+                    ctx.free(out)
+            for j in resident:      # (_repoint's assignment; row j of the batch, whatever the profile's place among the resident ones)
+                both[j]._counts, both[j]._device = None, (batch, j, False)
+
+
 def pooled(profiles, name=None):
     """A new profile: the sum of the tables of ``profiles`` (int64 wrap, as repeated ``merge`` with the sum merger), integer
     profiles summed as SETS (``kpal_pool_set_device``: at most two launches per group of at most ``_RECORD_BATCH_BYTES``).

@@ -309,17 +309,36 @@ def smooth(input_handle_left, input_handle_right, output_handle_left, output_han
     """Smooth two profiles by collapsing sub-profiles; several profiles per file are linked by name and
     processed pairwise.
 
-    (kpal/kmer.py:486-538.)  Built-in summary functions run as the level-wise tree kernels."""
+    (kpal/kmer.py:486-538.)  Both files are read in groups of at most ``klib._RECORD_BATCH_BYTES`` of counts over both sides; a
+    group is smoothed by one set call on the device (``klib.smooth_profiles``)."""
     names_left = _profile_names(input_handle_left, names_left)
     names_right = _profile_names(input_handle_right, names_right)
     if len(names_left) != len(names_right):      # before the custom function is evaluated, like the reference
         raise ValueError(PAIRED_NAMES_COUNT_ERROR)
     function = _custom_function(custom_summary, 'values') if custom_summary else metrics.summary[summary]
     dist = kdistlib.ProfileDistance(summary=function, threshold=threshold)
-    for left, right in _paired(input_handle_left, input_handle_right, names_left, names_right):
-        dist.dynamic_smooth(left, right)
-        left.save(output_handle_left)
-        right.save(output_handle_right)
+    lefts, rights, size = [], [], 0
+
+    def flush():
+        klib.smooth_profiles(lefts, rights, dist)
+        for left, right in zip(lefts, rights):
+            left.save(output_handle_left)
+            right.save(output_handle_right)
+        del lefts[:], rights[:]
+
+    for name_left, name_right in zip(names_left, names_right):
+        left = klib.Profile.from_file(input_handle_left, name=name_left)
+        right = klib.Profile.from_file(input_handle_right, name=name_right)
+        if left.length != right.length:
+            flush()      # the earlier pairs are written before the error, as the pair-by-pair loop wrote them
+            raise ValueError(LENGTH_ERROR)
+        lefts.append(left)
+        rights.append(right)
+        size += np.asanyarray(left.counts).nbytes + np.asanyarray(right.counts).nbytes
+        if size >= klib._RECORD_BATCH_BYTES:
+            flush()
+            size = 0
+    flush()
 
 
 def _profile_distance(distance_function, pairwise, custom_pairwise, do_smooth, summary, custom_summary, threshold,

@@ -8,7 +8,14 @@ the spread (smallest and largest repeat).
 Then the public API: ``kdistlib.successive_distances(windows, dist)`` on fresh ``Profile.from_fasta_by_window`` profiles (k = 8,
 5 kb windows, step 500) against the Python loop of ``dist.distance(windows[i], windows[i + 1])``.  Needs a GPU.
 
-Usage: python tools/pairbench.py [--out DIR] [--repeats N] [--quick]   (writes DIR/pairbench.json; default profiles/pairs)"""
+--smooth: the same three shapes under dynamic smoothing, option sets -m, -m -S and -m -s average -t 2:
+kpal_paired_smooth_distance_device against the route that served them before and is still there, kpal_paired_distance_device
+with do_smooth (the pair pipeline once per pair), in the same process on the same tables; then ``klib.smooth_profiles`` on fresh
+``from_fasta_by_window`` profiles against the loop of ``dist.dynamic_smooth``, and ``kdistlib.successive_distances`` with -m
+against the Python loop.
+
+Usage: python tools/pairbench.py [--out DIR] [--repeats N] [--quick] [--smooth]
+(writes DIR/pairbench.json, with --smooth DIR/pairbench_smooth.json; default profiles/pairs)"""
 import argparse
 import io
 import json
@@ -69,6 +76,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--quick', action='store_true', help='small sets: a rehearsal of the tool, not a measurement')
     ap.add_argument('--genome', type=int, default=900000, help='bases of the generated sequence of the end-to-end figure')
+    ap.add_argument('--smooth', action='store_true', help='the option sets with dynamic smoothing against the per-pair route')
     args = ap.parse_args()
     from kpal_amd import _native, klib, kdistlib, metrics
     if _native.device_count() < 1:
@@ -84,6 +92,9 @@ def main():
 
     option_sets = (('prod', opts(metric=_native.PAIRWISE_PROD), _native.PAIRWISE_PROD), ('scale', opts(do_scale=1), None),
                    ('euclidean', opts(metric=_native.EUCLIDEAN), _native.EUCLIDEAN))
+    if args.smooth:
+        option_sets = (('-m', opts(do_smooth=1), None), ('-m -S', opts(do_smooth=1, do_scale=1), None),
+                       ('-m -s average -t 2', opts(do_smooth=1, summary=1, threshold=2.0), None))
     report = {'repeats': args.repeats, 'warmups': WARMUPS, 'quick': bool(args.quick), 'shapes': []}
     for k, n, mean, distinct, with_rectangle in (QUICK if args.quick else SHAPES):
         bins = 4 ** k
@@ -99,9 +110,13 @@ def main():
             ctx.sync()
             for name, options, plain_metric in option_sets:
                 def paired():
+                    if args.smooth:
+                        return ctx.paired_smooth_distance_device(k, n, left, right, options)
                     return ctx.paired_distance_device(k, n, left, right, options)
 
                 def loop():
+                    if args.smooth:      # the pair pipeline once per pair inside the library
+                        return ctx.paired_distance_device(k, n, left, right, options)
                     if plain_metric is not None:
                         return [ctx.pair_distance_device(bins, left + i * tb, right + i * tb, plain_metric) for i in range(n)]
                     return [ctx.profile_distance_device(k, left + i * tb, right + i * tb, options) for i in range(n)]
@@ -115,7 +130,7 @@ def main():
                 got = paired()
                 assert close(got, loop()), ('loop', k, name)       # the sides agree before they are timed
                 skipped = None
-                if with_rectangle:
+                if with_rectangle and not args.smooth:
                     try:
                         diagonal = rectangle()
                         if close(got, diagonal):
@@ -146,7 +161,7 @@ def main():
     genome = 60000 if args.quick else args.genome
     seq = np.frombuffer(b'ACGT', dtype=np.uint8)[rng.integers(0, 4, genome)].tobytes().decode()
     text = '>genome\n' + '\n'.join(seq[j:j + 70] for j in range(0, genome, 70)) + '\n'
-    dist = kdistlib.ProfileDistance()
+    dist = kdistlib.ProfileDistance(do_smooth=True) if args.smooth else kdistlib.ProfileDistance()
 
     def fresh():
         return list(klib.Profile.from_fasta_by_window(io.StringIO(text), K, W, S))
@@ -165,8 +180,36 @@ def main():
         runs['scan'].append(scan_s)
         runs['successive_distances'].append(timed(ctx, lambda: kdistlib.successive_distances(windows, dist))[0])
         runs['loop'].append(timed(ctx, lambda: python_loop(windows))[0])
+    if args.smooth:
+        # klib.smooth_profiles: the first half of the windows against the second half, against the loop of dist.dynamic_smooth
+        def halves(windows):
+            return windows[:len(windows) // 2], windows[len(windows) // 2:2 * (len(windows) // 2)]
+
+        def smooth_loop(windows):
+            for l, r in zip(*halves(windows)):
+                dist.dynamic_smooth(l, r)
+            return windows
+
+        a, b = fresh(), fresh()
+        klib.smooth_profiles(*(halves(a) + (dist,)))
+        smooth_loop(b)
+        assert all(np.array_equal(x.counts, y.counts) for x, y in zip(a, b))
+        sruns = {'smooth_profiles': [], 'loop': []}
+        for _ in range(args.repeats):
+            a, b = fresh(), fresh()
+            sruns['smooth_profiles'].append(timed(ctx, lambda: klib.smooth_profiles(*(halves(a) + (dist,))))[0])
+            sruns['loop'].append(timed(ctx, lambda: smooth_loop(b))[0])
+        report['smooth_profiles'] = {'k': K, 'pairs': len(a) // 2,
+                                     'what': 'klib.smooth_profiles(first half, second half, ProfileDistance(do_smooth=True)) on fresh from_fasta_by_window '
+                                             'profiles, the tables in HBM before and after; loop: dist.dynamic_smooth(l, r) pair by pair on as fresh profiles '
+                                             '(the first pair downloads the batch)',
+                                     'seconds': sruns, 'median_s': dict((key, statistics.median(v)) for key, v in sruns.items()),
+                                     'min_s': dict((key, min(v)) for key, v in sruns.items()), 'max_s': dict((key, max(v)) for key, v in sruns.items()),
+                                     'loop_over_smooth_profiles': statistics.median(sruns['loop']) / statistics.median(sruns['smooth_profiles'])}
+        print('smooth_profiles k=%d pairs=%d  %.4f s, loop %.4f s' % (K, len(a) // 2, report['smooth_profiles']['median_s']['smooth_profiles'],
+                                                                      report['smooth_profiles']['median_s']['loop']), flush=True)
     report['api'] = {'k': K, 'window': W, 'step': S, 'bases': genome, 'windows': len(windows),
-                     'what': 'kdistlib.successive_distances(windows, ProfileDistance()) on fresh from_fasta_by_window profiles, the tables in HBM; '
+                     'what': 'kdistlib.successive_distances(windows, ProfileDistance(%s)) on fresh from_fasta_by_window profiles, the tables in HBM; ' % ('do_smooth=True' if args.smooth else '') +
                              'loop: [dist.distance(windows[i], windows[i + 1])] on the same profiles; scan: the from_fasta_by_window call alone',
                      'seconds': runs, 'median_s': dict((key, statistics.median(v)) for key, v in runs.items()),
                      'min_s': dict((key, min(v)) for key, v in runs.items()), 'max_s': dict((key, max(v)) for key, v in runs.items()),
@@ -174,7 +217,7 @@ def main():
     print('api k=%d windows=%d  successive_distances %.4f s, loop %.4f s, scan %.4f s' % (
         K, len(windows), report['api']['median_s']['successive_distances'], report['api']['median_s']['loop'], report['api']['median_s']['scan']), flush=True)
     os.makedirs(args.out, exist_ok=True)
-    path = os.path.join(args.out, 'pairbench_quick.json' if args.quick else 'pairbench.json')
+    path = os.path.join(args.out, 'pairbench%s%s.json' % ('_smooth' if args.smooth else '', '_quick' if args.quick else ''))
     with open(path, 'w') as fh:
         json.dump(report, fh, indent=1, sort_keys=True)
         fh.write('\n')
