@@ -8,11 +8,13 @@
 // on the values; matrix_all_kernels.hpp for a multiset triangle of 17..64 profiles; the fp64 Gram matrix on the matrix cores
 // for euclidean), one fixed-order reduction of the per-workgroup partials.
 //   with options (cross_option_kernels.hpp): a totals pass or a masked-totals rectangle pass more when the profiles are scaled;
-// dynamic smoothing in those entries stays one pair pipeline (kpal_pair.hip) per pair, on tables balanced once.
+// dynamic smoothing in those entries is one pair pipeline (kpal_pair.hip) per pair, on tables balanced once.
 //   dynamic smoothing over whole sets (kpal_cross_smooth_distance_device, kpal_smooth_distance_matrix_device; smooth_plan.hpp,
 // smooth_set_kernels.hpp): one pyramid of node sums and codes per profile (k + 1 launches for all of them), then two passes of
-// the rectangle kernels, over the bins and over the pyramids, and one reduction.
+// the rectangle kernels, over the bins and over the pyramids, and one reduction.  The pyramids (smooth_set_pyramids) also serve
+// the linked pairs of kpal_paired_smooth.hip; the launch functions of the cores serve the tiles of kpal_nearest.hip.
 #include "kpal_host.hpp"
+#include "dist_host.hpp"
 
 #include "cross_kernels.hpp"
 #include "cross_option_kernels.hpp"
@@ -38,12 +40,12 @@ static int upload_set(kpal_ctx *ctx, int64_t *dst, int count, uint64_t n, const 
     return KPAL_OK;
 }
 
-// The left and the right set of a rectangle, one behind the other in scratch[0].
+// The left and the right set of a rectangle, one behind the other in scratch[kScratchUpload].
 int upload_rectangle(kpal_ctx *ctx, uint64_t n, int Q, const int64_t *const *host_left, int R, const int64_t *const *host_right,
                      int64_t **dl, int64_t **dr)
 {
-    CHK(ensure(ctx, ctx->scratch[0], ((size_t)Q + (size_t)R) * n * 8));
-    *dl = (int64_t *)ctx->scratch[0].p;
+    CHK(ensure(ctx, ctx->scratch[kScratchUpload], ((size_t)Q + (size_t)R) * n * 8));
+    *dl = (int64_t *)ctx->scratch[kScratchUpload].p;
     *dr = *dl + (uint64_t)Q * n;
     CHK(upload_set(ctx, *dl, Q, n, host_left, "left profile"));
     return upload_set(ctx, *dr, R, n, host_right, "right profile");
@@ -57,12 +59,12 @@ int balance_set(kpal_ctx *ctx, int k, int count, const int64_t *src, int64_t *ds
     return KPAL_OK;
 }
 
-// Balanced copies of the sets of c (a triangle: of its one set) in scratch[2]; c names them from here on.  Balanced once per
+// Balanced copies of the sets of c (a triangle: of its one set) in scratch[kScratchBalanced]; c names them from here on.  Balanced once per
 // profile: identical to the reference balancing copies per pair (kdistlib.py:136-141).
 static int balance_sets(kpal_ctx *ctx, int k, CrossSets &c)
 {
-    CHK(ensure(ctx, ctx->scratch[2], ((size_t)c.Q + (c.tri ? 0 : (size_t)c.R)) * c.n * 8));
-    int64_t *bl = (int64_t *)ctx->scratch[2].p, *br = c.tri ? bl : bl + (uint64_t)c.Q * c.n;
+    CHK(ensure(ctx, ctx->scratch[kScratchBalanced], ((size_t)c.Q + (c.tri ? 0 : (size_t)c.R)) * c.n * 8));
+    int64_t *bl = (int64_t *)ctx->scratch[kScratchBalanced].p, *br = c.tri ? bl : bl + (uint64_t)c.Q * c.n;
     CHK(balance_set(ctx, k, c.Q, c.left, bl));
     if (!c.tri) CHK(balance_set(ctx, k, c.R, c.right, br));
     c.left = bl;
@@ -95,14 +97,14 @@ static int gram_euclidean(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof,
     static_assert(sizeof(GramBlock) == sizeof(int2), "gram_mfma_kernel reads the block list as int2");
     const GramPlan g = gram_plan(ctx->num_cu, P, n);
     const uint32_t nd = g.nd, no = g.no;
-    CHK(ensure(ctx, ctx->scratch[3], g.blocks.size() * sizeof(GramBlock)));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[3].p, g.blocks.data(), g.blocks.size() * sizeof(GramBlock), hipMemcpyHostToDevice, ctx->stream));
+    CHK(ensure(ctx, ctx->scratch[kScratchTotals], g.blocks.size() * sizeof(GramBlock)));
+    HIPCHK(hipMemcpyAsync(ctx->scratch[kScratchTotals].p, g.blocks.data(), g.blocks.size() * sizeof(GramBlock), hipMemcpyHostToDevice, ctx->stream));
     const size_t part_d = (size_t)nd * 4096 * g.gx_d, part_o = (size_t)no * 4096 * g.gx_o;
     CHK(ensure(ctx, ctx->partials, (part_d + part_o) * sizeof(Partial)));
     CHK(ensure(ctx, ctx->result, (size_t)(nd + no) * 4096 * sizeof(Partial)));
     Partial *pp = (Partial *)ctx->partials.p;
     Partial *res_d = (Partial *)ctx->result.p;
-    const int2 *dt = (const int2 *)ctx->scratch[3].p;
+    const int2 *dt = (const int2 *)ctx->scratch[kScratchTotals].p;
     // a diagonal block writes only its 10 tiles with gj <= gi; the reduction below runs over all 16: the other six read zeros
     HIPCHK(hipMemsetAsync(pp, 0, part_d * sizeof(Partial), ctx->stream));
     LAUNCH(ctx, "gram_mfma", (gram_mfma_kernel<true>), dim3(g.gx_d, nd), dim3(256), prof, P, n, dt, pp);
@@ -190,8 +192,8 @@ int cross_pairs_launch(kpal_ctx *ctx, const CrossSets &c, int metric, bool stage
     const CrossOpt o = {c, 0, nullptr, 0u, (uint32_t)g.slots};
     bool done = false;
     if (staged && recip && metric != KPAL_EUCLIDEAN) {
-        CHK(ensure(ctx, ctx->scratch[3], 16));
-        uint32_t *big = (uint32_t *)ctx->scratch[3].p;
+        CHK(ensure(ctx, ctx->scratch[kScratchTotals], 16));
+        uint32_t *big = (uint32_t *)ctx->scratch[kScratchTotals].p;
         CHK(try_recip(ctx, big, sizeof(uint32_t), pp, g.slots * g.gx, [&]() -> int {
             const dim3 grid(g.gx * g.units);   // (gx: a multiple of 8)
             if (metric == KPAL_PAIRWISE_PROD) LAUNCH(ctx, c.tri ? "matrix_rdiff" : "cross_rdiff", (cross_recip_kernel<0>), grid, dim3(256), c, g.units, g.superR, pp, big);
@@ -201,9 +203,7 @@ int cross_pairs_launch(kpal_ctx *ctx, const CrossSets &c, int metric, bool stage
     }
     if (!done) {
         const char *name = staged ? (c.tri ? "matrix_super" : "cross_super") : (c.tri ? "matrix_tile" : "cross_tile");
-        if (metric == KPAL_PAIRWISE_PROD) CHK(launch_cross<PlainAcc<0>>(ctx, name, staged, o, g, pp));
-        else if (metric == KPAL_PAIRWISE_SUM) CHK(launch_cross<PlainAcc<1>>(ctx, name, staged, o, g, pp));
-        else CHK(launch_cross<PlainAcc<2>>(ctx, name, staged, o, g, pp));
+        CHK(with_metric<KPAL_EUCLIDEAN>(metric, [&](auto m) { return launch_cross<PlainAcc<m>>(ctx, name, staged, o, g, pp); }));
     }
     return KPAL_OK;
 }
@@ -233,10 +233,10 @@ int distance_matrix_core(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof, 
     if (route.all) {
         const bool wide = route.all_wide;
         gx = matrix_all_gx(ctx->num_cu, n, wide);
-        CHK(ensure(ctx, ctx->scratch[3], 32));
+        CHK(ensure(ctx, ctx->scratch[kScratchTotals], 32));
         CHK(ensure(ctx, ctx->partials, slots * gx * sizeof(Partial)));
         Partial *pp = (Partial *)ctx->partials.p;
-        uint32_t *big = (uint32_t *)ctx->scratch[3].p;
+        uint32_t *big = (uint32_t *)ctx->scratch[kScratchTotals].p;
         CHK(try_recip(ctx, big, 32, pp, slots * gx, [&]() -> int {
             if (metric == 0) {
                 if (wide) LAUNCH(ctx, "matrix_rdiff_all", (matrix_rdiff_all_kernel<16, kMatrixAllBins, kMatrixAllUnits>), dim3(gx), dim3(1024 / kMatrixAllUnits), prof, P, n, pp, big);
@@ -258,8 +258,7 @@ int distance_matrix_core(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof, 
     std::vector<Partial> res;
     if (all_done) CHK(finish_partials(ctx, (uint32_t)slots, gx, res, allreduce));
     else CHK(cross_pairs(ctx, c, metric, route.staged, route.recip, allreduce, res));
-    for (int i = 1; i < P; ++i)
-        for (int j = 0; j < i; ++j) out_lower[triangle_index(i, j)] = finish_value(metric, res[cross_slot(c, 0, i, j)], nullptr);   // (a triangle's slots know no side)
+    fill_pairs(c, 0, out_lower, [&](uint64_t slot) { return finish_value(metric, res[slot], nullptr); });   // (a triangle's slots know no side)
     return KPAL_OK;
 }
 
@@ -273,9 +272,7 @@ static int cross_core(kpal_ctx *ctx, const CrossSets &c, int metric, double *out
     }
     std::vector<Partial> res;
     CHK(cross_pairs(ctx, c, metric, staged, true, false, res));
-    const int sideR = (c.R + 3) / 4;
-    for (int q = 0; q < c.Q; ++q)
-        for (int r = 0; r < c.R; ++r) out[(size_t)q * c.R + r] = finish_value(metric, res[cross_slot(c, sideR, q, r)], nullptr);
+    fill_pairs(c, (c.R + 3) / 4, out, [&](uint64_t slot) { return finish_value(metric, res[slot], nullptr); });
     return KPAL_OK;
 }
 
@@ -303,18 +300,10 @@ KPAL_API int kpal_distance_matrix(kpal_ctx *ctx, int P, int k, const int64_t *co
     if (P == 1) return KPAL_OK;
     if (!host_profiles || !out_lower) return set_err(KPAL_E_INVALID, "NULL pointer");
     const uint64_t n = 1ULL << (2 * k);
-    CHK(ensure(ctx, ctx->scratch[0], (size_t)P * n * 8));
-    CHK(upload_set(ctx, (int64_t *)ctx->scratch[0].p, P, n, host_profiles, "profile"));
-    return kpal_distance_matrix_device(ctx, P, k, (const int64_t *)ctx->scratch[0].p, metric, do_balance, out_lower);
-}
-
-static int cross_check(int k, int Q, int R, int metric, const void *left, const void *right, const double *out)
-{
-    if (Q < 1 || R < 1) return set_err(KPAL_E_INVALID, "Q and R must be >= 1");
-    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
-    if (metric < 0 || metric > 2) return set_err(KPAL_E_INVALID, "unknown metric %d", metric);
-    if (!left || !right || !out) return set_err(KPAL_E_INVALID, "NULL pointer");
-    return KPAL_OK;
+    CHK(ensure(ctx, ctx->scratch[kScratchUpload], (size_t)P * n * 8));
+    int64_t *prof = (int64_t *)ctx->scratch[kScratchUpload].p;
+    CHK(upload_set(ctx, prof, P, n, host_profiles, "profile"));
+    return kpal_distance_matrix_device(ctx, P, k, prof, metric, do_balance, out_lower);
 }
 
 KPAL_API int kpal_cross_distance_device(kpal_ctx *ctx, int k, int Q, const int64_t *dev_left, int R, const int64_t *dev_right,
@@ -322,7 +311,7 @@ KPAL_API int kpal_cross_distance_device(kpal_ctx *ctx, int k, int Q, const int64
 {
     CTX_ENTER(ctx);
     CHK(cross_check(k, Q, R, metric, dev_left, dev_right, out));
-    if (((uintptr_t)dev_left & 15) || ((uintptr_t)dev_right & 15)) return set_err(KPAL_E_INVALID, "device tables must be 16-byte aligned");
+    CHK(tables_aligned(dev_left, dev_right));
     CrossSets c = {dev_left, dev_right, Q, R, 1ULL << (2 * k), 0};
     if (do_balance) CHK(balance_sets(ctx, k, c));
     return cross_core(ctx, c, metric, out);
@@ -341,17 +330,6 @@ KPAL_API int kpal_cross_distance(kpal_ctx *ctx, int k, int Q, const int64_t *con
 // ----------------------------------------------------------------------------------------------
 // ProfileDistance with options over a rectangle / a lower triangle (cross_option_kernels.hpp)
 // ----------------------------------------------------------------------------------------------
-template <int MODE>
-static int launch_cross_option_metric(kpal_ctx *ctx, const char *name, bool staged, bool scaled, bool positive, const CrossOpt &o,
-                                      const CrossGrid &g, Partial *pp)
-{
-    if (scaled) return positive ? launch_cross<OptAcc<MODE, true, true>>(ctx, name, staged, o, g, pp)
-                                : launch_cross<OptAcc<MODE, true, false>>(ctx, name, staged, o, g, pp);
-    if (positive) return launch_cross<OptAcc<MODE, false, true>>(ctx, name, staged, o, g, pp);
-    if constexpr (MODE == KPAL_COSINE) return launch_cross<OptAcc<MODE, false, false>>(ctx, name, staged, o, g, pp);
-    return set_err(KPAL_E_STATE, "plain options belong to the plain rectangle");   // (delegated by the callers)
-}
-
 // Every pair of c (c.tri: pairs below the diagonal only) for a batched option set -- no smoothing, not plain -- from tables
 // that are already balanced.  cross_option_launch: the kernels alone -- the workgroup partials of the option_nacc(metric)
 // accumulators lie in ctx->partials, accumulator a of a pair at a * g->slots + its slot, g->gx of each.
@@ -367,8 +345,8 @@ int cross_option_launch(kpal_ctx *ctx, const CrossSets &c, const kpal_distance_o
     const uint32_t nprof = tri ? (uint32_t)c.Q : (uint32_t)c.Q + (uint32_t)c.R;
     const uint32_t gxt = option_totals_gx(ctx->num_cu, nprof, c.n);
     CHK(ensure(ctx, ctx->partials, std::max<size_t>((size_t)slots * nacc_max * gx, (size_t)nprof * gxt) * sizeof(Partial)));
-    CHK(ensure(ctx, ctx->scratch[3], std::max<size_t>((size_t)slots * 2, nprof) * sizeof(Partial)));
-    Partial *pp = (Partial *)ctx->partials.p, *totals = (Partial *)ctx->scratch[3].p;
+    CHK(ensure(ctx, ctx->scratch[kScratchTotals], std::max<size_t>((size_t)slots * 2, nprof) * sizeof(Partial)));
+    Partial *pp = (Partial *)ctx->partials.p, *totals = (Partial *)ctx->scratch[kScratchTotals].p;
     const CrossOpt o = {c, opt->down ? 1 : 0, totals, tri ? 0u : (uint32_t)c.Q, (uint32_t)slots};
     if (scaled && !positive) {
         // np.sum of every (balanced) profile once; the pairs' factors are derived from them inside the rectangle kernel
@@ -380,36 +358,24 @@ int cross_option_launch(kpal_ctx *ctx, const CrossSets &c, const kpal_distance_o
         CHK(reduce_partials(ctx, pp, (uint32_t)slots * 2, gx, totals));
     }
     const char *name = staged ? "cross_option_super" : "cross_option_tile";
-    switch (opt->metric) {
-    case KPAL_PAIRWISE_PROD: CHK(launch_cross_option_metric<0>(ctx, name, staged, scaled, positive, o, g, pp)); break;
-    case KPAL_PAIRWISE_SUM: CHK(launch_cross_option_metric<1>(ctx, name, staged, scaled, positive, o, g, pp)); break;
-    case KPAL_EUCLIDEAN: CHK(launch_cross_option_metric<2>(ctx, name, staged, scaled, positive, o, g, pp)); break;
-    default: CHK(launch_cross_option_metric<3>(ctx, name, staged, scaled, positive, o, g, pp)); break;
-    }
-    return KPAL_OK;
+    return with_metric(opt->metric, [&](auto m, auto s, auto p) -> int {
+        // unscaled, not positive: the cosine alone is an option set (the callers delegate the others)
+        if constexpr (!s && !p && m != KPAL_COSINE) return set_err(KPAL_E_STATE, "plain options belong to the plain rectangle");
+        else return launch_cross<OptAcc<m, s, p>>(ctx, name, staged, o, g, pp);
+    }, scaled, positive);
 }
 
 // out: Q x R row-major, or the lower triangle in distance_matrix order.
 static int cross_option_core(kpal_ctx *ctx, const CrossSets &c, const kpal_distance_options *opt, double *out)
 {
-    const bool scaled = opt->do_scale != 0, tri = c.tri != 0;
+    const bool scaled = opt->do_scale != 0;
     CrossGrid g;
     CHK(cross_option_launch(ctx, c, opt, &g));
     const uint64_t slots = g.slots;
     const uint32_t nacc = option_nacc(opt->metric);
     std::vector<Partial> res;
     CHK(finish_partials(ctx, (uint32_t)(slots * nacc), g.gx, res));
-    auto value = [&](int i, int j) -> double {   // (accumulators 1 and 2 exist for the cosine only: p0 again, unread)
-        const size_t slot = cross_slot(c, g.sideR, i, j);
-        return finish_distance(opt->metric, scaled, res[slot], res[(nacc / 2) * slots + slot], res[(nacc - 1) * slots + slot]);
-    };
-    if (tri) {
-        for (int i = 1; i < c.Q; ++i)
-            for (int j = 0; j < i; ++j) out[triangle_index(i, j)] = value(i, j);
-    } else {
-        for (int q = 0; q < c.Q; ++q)
-            for (int r = 0; r < c.R; ++r) out[(size_t)q * c.R + r] = value(q, r);
-    }
+    fill_pairs(c, g.sideR, out, [&](uint64_t slot) { return option_value(opt->metric, scaled, res.data(), nacc, slots, slot); });
     return KPAL_OK;
 }
 
@@ -420,7 +386,7 @@ KPAL_API int kpal_cross_profile_distance_device(kpal_ctx *ctx, int k, int Q, con
     CHK(check_options(opt));
     if (options_plain(opt)) return kpal_cross_distance_device(ctx, k, Q, dev_left, R, dev_right, opt->metric, opt->do_balance, out);
     CHK(cross_check(k, Q, R, 0, dev_left, dev_right, out));
-    if (((uintptr_t)dev_left & 15) || ((uintptr_t)dev_right & 15)) return set_err(KPAL_E_INVALID, "device tables must be 16-byte aligned");
+    CHK(tables_aligned(dev_left, dev_right));
     const uint64_t n = 1ULL << (2 * k);
     CrossSets c = {dev_left, dev_right, Q, R, n, 0};
     if (opt->do_balance) CHK(balance_sets(ctx, k, c));
@@ -456,7 +422,7 @@ KPAL_API int kpal_profile_distance_matrix_device(kpal_ctx *ctx, int P, int k, co
     if (P == 1) return KPAL_OK;
     if (!dev_profiles || !out_lower) return set_err(KPAL_E_INVALID, "NULL pointer");
     if (options_plain(opt)) return kpal_distance_matrix_device(ctx, P, k, dev_profiles, opt->metric, opt->do_balance, out_lower);
-    if ((uintptr_t)dev_profiles & 15) return set_err(KPAL_E_INVALID, "device tables must be 16-byte aligned");
+    CHK(tables_aligned(dev_profiles, dev_profiles));
     const uint64_t n = 1ULL << (2 * k);
     CrossSets c = {dev_profiles, dev_profiles, P, P, n, 1};
     if (opt->do_balance) CHK(balance_sets(ctx, k, c));
@@ -490,23 +456,16 @@ KPAL_API int kpal_profile_distance_matrix(kpal_ctx *ctx, int P, int k, const int
 // ----------------------------------------------------------------------------------------------
 // dynamic smoothing over a rectangle / a lower triangle (smooth_plan.hpp, smooth_set_kernels.hpp)
 // ----------------------------------------------------------------------------------------------
-template <int MODE>
-static int launch_smooth_pass(kpal_ctx *ctx, bool staged, bool scaled, const CrossCodeOpt &o, const CrossGrid &g, Partial *pp)
-{
-    const char *name = staged ? "smooth_set_super" : "smooth_set_tile";
-    return scaled ? launch_cross<SmoothAcc<MODE, true>>(ctx, name, staged, o, g, pp) : launch_cross<SmoothAcc<MODE, false>>(ctx, name, staged, o, g, pp);
-}
-
 // The pyramids of the nprof profiles of c (smooth_set_kernels.hpp: left 0 .. Q-1, then right; nprof = Q reads the left set
-// alone) in the context's opt_levels, their roots in scratch[3]: k level launches and the codes launch.
+// alone) in the context's opt_levels, their roots in scratch[kScratchTotals]: k level launches and the codes launch.
 int smooth_set_pyramids(kpal_ctx *ctx, int k, const CrossSets &c, uint32_t nprof, int summary, double threshold, SmoothPyramids *out)
 {
     const uint64_t stride = smooth_stride(k), elements = (uint64_t)nprof * stride;
     CHK(ensure(ctx, ctx->opt_levels, (size_t)smooth_scratch_bytes(k, nprof)));
-    CHK(ensure(ctx, ctx->scratch[3], (size_t)nprof * sizeof(Partial)));
+    CHK(ensure(ctx, ctx->scratch[kScratchTotals], (size_t)nprof * sizeof(Partial)));
     int64_t *sums = (int64_t *)ctx->opt_levels.p;
     uint8_t *codes = (uint8_t *)(sums + elements);
-    Partial *totals = (Partial *)ctx->scratch[3].p;
+    Partial *totals = (Partial *)ctx->scratch[kScratchTotals].p;
     const SmoothSet set = {c, nprof, k, stride, sums, codes, codes + elements, totals};
     for (int h = 0; h < k; ++h) {
         const uint32_t per = option_totals_gx(ctx->num_cu, nprof, smooth_level_nodes(k, h));
@@ -544,31 +503,19 @@ static int cross_smooth_core(kpal_ctx *ctx, int k, const CrossSets &c, const kpa
     const CrossCodeOpt nodes = {{pyramids, bins.down, totals, bins.roff, bins.slots}, codes, rcodes, stride, 0};
     Partial *pass[2] = {pp, pp + slots * nacc * gx};
     const CrossCodeOpt *of[2] = {&bins, &nodes};
+    const char *name = staged ? "smooth_set_super" : "smooth_set_tile";
     for (int i = 0; i < 2; ++i)
-        switch (opt->metric) {
-        case KPAL_PAIRWISE_PROD: CHK(launch_smooth_pass<0>(ctx, staged, scaled, *of[i], g, pass[i])); break;
-        case KPAL_PAIRWISE_SUM: CHK(launch_smooth_pass<1>(ctx, staged, scaled, *of[i], g, pass[i])); break;
-        case KPAL_EUCLIDEAN: CHK(launch_smooth_pass<2>(ctx, staged, scaled, *of[i], g, pass[i])); break;
-        default: CHK(launch_smooth_pass<3>(ctx, staged, scaled, *of[i], g, pass[i])); break;
-        }
+        CHK(with_metric(opt->metric, [&](auto m, auto s) { return launch_cross<SmoothAcc<m, s>>(ctx, name, staged, *of[i], g, pass[i]); }, scaled));
     std::vector<Partial> res;
     CHK(finish_partials(ctx, (uint32_t)(slots * nacc * 2), gx, res));
-    auto value = [&](int i, int j) -> double {
-        const size_t slot = cross_slot(c, g.sideR, i, j);
+    fill_pairs(c, g.sideR, out, [&](uint64_t slot) {
         Partial p[3];
         for (uint32_t a = 0; a < nacc; ++a) {   // bins, then nodes: a fixed order
             const Partial &b = res[a * slots + slot], &n = res[(nacc + a) * slots + slot];
             p[a] = Partial{b.s + n.s, b.m + n.m};
         }
-        return finish_distance(opt->metric, scaled, p[0], p[nacc / 2], p[nacc - 1]);
-    };
-    if (tri) {
-        for (int i = 1; i < c.Q; ++i)
-            for (int j = 0; j < i; ++j) out[triangle_index(i, j)] = value(i, j);
-    } else {
-        for (int q = 0; q < c.Q; ++q)
-            for (int r = 0; r < c.R; ++r) out[(size_t)q * c.R + r] = value(q, r);
-    }
+        return option_value(opt->metric, scaled, p, nacc, 1, 0);
+    });
     return KPAL_OK;
 }
 
@@ -579,7 +526,7 @@ KPAL_API int kpal_cross_smooth_distance_device(kpal_ctx *ctx, int k, int Q, cons
     CHK(check_options(opt));
     if (!opt->do_smooth) return kpal_cross_profile_distance_device(ctx, k, Q, dev_left, R, dev_right, opt, out);
     CHK(cross_check(k, Q, R, 0, dev_left, dev_right, out));
-    if (((uintptr_t)dev_left & 15) || ((uintptr_t)dev_right & 15)) return set_err(KPAL_E_INVALID, "device tables must be 16-byte aligned");
+    CHK(tables_aligned(dev_left, dev_right));
     // with positive, or past the budget: one pair pipeline per pair
     if (!smooth_batched(k, Q, R, opt->do_positive != 0, kSmoothBudgetBytes)) return kpal_cross_profile_distance_device(ctx, k, Q, dev_left, R, dev_right, opt, out);
     CrossSets c = {dev_left, dev_right, Q, R, 1ULL << (2 * k), 0};
@@ -598,7 +545,7 @@ KPAL_API int kpal_smooth_distance_matrix_device(kpal_ctx *ctx, int P, int k, con
     if (!dev_profiles || !out_lower) return set_err(KPAL_E_INVALID, "NULL pointer");
     if (!opt->do_smooth || !smooth_batched(k, P, 0, opt->do_positive != 0, kSmoothBudgetBytes))
         return kpal_profile_distance_matrix_device(ctx, P, k, dev_profiles, opt, out_lower);
-    if ((uintptr_t)dev_profiles & 15) return set_err(KPAL_E_INVALID, "device tables must be 16-byte aligned");
+    CHK(tables_aligned(dev_profiles, dev_profiles));
     CrossSets c = {dev_profiles, dev_profiles, P, P, 1ULL << (2 * k), 1};
     if (opt->do_balance) CHK(balance_sets(ctx, k, c));
     return cross_smooth_core(ctx, k, c, opt, out_lower);

@@ -6,12 +6,12 @@
 // split, summaries, merge, shrink; kpal_sets.hip: the summaries and the strand balance of a whole set of vectors, planned by
 // stat_plan.hpp, and the strand balance of one vector, which is a set of one; kpal_spectrum.hip: the count-of-counts spectrum of
 // every vector of a set, planned by spectrum_plan.hpp; kpal_transform.hip: the balance, the shrink and the pool of a whole set of
-// vectors, planned by transform_plan.hpp; kpal_pair.hip: the distance of one pair, plain and
-// with options; kpal_cross.hip: the distances
-// of sets of profiles, triangle and rectangle, planned by matrix_plan.hpp; kpal_paired.hip: the distances of the linked pairs of
-// two sets, planned by pair_set_plan.hpp; kpal_paired_smooth.hip: those with dynamic smoothing and the smoothed tables of the
-// pairs, planned by pair_smooth_plan.hpp; kpal_nearest.hip: the nearest n of a rectangle,
-// tiled by nearest_plan.hpp; kpal_multi.hip: multi-GPU entry points over RCCL.)
+// vectors, planned by transform_plan.hpp; kpal_multi.hip: multi-GPU entry points over RCCL.  The five units that serve distances
+// share dist_host.hpp on top of this header -- kpal_pair.hip: the distance of one pair, plain and with options; kpal_cross.hip:
+// the distances of sets of profiles, triangle and rectangle, plain, with options and with dynamic smoothing, planned by
+// matrix_plan.hpp and smooth_plan.hpp; kpal_paired.hip: the distances of the linked pairs of two sets, planned by
+// pair_set_plan.hpp; kpal_paired_smooth.hip: those with dynamic smoothing and the smoothed tables of the pairs, planned by
+// pair_smooth_plan.hpp; kpal_nearest.hip: the nearest n of a rectangle, tiled by nearest_plan.hpp.)
 #pragma once
 #include "../../include/kpal_hip.h"
 
@@ -123,6 +123,9 @@ struct RecordFileScan {
     uint64_t records = 0;
 };
 
+// The roles of kpal_ctx::scratch that the distance units rely on: the table at that member.
+enum { kScratchUpload = 0, kScratchBalanced = 2, kScratchTotals = 3 };
+
 struct kpal_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -208,7 +211,29 @@ struct kpal_ctx {
     hipEvent_t ev_copied[2] = {nullptr, nullptr};
     hipEvent_t ev_done[2] = {nullptr, nullptr};
     bool stage_used[2] = {false, false};
-    // scratch for vector ops
+    // Scratch for vector ops.  kpal_vec, kpal_sets, kpal_records, kpal_spectrum and kpal_multi use scratch[0..3] within one function.
+    // The distance units (dist_host.hpp) hold a buffer ACROSS calls into functions that take workspace themselves, by these roles.
+    // ensure() frees a buffer that must grow: a callee that grew one its caller still points into would leave that pointer
+    // dangling, so only the functions of the last column may ensure() a buffer, and nothing called while a pointer is held does.
+    //   buffer (kScratch*) filled by                                  held across                                  ensured by
+    //   scratch[Upload]    the host entries: upload_rectangle,        the whole device entry the host entry ends   those host entries alone (one pair: the
+    //                      kpal_distance_matrix, upload_pair          in                                           right vector in scratch[Upload + 1])
+    //   scratch[Balanced]  the device entries, before their cores:    the cores, the pair pipeline (balanced =     those device entries alone (one plain pair:
+    //                      balance_sets, balanced_pair_chunk, the     true), smooth_set_pyramids, every tile of    the right copy in scratch[Balanced + 1],
+    //                      tile loop of kpal_cross_nearest_device     a nearest call                               which takes no totals)
+    //   scratch[Totals]    the launch functions: totals (cross_       the launches that follow in the same core    those launch functions alone; reduce_partials
+    //                      option_launch, paired_chunk), pyramid      and its finish_partials; the roots as        and finish_partials never touch scratch
+    //                      roots (smooth_set_pyramids), the word of   SmoothPyramids::totals until the pair or
+    //                      a reciprocal form, the Gram block list     rectangle passes are reduced
+    //   partials           the kernels of every launch function       cross_*_launch leave them to their caller,   the launch functions (and the cores before
+    //                                                                 up to its finish_partials / reduce_partials  smooth_set_pyramids, which takes none)
+    //   result             reduce_partials                            the finish kernels of a nearest tile;        finish_partials, reduce_to_result,
+    //                                                                 gram_euclidean until its download            gram_euclidean
+    //   opt_l, opt_r       profile_distance_pair, kpal_dynamic_smooth nothing outside those two functions          those two functions
+    //   opt_levels         launch_smooth (one pair; held nowhere),    the passes over the pyramids, as             those two functions
+    //                      smooth_set_pyramids                        SmoothPyramids::sums / codes
+    //   opt_profiles       kpal_profile_distance_matrix's upload      the device entry it ends in                  that host entry alone
+    //   near_dist, _best   kpal_cross_nearest_device                  every tile of the call                       that entry alone, before its first tile
     DevBuf scratch[4];
     DevBuf partials, result;
     // the (value, number) pairs of the last kpal_distribution_set / _set_device, table after table (kpal_spectrum.hip): what
@@ -391,32 +416,8 @@ int table_ready(kpal_ctx *ctx);                                           // kpa
 int launch_balance(kpal_ctx *ctx, int k, const int64_t *in, int64_t *out);   // kpal_vec.hip
 int canon_tiles(kpal_ctx *ctx, int k, int per_cu, const uint32_t **list, uint32_t *count, unsigned *grid);   // kpal_vec.hip: the canonical tile pairs of the LDS-tiled balance family (k >= 6), the grid for per_cu workgroups on a CU
 int balance_set_launch(kpal_ctx *ctx, int k, size_t n_tables, const int64_t *dev_in, int64_t *dev_out);   // kpal_transform.hip: the one launch behind kpal_balance_set_device (nothing checked)
-int check_options(const kpal_distance_options *opt);                       // kpal_pair.hip
-int profile_distance_pair(kpal_ctx *ctx, int k, const int64_t *dl, const int64_t *dr, const kpal_distance_options *opt, bool balanced,
-                          double *out);   // kpal_pair.hip: the option pipeline of one pair of 16-byte aligned device tables (balanced: do_balance is not applied again)
 int distance_matrix_core(kpal_ctx *ctx, int P, uint64_t n, const int64_t *prof, int metric, double *out_lower, bool allreduce,
                          int tiled = -1);   // kpal_cross.hip (tiled: -1 decided from n; 0 / 1 agreed between the ranks)
-// kpal_cross.hip: the launches of the rectangle cores up to where their host loops begin -- the workgroup partials are left in
-// ctx->partials for finish_partials, or for kpal_nearest.hip, which reduces and finishes them on the device
-struct CrossGramLayout {
-    int blocksR;
-    uint32_t gx;
-    size_t dots, groups;   // reduced: the dot of (q, r) at cross_gram_index(blocksR, q, r), the Q + R norms from `dots` on
-};
-int balance_set(kpal_ctx *ctx, int k, int count, const int64_t *src, int64_t *dst);
-int upload_rectangle(kpal_ctx *ctx, uint64_t n, int Q, const int64_t *const *host_left, int R, const int64_t *const *host_right,
-                     int64_t **dl, int64_t **dr);   // the left and the right set, one behind the other in scratch[0]
-int cross_gram_launch(kpal_ctx *ctx, const CrossSets &c, CrossGramLayout *lay);
-int cross_pairs_launch(kpal_ctx *ctx, const CrossSets &c, int metric, bool staged, bool recip, CrossGrid *grid);
-int cross_option_launch(kpal_ctx *ctx, const CrossSets &c, const kpal_distance_options *opt, CrossGrid *grid);
-struct SmoothPyramids {   // smooth_plan.hpp: one pyramid per profile, in the context's workspace
-    int64_t *sums;
-    uint8_t *codes;
-    Partial *totals;   // .m: the root of every pyramid, its table's np.sum
-    uint64_t stride;
-};
-int smooth_set_pyramids(kpal_ctx *ctx, int k, const CrossSets &c, uint32_t nprof, int summary, double threshold,
-                        SmoothPyramids *out);   // kpal_cross.hip: the k level launches and the codes launch of dynamic smoothing over sets
 int reduce_partials(kpal_ctx *ctx, const Partial *partials, uint32_t nq, uint32_t nblocks, Partial *out);   // kpal_vec.hip: nq groups of nblocks device partials added in a fixed order
 int finish_partials(kpal_ctx *ctx, uint32_t nq, uint32_t nblocks, std::vector<Partial> &out, bool allreduce = false);   // kpal_vec.hip: reduce nq groups of nblocks partials, fetch them
 double finish_value(int metric, const Partial &p, int64_t *aux);         // kpal_vec.hip: the distance of one reduced partial of a plain metric (aux: its count / wrapping dot)

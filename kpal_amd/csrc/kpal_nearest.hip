@@ -5,6 +5,7 @@
 // tiles of a band and are downloaded once per band.  Option sets with dynamic smoothing compute a tile with
 // kpal_cross_smooth_distance_device into a host buffer of that tile and merge on the host, under the same order.
 #include "kpal_host.hpp"
+#include "dist_host.hpp"
 
 #include "nearest_kernels.hpp"
 
@@ -87,10 +88,8 @@ KPAL_API int kpal_cross_nearest_device(kpal_ctx *ctx, int k, int Q, const int64_
 {
     CTX_ENTER(ctx);
     CHK(check_options(opt));
-    if (Q < 1 || R < 1) return set_err(KPAL_E_INVALID, "Q and R must be >= 1");
-    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
-    if (!dev_left || !dev_right || !dist_inout || !index_inout) return set_err(KPAL_E_INVALID, "NULL pointer");
-    if (((uintptr_t)dev_left & 15) || ((uintptr_t)dev_right & 15)) return set_err(KPAL_E_INVALID, "device tables must be 16-byte aligned");
+    CHK(cross_check(k, Q, R, 0, dev_left, dev_right, index_inout ? dist_inout : nullptr));   // (both outputs)
+    CHK(tables_aligned(dev_left, dev_right));
     if (n < 1 || n > KPAL_NEAREST_MAX) return set_err(KPAL_E_INVALID, "nearest: n=%d out of range 1..%d", n, KPAL_NEAREST_MAX);
     if (have < 0 || have > n) return set_err(KPAL_E_INVALID, "nearest: have=%d out of range 0..n=%d", have, n);
     if (tile_q < 0 || tile_r < 0) return set_err(KPAL_E_INVALID, "nearest: negative tile cap");
@@ -103,12 +102,12 @@ KPAL_API int kpal_cross_nearest_device(kpal_ctx *ctx, int k, int Q, const int64_
     const size_t tq = (size_t)plan.tile_q, tr = (size_t)plan.tile_r;
     CHK(ensure(ctx, ctx->near_dist, tq * tr * sizeof(double) + 16));
     CHK(ensure(ctx, ctx->near_best, tq * (size_t)n * 16));
-    if (opt->do_balance) CHK(ensure(ctx, ctx->scratch[2], (tq + tr) * bins * 8));
+    if (opt->do_balance) CHK(ensure(ctx, ctx->scratch[kScratchBalanced], (tq + tr) * bins * 8));
     double *dd = (double *)ctx->near_dist.p;
     uint32_t *flag = (uint32_t *)(dd + tq * tr);
     double *best_d = (double *)ctx->near_best.p;
     int64_t *best_i = (int64_t *)(best_d + tq * (size_t)n);
-    int64_t *bal_left = (int64_t *)ctx->scratch[2].p, *bal_right = bal_left ? bal_left + tq * bins : nullptr;
+    int64_t *bal_left = (int64_t *)ctx->scratch[kScratchBalanced].p, *bal_right = bal_left ? bal_left + tq * bins : nullptr;
     const int64_t *band_left = nullptr;
     for (const NearestTile &t : plan.tiles) {
         const int Qt = t.q1 - t.q0, Rt = t.r1 - t.r0;
@@ -149,9 +148,7 @@ KPAL_API int kpal_cross_nearest(kpal_ctx *ctx, int k, int Q, const int64_t *cons
 {
     CTX_ENTER(ctx);
     CHK(check_options(opt));
-    if (Q < 1 || R < 1) return set_err(KPAL_E_INVALID, "Q and R must be >= 1");
-    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
-    if (!host_left || !host_right || !dist_inout || !index_inout) return set_err(KPAL_E_INVALID, "NULL pointer");
+    CHK(cross_check(k, Q, R, 0, host_left, host_right, index_inout ? dist_inout : nullptr));   // (both outputs)
     int64_t *dl = nullptr, *dr = nullptr;
     CHK(upload_rectangle(ctx, 1ULL << (2 * k), Q, host_left, R, host_right, &dl, &dr));
     return kpal_cross_nearest_device(ctx, k, Q, dl, R, dr, opt, n, right_first, have, tile_q, tile_r, dist_inout, index_inout);

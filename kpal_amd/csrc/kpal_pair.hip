@@ -1,10 +1,25 @@
 // kpal_pair.hip -- everything of the C-ABI that works on ONE PAIR of count vectors: the plain pair distances (with the balance
 // fused in LDS tiles for k >= 6), and the ProfileDistance option pipeline of a pair -- balance, positive, dynamic smoothing,
-// scaling, the metric (option_kernels.hpp) -- which the sets of kpal_cross.hip fall back to where an option exists per pair only.
+// scaling, the metric (option_kernels.hpp) -- which kpal_cross.hip and kpal_paired.hip fall back to where an option exists per pair only.
 #include "kpal_host.hpp"
+#include "dist_host.hpp"
 
 #include "vec_kernels.hpp"
 #include "option_kernels.hpp"
+
+// A pair of host vectors of n 8-byte elements in scratch[kScratchUpload] and the buffer behind it.
+template <typename T>
+static int upload_pair(kpal_ctx *ctx, size_t n, const T *host_left, const T *host_right, const T **dl, const T **dr)
+{
+    DevBuf &bl = ctx->scratch[kScratchUpload], &br = ctx->scratch[kScratchUpload + 1];
+    CHK(ensure(ctx, bl, n * 8));
+    CHK(ensure(ctx, br, n * 8));
+    HIPCHK(hipMemcpyAsync(bl.p, host_left, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(br.p, host_right, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    *dl = (const T *)bl.p;
+    *dr = (const T *)br.p;
+    return KPAL_OK;
+}
 
 template <typename T>
 static int pair_distance_launch(kpal_ctx *ctx, size_t n, const T *dl, const T *dr, int metric, double *out, int64_t *aux)
@@ -12,14 +27,11 @@ static int pair_distance_launch(kpal_ctx *ctx, size_t n, const T *dl, const T *d
     const unsigned grid = stream_grid(ctx, (n + 1) / 2);
     CHK(ensure(ctx, ctx->partials, (size_t)grid * sizeof(Partial)));
     Partial *pp = (Partial *)ctx->partials.p;
-    if (metric == KPAL_PAIRWISE_PROD) LAUNCH(ctx, "pair_distance", (pair_distance_kernel<0, T>), dim3(grid), dim3(256), dl, dr, (uint64_t)n, pp);
-    else if (metric == KPAL_PAIRWISE_SUM) LAUNCH(ctx, "pair_distance", (pair_distance_kernel<1, T>), dim3(grid), dim3(256), dl, dr, (uint64_t)n, pp);
-    else {
-        if constexpr (std::is_same<T, int64_t>::value)
-            LAUNCH(ctx, "pair_distance", (pair_distance_kernel<2, T>), dim3(grid), dim3(256), dl, dr, (uint64_t)n, pp);
-        else
-            return set_err(KPAL_E_INVALID, "euclidean is int64 only");
-    }
+    CHK(with_metric<KPAL_EUCLIDEAN>(metric, [&](auto m) -> int {
+        if constexpr (m == KPAL_EUCLIDEAN && !std::is_same<T, int64_t>::value) return set_err(KPAL_E_INVALID, "euclidean is int64 only");
+        else LAUNCH(ctx, "pair_distance", (pair_distance_kernel<m, T>), dim3(grid), dim3(256), dl, dr, (uint64_t)n, pp);
+        return KPAL_OK;
+    }));
     std::vector<Partial> res;
     CHK(finish_partials(ctx, 1, grid, res));
     *out = finish_value(metric, res[0], aux);
@@ -45,20 +57,22 @@ KPAL_API int kpal_pair_distance_device(kpal_ctx *ctx, size_t n, const int64_t *d
             CHK(canon_tiles(ctx, k, 1, &canon, &ncanon, &grid));
             CHK(ensure(ctx, ctx->partials, (size_t)grid * sizeof(Partial)));
             Partial *pp = (Partial *)ctx->partials.p;
-            if (metric == KPAL_PAIRWISE_PROD) LAUNCH(ctx, "pair_distance_balanced", (pair_distance_balanced_kernel<0>), dim3(grid), dim3(1024), l, r, k, canon, ncanon, pp);
-            else if (metric == KPAL_PAIRWISE_SUM) LAUNCH(ctx, "pair_distance_balanced", (pair_distance_balanced_kernel<1>), dim3(grid), dim3(1024), l, r, k, canon, ncanon, pp);
-            else LAUNCH(ctx, "pair_distance_balanced", (pair_distance_balanced_kernel<2>), dim3(grid), dim3(1024), l, r, k, canon, ncanon, pp);
+            CHK(with_metric<KPAL_EUCLIDEAN>(metric, [&](auto m) -> int {
+                LAUNCH(ctx, "pair_distance_balanced", (pair_distance_balanced_kernel<m>), dim3(grid), dim3(1024), l, r, k, canon, ncanon, pp);
+                return KPAL_OK;
+            }));
             std::vector<Partial> res;
             CHK(finish_partials(ctx, 1, grid, res));
             *out = finish_value(metric, res[0], aux_out);
             return KPAL_OK;
         }
-        CHK(ensure(ctx, ctx->scratch[2], n * 8));
-        CHK(ensure(ctx, ctx->scratch[3], n * 8));
-        CHK(launch_balance(ctx, k, l, (int64_t *)ctx->scratch[2].p));
-        CHK(launch_balance(ctx, k, r, (int64_t *)ctx->scratch[3].p));
-        l = (const int64_t *)ctx->scratch[2].p;
-        r = (const int64_t *)ctx->scratch[3].p;
+        DevBuf &bl = ctx->scratch[kScratchBalanced], &br = ctx->scratch[kScratchBalanced + 1];   // (no totals in this entry)
+        CHK(ensure(ctx, bl, n * 8));
+        CHK(ensure(ctx, br, n * 8));
+        CHK(launch_balance(ctx, k, l, (int64_t *)bl.p));
+        CHK(launch_balance(ctx, k, r, (int64_t *)br.p));
+        l = (const int64_t *)bl.p;
+        r = (const int64_t *)br.p;
     }
     return pair_distance_launch<int64_t>(ctx, n, l, r, metric, out, aux_out);
 }
@@ -68,12 +82,9 @@ KPAL_API int kpal_pair_distance(kpal_ctx *ctx, size_t n, const int64_t *host_lef
 {
     CTX_ENTER(ctx);
     if (!host_left || !host_right || !out) return set_err(KPAL_E_INVALID, "NULL pointer");
-    CHK(ensure(ctx, ctx->scratch[0], n * 8));
-    CHK(ensure(ctx, ctx->scratch[1], n * 8));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, host_left, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[1].p, host_right, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    return kpal_pair_distance_device(ctx, n, (const int64_t *)ctx->scratch[0].p, (const int64_t *)ctx->scratch[1].p,
-                                     metric, do_balance, k, out, aux_out);
+    const int64_t *dl = nullptr, *dr = nullptr;
+    CHK(upload_pair(ctx, n, host_left, host_right, &dl, &dr));
+    return kpal_pair_distance_device(ctx, n, dl, dr, metric, do_balance, k, out, aux_out);
 }
 
 KPAL_API int kpal_pair_distance_f64(kpal_ctx *ctx, size_t n, const double *host_left, const double *host_right,
@@ -82,12 +93,9 @@ KPAL_API int kpal_pair_distance_f64(kpal_ctx *ctx, size_t n, const double *host_
     CTX_ENTER(ctx);
     if (!host_left || !host_right || !out) return set_err(KPAL_E_INVALID, "NULL pointer");
     if (pairwise != KPAL_PAIRWISE_PROD && pairwise != KPAL_PAIRWISE_SUM) return set_err(KPAL_E_INVALID, "pairwise must be prod or sum");
-    CHK(ensure(ctx, ctx->scratch[0], n * 8));
-    CHK(ensure(ctx, ctx->scratch[1], n * 8));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, host_left, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[1].p, host_right, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    return pair_distance_launch<double>(ctx, n, (const double *)ctx->scratch[0].p, (const double *)ctx->scratch[1].p,
-                                        pairwise, out, aux_out);
+    const double *dl = nullptr, *dr = nullptr;
+    CHK(upload_pair(ctx, n, host_left, host_right, &dl, &dr));
+    return pair_distance_launch<double>(ctx, n, dl, dr, pairwise, out, aux_out);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -131,15 +139,6 @@ static int launch_smooth(kpal_ctx *ctx, int k, const int64_t *l, const int64_t *
     return KPAL_OK;
 }
 
-template <int METRIC>
-static void launch_option_distance(kpal_ctx *ctx, unsigned grid, bool scaled, const int64_t *l, const int64_t *r, uint64_t n,
-                                   double ls, double rs, Partial *pp)
-{
-    ProfScope ps_(ctx, "option_distance");
-    if (scaled) hipLaunchKernelGGL((option_distance_kernel<METRIC, true>), dim3(grid), dim3(256), 0, ctx->stream, l, r, n, ls, rs, pp);
-    else hipLaunchKernelGGL((option_distance_kernel<METRIC, false>), dim3(grid), dim3(256), 0, ctx->stream, l, r, n, ls, rs, pp);
-}
-
 // One pair, both vectors on the device and 16-byte aligned; `balanced`: the inputs are already
 // balanced (matrix path), so opt->do_balance is not applied again.
 int profile_distance_pair(kpal_ctx *ctx, int k, const int64_t *dl, const int64_t *dr, const kpal_distance_options *opt, bool balanced,
@@ -181,16 +180,13 @@ int profile_distance_pair(kpal_ctx *ctx, int k, const int64_t *dl, const int64_t
         scale_factors((int64_t)res[0].m, (int64_t)res[1].m, opt->down != 0, &ls, &rs);
     }
     const bool scaled = opt->do_scale != 0;
-    switch (opt->metric) {
-    case KPAL_PAIRWISE_PROD: launch_option_distance<0>(ctx, grid, scaled, l, r, n, ls, rs, pp); break;
-    case KPAL_PAIRWISE_SUM: launch_option_distance<1>(ctx, grid, scaled, l, r, n, ls, rs, pp); break;
-    case KPAL_EUCLIDEAN: launch_option_distance<2>(ctx, grid, scaled, l, r, n, ls, rs, pp); break;
-    default: launch_option_distance<3>(ctx, grid, scaled, l, r, n, ls, rs, pp); break;
-    }
-    HIPCHK(hipGetLastError());
+    CHK(with_metric(opt->metric, [&](auto m, auto s) -> int {
+        LAUNCH(ctx, "option_distance", (option_distance_kernel<m, s>), dim3(grid), dim3(256), l, r, n, ls, rs, pp);
+        return KPAL_OK;
+    }, scaled));
     const uint32_t nacc = option_nacc(opt->metric);   // 1, or the cosine's 3: the dot and the two norms
     CHK(finish_partials(ctx, nacc, grid, res));
-    *out = finish_distance(opt->metric, scaled, res[0], res[nacc / 2], res[nacc - 1]);
+    *out = option_value(opt->metric, scaled, res.data(), nacc, 1, 0);
     return KPAL_OK;
 }
 
@@ -213,11 +209,9 @@ KPAL_API int kpal_profile_distance(kpal_ctx *ctx, int k, const int64_t *host_lef
     if (!host_left || !host_right || !out) return set_err(KPAL_E_INVALID, "NULL pointer");
     CHK(check_options(opt));
     const uint64_t n = 1ULL << (2 * k);
-    CHK(ensure(ctx, ctx->scratch[0], n * 8));
-    CHK(ensure(ctx, ctx->scratch[1], n * 8));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, host_left, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[1].p, host_right, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    return profile_distance_pair(ctx, k, (const int64_t *)ctx->scratch[0].p, (const int64_t *)ctx->scratch[1].p, opt, false, out);
+    const int64_t *dl = nullptr, *dr = nullptr;
+    CHK(upload_pair(ctx, n, host_left, host_right, &dl, &dr));
+    return profile_distance_pair(ctx, k, dl, dr, opt, false, out);
 }
 
 KPAL_API int kpal_dynamic_smooth(kpal_ctx *ctx, int k, int64_t *host_left_inout, int64_t *host_right_inout,

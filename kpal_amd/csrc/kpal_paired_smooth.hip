@@ -3,7 +3,7 @@
 // (kpal_paired_smooth_distance[_device]; kdistlib.paired_distances / successive_distances, `kpal distance -m`), and the smoothed
 // tables themselves (kpal_paired_smooth_device; klib.smooth_profiles, `kpal smooth`).  Planned by pair_smooth_plan.hpp, the
 // kernels are pair_smooth_kernels.hpp.  Per chunk of pairs, whatever N is:
-//   do_balance        one launch of the set balance per distinct input range, exactly as kpal_paired_distance_device does it
+//   do_balance        one launch of the set balance per distinct input range: kpal_paired_distance_device's balanced_pair_chunk (dist_host.hpp)
 //   the pyramids      of the chunk's distinct tables once (the union of the two ranges when they are the same range or lie a
 //                     whole number of tables apart): k level launches and the codes launch (smooth_set_pyramids, kpal_cross.hip)
 //   distances         ONE launch of pair_smooth over all (pair, slice) items and ONE reduction -- no totals pass under scale:
@@ -12,29 +12,9 @@
 // Without do_smooth, and with do_positive (the masks come first: node sums depend on the partner), kpal_paired_distance_device
 // serves the call.  The inputs are never written and may alias in any way.
 #include "kpal_host.hpp"
+#include "dist_host.hpp"
 
 #include "pair_smooth_kernels.hpp"
-
-template <int MODE>
-static int launch_pair_smooth_metric(kpal_ctx *ctx, bool scaled, bool wave, unsigned grid, const PairSmoothArgs &a, Partial *pp)
-{
-    const dim3 g(grid), b(kPairSetThreads);
-    if (scaled && wave) LAUNCH(ctx, "pair_smooth", (pair_smooth_kernel<MODE, true, true>), g, b, a, pp);
-    else if (scaled) LAUNCH(ctx, "pair_smooth", (pair_smooth_kernel<MODE, true, false>), g, b, a, pp);
-    else if (wave) LAUNCH(ctx, "pair_smooth", (pair_smooth_kernel<MODE, false, true>), g, b, a, pp);
-    else LAUNCH(ctx, "pair_smooth", (pair_smooth_kernel<MODE, false, false>), g, b, a, pp);
-    return KPAL_OK;
-}
-
-static int launch_pair_smooth(kpal_ctx *ctx, int metric, bool scaled, bool wave, unsigned grid, const PairSmoothArgs &a, Partial *pp)
-{
-    switch (metric) {
-    case KPAL_PAIRWISE_PROD: return launch_pair_smooth_metric<0>(ctx, scaled, wave, grid, a, pp);
-    case KPAL_PAIRWISE_SUM: return launch_pair_smooth_metric<1>(ctx, scaled, wave, grid, a, pp);
-    case KPAL_EUCLIDEAN: return launch_pair_smooth_metric<2>(ctx, scaled, wave, grid, a, pp);
-    default: return launch_pair_smooth_metric<3>(ctx, scaled, wave, grid, a, pp);
-    }
-}
 
 // The pyramids of the distinct tables of the cn pairs (cl + i * bins, cr + i * bins): of the union of the two ranges (un tables
 // from the lower one on) or of the two sides, left first.  -> the kernels' arguments but for the grid.
@@ -47,15 +27,6 @@ static int pair_smooth_pyramids(kpal_ctx *ctx, int k, uint64_t cn, const int64_t
     CHK(smooth_set_pyramids(ctx, k, c, (uint32_t)(un ? un : 2 * cn), summary, threshold, &pyr));
     *a = PairSmoothArgs{cl, cr, pyr.sums, pyr.codes, pyr.totals, bins, pyr.stride, (uint32_t)cn, (uint32_t)pair_smooth_bin_slices(k), (uint32_t)pair_smooth_slices(k), 0,
                         (uint32_t)pair_smooth_left(cn, alias, lag, 0), (uint32_t)pair_smooth_right(cn, alias, lag, 0), k, down};
-    return KPAL_OK;
-}
-
-static int paired_checks(int k, int64_t N, const void *dev_left, const void *dev_right, const void *out)
-{
-    if (N < 1) return set_err(KPAL_E_INVALID, "N must be >= 1");
-    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
-    if (!dev_left || !dev_right || !out) return set_err(KPAL_E_INVALID, "NULL pointer");
-    if (((uintptr_t)dev_left & 15) || ((uintptr_t)dev_right & 15)) return set_err(KPAL_E_INVALID, "device tables must be 16-byte aligned");
     return KPAL_OK;
 }
 
@@ -77,33 +48,22 @@ KPAL_API int kpal_paired_smooth_distance_device(kpal_ctx *ctx, int k, int64_t N,
     for (uint64_t c0 = 0; c0 < (uint64_t)N; c0 += chunk) {
         const uint64_t cn = std::min<uint64_t>(chunk, (uint64_t)N - c0);
         const int64_t *cl = dev_left + c0 * bins, *cr = dev_right + c0 * bins;
-        const uint64_t un = pair_smooth_union(cn, alias, lag);
-        if (do_balance) {
-            // balanced once per table, as kpal_paired_distance_device balances them
-            CHK(ensure(ctx, ctx->scratch[2], (size_t)pair_set_balance_bytes(cn, bins, un)));
-            int64_t *b = (int64_t *)ctx->scratch[2].p;
-            if (un) {
-                CHK(balance_set_launch(ctx, k, (size_t)un, lag < 0 ? cr : cl, b));
-                cl = b + (lag < 0 ? (uint64_t)(-lag) : 0) * bins;
-                cr = b + (lag > 0 ? (uint64_t)lag : 0) * bins;
-            } else {
-                CHK(balance_set_launch(ctx, k, (size_t)cn, cl, b));
-                CHK(balance_set_launch(ctx, k, (size_t)cn, cr, b + cn * bins));
-                cl = b;
-                cr = b + cn * bins;
-            }
-        }
+        const uint64_t un = pair_set_union(cn, alias, lag);
+        if (do_balance) CHK(balanced_pair_chunk(ctx, k, cn, bins, un, lag, &cl, &cr));   // as kpal_paired_distance_device balances them
         if (partials_too_many(cn * nacc, slices)) return set_err(KPAL_E_INVALID, "paired distance: %llu pairs are too many for one chunk", (unsigned long long)cn);
         CHK(ensure(ctx, ctx->partials, (size_t)(cn * nacc * slices) * sizeof(Partial)));
         PairSmoothArgs a;
         CHK(pair_smooth_pyramids(ctx, k, cn, cl, cr, un, alias, lag, opt->summary, opt->threshold, opt->down ? 1 : 0, &a));
         a.units = (uint32_t)pair_smooth_units(cn, k);
         Partial *pp = (Partial *)ctx->partials.p;
-        CHK(launch_pair_smooth(ctx, opt->metric, scaled, wave, (unsigned)pair_smooth_workgroups(cn, k, (uint64_t)ctx->num_cu), a, pp));
+        const dim3 grid((unsigned)pair_smooth_workgroups(cn, k, (uint64_t)ctx->num_cu)), block(kPairSetThreads);
+        CHK(with_metric(opt->metric, [&](auto m, auto s, auto w) -> int {
+            LAUNCH(ctx, "pair_smooth", (pair_smooth_kernel<m, s, w>), grid, block, a, pp);
+            return KPAL_OK;
+        }, scaled, wave));
         std::vector<Partial> res;
         CHK(finish_partials(ctx, (uint32_t)(cn * nacc), slices, res));
-        for (uint64_t p = 0; p < cn; ++p)
-            out[c0 + p] = finish_distance(opt->metric, scaled, res[p], res[(nacc / 2) * cn + p], res[(nacc - 1) * cn + p]);
+        for (uint64_t p = 0; p < cn; ++p) out[c0 + p] = option_value(opt->metric, scaled, res.data(), nacc, cn, p);
     }
     return KPAL_OK;
 }
@@ -111,18 +71,7 @@ KPAL_API int kpal_paired_smooth_distance_device(kpal_ctx *ctx, int k, int64_t N,
 KPAL_API int kpal_paired_smooth_distance(kpal_ctx *ctx, int k, int64_t N, const int64_t *const *host_left, const int64_t *const *host_right,
                                          const kpal_distance_options *opt, double *out)
 {
-    CTX_ENTER(ctx);
-    if (N < 1) return set_err(KPAL_E_INVALID, "N must be >= 1");
-    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
-    if (!host_left || !host_right || !out) return set_err(KPAL_E_INVALID, "NULL pointer");
-    CHK(check_options(opt));
-    const uint64_t bins = 1ULL << (2 * k);
-    if (N > 0x3fffffff || !transform_bytes_fit((uint64_t)N * 2, bins)) return set_err(KPAL_E_INVALID, "%lld pairs at k=%d: too many bytes", (long long)N, k);
-    for (int64_t p = 0; p < N; ++p)
-        if (!host_left[p] || !host_right[p]) return set_err(KPAL_E_INVALID, "%s profile %lld is NULL", host_left[p] ? "right" : "left", (long long)p);
-    int64_t *dl = nullptr, *dr = nullptr;
-    CHK(upload_rectangle(ctx, bins, (int)N, host_left, (int)N, host_right, &dl, &dr));
-    return kpal_paired_smooth_distance_device(ctx, k, N, dl, dr, opt, 0, out);
+    return paired_host_entry(ctx, k, N, host_left, host_right, opt, out, kpal_paired_smooth_distance_device);
 }
 
 // Whether the byte ranges [a, a + n) and [b, b + n) meet.
@@ -154,7 +103,7 @@ KPAL_API int kpal_paired_smooth_device(kpal_ctx *ctx, int k, int64_t N, const in
     for (uint64_t c0 = 0; c0 < (uint64_t)N; c0 += chunk) {
         const uint64_t cn = std::min<uint64_t>(chunk, (uint64_t)N - c0);
         PairSmoothArgs a;
-        CHK(pair_smooth_pyramids(ctx, k, cn, dev_left + c0 * bins, dev_right + c0 * bins, pair_smooth_union(cn, alias, lag), alias, lag, summary, threshold, 0, &a));
+        CHK(pair_smooth_pyramids(ctx, k, cn, dev_left + c0 * bins, dev_right + c0 * bins, pair_set_union(cn, alias, lag), alias, lag, summary, threshold, 0, &a));
         a.units = (uint32_t)pair_set_units(cn, bins);
         const dim3 g((unsigned)pair_set_workgroups(cn, bins, (uint64_t)ctx->num_cu)), b(kPairSetThreads);
         if (wave) LAUNCH(ctx, "pair_smooth_apply", pair_smooth_apply_kernel<true>, g, b, a, dev_out_left + c0 * bins, dev_out_right + c0 * bins);

@@ -113,6 +113,17 @@ KPAL_MATRIX_HD uint64_t pair_set_union_tables(uint64_t chunk, int64_t lag)
     const uint64_t d = lag < 0 ? (uint64_t)(-lag) : (uint64_t)lag;
     return d < chunk ? chunk + d : 0;
 }
+// Tables of the union that serves both sides of a chunk of `chunk` pairs (alias, lag: pair_set_alias), 0: two separate sides.
+KPAL_MATRIX_HD uint64_t pair_set_union(uint64_t chunk, int alias, int64_t lag)
+{
+    return alias == kPairSetSame ? chunk : alias == kPairSetLag ? pair_set_union_tables(chunk, lag) : 0;
+}
+// The distinct tables of such a chunk: those of the union, or of the two sides.
+KPAL_MATRIX_HD uint64_t pair_set_tables(uint64_t chunk, int alias, int64_t lag)
+{
+    const uint64_t un = pair_set_union(chunk, alias, lag);
+    return un ? un : 2 * chunk;
+}
 // Bytes of the balanced copies of such a chunk (union_tables: 0 for two separate sides).
 KPAL_MATRIX_HD uint64_t pair_set_balance_bytes(uint64_t chunk, uint64_t bins, uint64_t union_tables)
 {

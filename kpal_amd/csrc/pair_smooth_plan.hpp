@@ -52,16 +52,10 @@ KPAL_MATRIX_HD uint64_t pair_smooth_workgroups(uint64_t n_pairs, int k, uint64_t
 // The units of the apply kernel are those of the bins alone: pair_set_units(n_pairs, 4^k).
 
 // ---- the pyramid set of a chunk -------------------------------------------------------------------------------------------------------
-// Tables of the union that serves both sides of a chunk of `chunk` pairs (alias, lag: pair_set_alias), 0: two separate sides.
-KPAL_MATRIX_HD uint64_t pair_smooth_union(uint64_t chunk, int alias, int64_t lag)
-{
-    return alias == kPairSetSame ? chunk : alias == kPairSetLag ? pair_set_union_tables(chunk, lag) : 0;
-}
-KPAL_MATRIX_HD uint64_t pair_smooth_tables(uint64_t chunk, int alias, int64_t lag)
-{
-    const uint64_t un = pair_smooth_union(chunk, alias, lag);
-    return un ? un : 2 * chunk;
-}
+// The pyramids of a chunk are those of its distinct tables: pair_set_union / pair_set_tables (pair_set_plan.hpp), which the
+// balanced copies share, under this plan's names.
+KPAL_MATRIX_HD uint64_t pair_smooth_union(uint64_t chunk, int alias, int64_t lag) { return pair_set_union(chunk, alias, lag); }
+KPAL_MATRIX_HD uint64_t pair_smooth_tables(uint64_t chunk, int alias, int64_t lag) { return pair_set_tables(chunk, alias, lag); }
 // The pyramid of pair p's left / right table in the set of such a chunk.
 KPAL_MATRIX_HD uint64_t pair_smooth_left(uint64_t chunk, int alias, int64_t lag, uint64_t pair)
 {

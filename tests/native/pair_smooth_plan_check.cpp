@@ -11,8 +11,8 @@
 //                                     the shares of the workgroups sum to the units and differ by at most one, else 0
 //   partial  K N NACC              -> 1 if pair_set_partial over pair_smooth_slices(K) is a bijection onto [0, NACC * N * slices)
 //                                     (enumerated up to 2^22 values, else checked at both ends and 4096 places between); that size
-//   chunk    K N BALANCE CHUNK ALIAS LAG -> pair_smooth_chunk, pair_smooth_tables of that chunk, smooth_scratch_bytes of those
-//   tables   CHUNK ALIAS LAG PAIR  -> pair_smooth_union pair_smooth_tables pair_smooth_left pair_smooth_right
+//   chunk    K N BALANCE CHUNK ALIAS LAG -> pair_smooth_chunk, pair_set_tables of that chunk, smooth_scratch_bytes of those
+//   tables   CHUNK ALIAS LAG PAIR  -> pair_set_union pair_set_tables pair_smooth_left pair_smooth_right
 //   batched  SMOOTH POSITIVE       -> pair_smooth_batched
 // Test infrastructure.
 #include <cinttypes>
@@ -80,11 +80,11 @@ int main()
             printf("%d %" PRIu64 "\n", ok, size);
         } else if (!strcmp(what, "chunk") && got == 6 && k) {
             const uint64_t c = pair_smooth_chunk(k, (uint64_t)a[1], a[2] != 0, (uint64_t)a[3], (int)a[4], (int64_t)a[5]);
-            const uint64_t t = pair_smooth_tables(c, (int)a[4], (int64_t)a[5]);
+            const uint64_t t = pair_set_tables(c, (int)a[4], (int64_t)a[5]);
             printf("%" PRIu64 " %" PRIu64 " %" PRIu64 "\n", c, t, smooth_scratch_bytes(k, t));
         } else if (!strcmp(what, "tables") && got == 4)
-            printf("%" PRIu64 " %" PRIu64 " %" PRIu64 " %" PRIu64 "\n", pair_smooth_union((uint64_t)a[0], (int)a[1], (int64_t)a[2]),
-                   pair_smooth_tables((uint64_t)a[0], (int)a[1], (int64_t)a[2]), pair_smooth_left((uint64_t)a[0], (int)a[1], (int64_t)a[2], (uint64_t)a[3]),
+            printf("%" PRIu64 " %" PRIu64 " %" PRIu64 " %" PRIu64 "\n", pair_set_union((uint64_t)a[0], (int)a[1], (int64_t)a[2]),
+                   pair_set_tables((uint64_t)a[0], (int)a[1], (int64_t)a[2]), pair_smooth_left((uint64_t)a[0], (int)a[1], (int64_t)a[2], (uint64_t)a[3]),
                    pair_smooth_right((uint64_t)a[0], (int)a[1], (int64_t)a[2], (uint64_t)a[3]));
         else if (!strcmp(what, "batched") && got == 2) printf("%d\n", pair_smooth_batched(a[0] != 0, a[1] != 0) ? 1 : 0);
         else {

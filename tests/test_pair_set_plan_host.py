@@ -60,8 +60,9 @@ def test_header_knows_no_gpu():
     for user, names in (('pair_set_kernels.hpp', ('kPairSetThreads', 'kPairSetWaves', 'kPairSetUnroll', 'pair_set_slice_begin(', 'pair_set_slice_end(',
                                                   'pair_set_partial(')),
                         ('kpal_paired.hip', ('pair_set_wave_form(', 'pair_set_slices(', 'pair_set_units(', 'pair_set_workgroups(', 'pair_set_chunk(',
-                                             'pair_set_alias(', 'pair_set_union_tables(', 'pair_set_balance_bytes(', 'kPairSetSame', 'kPairSetLag',
-                                             'partials_too_many('))):
+                                             'pair_set_alias(', 'pair_set_union(', 'balanced_pair_chunk(', 'partials_too_many(')),
+                        ('pair_set_plan.hpp', ('pair_set_union_tables(', 'kPairSetSame', 'kPairSetLag')),      # pair_set_union: the union of a chunk
+                        ('dist_host.hpp', ('pair_set_balance_bytes(', 'balance_set_launch('))):                # balanced_pair_chunk: shared with kpal_paired_smooth.hip
         text = re.sub(r'//.*', '', open(os.path.join(CSRC, user)).read())
         assert all(n in text for n in names), user
     # the term of a bin is defined once, for the rectangle kernels and these

@@ -73,9 +73,10 @@ def test_header_knows_no_gpu():
     assert '#include "pair_set_plan.hpp"' in header and '#include "smooth_plan.hpp"' in header
     for user, names in (('pair_smooth_kernels.hpp', ('kPairSetThreads', 'kPairSetWaves', 'kPairSetUnroll', 'pair_set_slice_begin(', 'pair_set_slice_end(',
                                                      'pair_set_partial(', 'pair_smooth_node_begin(', 'kPairSmoothSliceNodes', 'opt_term<', 'cross_opt_scale(')),
-                        ('kpal_paired_smooth.hip', ('pair_smooth_chunk(', 'pair_smooth_union(', 'pair_smooth_left(', 'pair_smooth_right(', 'pair_smooth_units(',
+                        ('kpal_paired_smooth.hip', ('pair_smooth_chunk(', 'pair_set_union(', 'pair_smooth_left(', 'pair_smooth_right(', 'pair_smooth_units(',
                                                     'pair_smooth_workgroups(', 'pair_smooth_slices(', 'pair_smooth_batched(', 'pair_set_alias(',
-                                                    'pair_set_balance_bytes(', 'balance_set_launch(', 'smooth_set_pyramids(', 'partials_too_many('))):
+                                                    'balanced_pair_chunk(', 'smooth_set_pyramids(', 'partials_too_many(')),
+                        ('dist_host.hpp', ('pair_set_balance_bytes(', 'balance_set_launch('))):      # balanced_pair_chunk: shared with kpal_paired.hip
         text = re.sub(r'//.*', '', open(os.path.join(CSRC, user)).read())
         assert all(n in text for n in names), (user, [n for n in names if n not in text])
     unit = open(os.path.join(CSRC, 'kpal_paired_smooth.hip')).read()
