@@ -20,6 +20,8 @@ LINKED pairs of two sets, ``left[i]`` against ``right[i]``, or of one set agains
 (``kpal_paired_distance_device``, with dynamic smoothing ``kpal_paired_smooth_distance_device``: a number of launches that
 does not grow with the number of pairs).
 """
+import contextlib
+
 import numpy as np
 
 from . import _native, metrics
@@ -184,11 +186,8 @@ def distance_matrix(profiles, output, precision, dist):
     elif options is not None and options.do_smooth:
         # gathered once; one pyramid of node sums and codes per profile, every pair through the rectangle kernels
         ctx = _cross_context(profiles)
-        pset = _DeviceSet(ctx, profiles)
-        try:
+        with _DeviceSet(ctx, profiles) as pset:
             values = ctx.smooth_distance_matrix_device(count, profiles[0].length, pset.ptr, options)
-        finally:
-            pset.release()
     elif options is not None:
         # profiles uploaded (and balanced) once, every pair through the option kernels
         values = _native.context().profile_distance_matrix([p.counts for p in profiles], profiles[0].length, options)
@@ -225,22 +224,26 @@ def _chunked(iterable, size):
         yield chunk
 
 
+def _device_table(profile):
+    """(context, device address) of the table of ``profile`` while it is in HBM only, else None -- of any object: what has no
+    ``_device_counts`` (the profiles of the reference, stand-ins) is not in HBM."""
+    at = getattr(profile, '_device_counts', None)
+    return at() if at is not None else None
+
+
 class _DeviceSet(object):
     """The tables of ``profiles`` (one k) as consecutive int64 tables in HBM on ``ctx``: where they lie when they are
     consecutive tables of one batch on that context, otherwise gathered (device-to-device copies for tables in HBM on that
-    context, uploads for host counts) into an allocation that ``release`` frees."""
+    context, uploads for host counts) into an allocation that ``release`` -- the end of a ``with`` -- frees."""
 
     def __init__(self, ctx, profiles):
         k = profiles[0].length
         table_bytes = 8 * 4 ** k
-        devs = []
-        for p in profiles:
-            d = getattr(p, '_device_counts', None)
-            d = d() if d is not None else None
-            devs.append(d if d and d[0] is ctx else None)
+        devs = [d if d and d[0] is ctx else None for d in map(_device_table, profiles)]
         self.ctx, self.owned = ctx, None
-        if all(devs) and all(devs[i][1] == devs[0][1] + i * table_bytes for i in range(len(devs))):
-            self.ptr = devs[0][1]
+        first = devs[0]
+        if first and all(d and d[1] == first[1] + i * table_bytes for i, d in enumerate(devs)):
+            self.ptr = first[1]
             return
         self.ptr = self.owned = ctx.alloc(len(profiles) * table_bytes)
         try:
@@ -259,19 +262,32 @@ class _DeviceSet(object):
             self.ctx.sync()
             self.ctx.free(owned)
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+
+
+def _right_set(ctx, lset, left, right):
+    """The device set of ``right`` for a ``with``: ``lset`` itself, which stays its maker's to release, when both sides are
+    the same profiles."""
+    if len(right) == len(left) and all(a is b for a, b in zip(right, left)):
+        return contextlib.nullcontext(lset)
+    return _DeviceSet(ctx, right)
+
 
 def _cross_context(profiles):
     """The context the first device-resident profile lives on, else the default one."""
     for p in profiles:
-        d = getattr(p, '_device_counts', None)
-        d = d() if d is not None else None
+        d = _device_table(p)
         if d:
             return d[0]
     return _native.context()
 
 
 def _integer_counts(profile):
-    return getattr(profile, '_device_counts', lambda: None)() is not None or np.asanyarray(profile.counts).dtype.kind in 'iub'
+    return _device_table(profile) is not None or np.asanyarray(profile.counts).dtype.kind in 'iub'
 
 
 def cross_distances(left_profiles, right_profiles, dist, max_bytes=None):
@@ -307,15 +323,13 @@ def cross_distances(left_profiles, right_profiles, dist, max_bytes=None):
     per = _chunk_tables(table_bytes, CROSS_MAX_BYTES if max_bytes is None else max_bytes)
     ctx = _cross_context(left)
     blocks = []
-    lset = _DeviceSet(ctx, left)
-    try:
+    with _DeviceSet(ctx, left) as lset:
         for chunk in _chunked(right_profiles, per):
             if any(p.length != k or not _integer_counts(p) for p in chunk):
                 # a mixed-k pair raises what dist.distance raises; other counts (scaled profiles) keep its formulation
                 blocks.append(np.array([[dist.distance(l, r) for r in chunk] for l in left], dtype=np.float64))
                 continue
-            rset = lset if (len(chunk) == len(left) and all(a is b for a, b in zip(chunk, left))) else _DeviceSet(ctx, chunk)
-            try:
+            with _right_set(ctx, lset, left, chunk) as rset:
                 if plain:
                     blocks.append(ctx.cross_distance_device(k, len(left), lset.ptr, len(chunk), rset.ptr, metric,
                                                             do_balance=dist._do_balance))
@@ -323,11 +337,6 @@ def cross_distances(left_profiles, right_profiles, dist, max_bytes=None):
                     blocks.append(ctx.cross_smooth_distance_device(k, len(left), lset.ptr, len(chunk), rset.ptr, options))
                 else:
                     blocks.append(ctx.cross_profile_distance_device(k, len(left), lset.ptr, len(chunk), rset.ptr, options))
-            finally:
-                if rset is not lset:
-                    rset.release()
-    finally:
-        lset.release()
     if not blocks:
         return np.zeros((len(left), 0), dtype=np.float64)
     return np.concatenate(blocks, axis=1)
@@ -371,17 +380,9 @@ def paired_distances(left_profiles, right_profiles, dist, max_bytes=None):
     blocks = []
     for at in range(0, len(left), per):
         lgroup, rgroup = left[at:at + per], right[at:at + per]
-        lset = _DeviceSet(ctx, lgroup)
-        try:
-            rset = lset if all(a is b for a, b in zip(lgroup, rgroup)) else _DeviceSet(ctx, rgroup)
-            try:
-                entry = ctx.paired_smooth_distance_device if options.do_smooth else ctx.paired_distance_device
-                blocks.append(entry(k, len(lgroup), lset.ptr, rset.ptr, options))
-            finally:
-                if rset is not lset:
-                    rset.release()
-        finally:
-            lset.release()
+        with _DeviceSet(ctx, lgroup) as lset, _right_set(ctx, lset, lgroup, rgroup) as rset:
+            entry = ctx.paired_smooth_distance_device if options.do_smooth else ctx.paired_distance_device
+            blocks.append(entry(k, len(lgroup), lset.ptr, rset.ptr, options))
     return np.concatenate(blocks)
 
 
@@ -405,12 +406,9 @@ def successive_distances(profiles, dist, lag=1):
         return np.array([dist.distance(profiles[i], profiles[i + lag]) for i in range(pairs)], dtype=np.float64)
     k = profiles[0].length
     ctx = _cross_context(profiles)
-    pset = _DeviceSet(ctx, profiles)
-    try:
+    with _DeviceSet(ctx, profiles) as pset:
         entry = ctx.paired_smooth_distance_device if options.do_smooth else ctx.paired_distance_device
         return entry(k, pairs, pset.ptr, pset.ptr + lag * 8 * 4 ** k, options)
-    finally:
-        pset.release()
 
 
 def nearest(values, n):
@@ -430,7 +428,7 @@ def _left_chunks(profiles, max_bytes):
     chunk, size, run = [], 0, None   # run: (context, address) the next table must have to continue the chunk's run
     for p in profiles:
         nbytes = 8 * 4 ** p.length
-        at = getattr(p, '_device_counts', lambda: None)()
+        at = _device_table(p)
         if chunk and (size + nbytes > max_bytes or (run is not None and at is not None and at != run)):
             yield chunk
             chunk, size = [], 0
@@ -488,44 +486,34 @@ def _nearest_chunks(left_profiles, right, dist, n, max_bytes):
     bounds = cross_chunks(8 * 4 ** right[0].length, R, max_bytes) if R else []
     whole = list(right[0:R]) if len(bounds) == 1 else None    # the right side when it is resident for the whole call
     ctx = whole_set = None
-    try:
+    with contextlib.ExitStack() as whole_call:       # releases the right side that is resident for the whole call
         for chunk in _left_chunks(left_profiles, max_bytes):
             rows, k = len(chunk), chunk[0].length
             distances = np.full((rows, m), np.nan, dtype=np.float64)
             indices = np.full((rows, m), -1, dtype=np.int64)
             fast_left = options is not None and all(p.length == k and _integer_counts(p) for p in chunk)
             have, lset = 0, None
-            try:
+            with contextlib.ExitStack() as this_chunk:   # releases the left set, made when the first block needs it
                 for start, stop in bounds:
                     block = whole if whole is not None else list(right[start:stop])
                     if fast_left and all(p.length == k and _integer_counts(p) for p in block):
                         if ctx is None:
                             ctx = _cross_context(chunk)
                         if lset is None:
-                            lset = _DeviceSet(ctx, chunk)
+                            lset = this_chunk.enter_context(_DeviceSet(ctx, chunk))
                         if whole is not None and whole_set is None:
-                            whole_set = _DeviceSet(ctx, whole)
-                        rset = whole_set if whole is not None else _DeviceSet(ctx, block)
-                        try:
+                            whole_set = whole_call.enter_context(_DeviceSet(ctx, whole))
+                        with (contextlib.nullcontext(whole_set) if whole is not None else _DeviceSet(ctx, block)) as rset:
                             ctx.cross_nearest_device(k, rows, lset.ptr, stop - start, rset.ptr, options, m, right_first=start,
                                                      have=have, dist=distances, index=indices)
-                        finally:
-                            if rset is not whole_set:
-                                rset.release()
                         have = min(m, have + stop - start)
                     else:
                         # a mixed-k pair raises what dist.distance raises; other counts keep its formulation
                         values = np.array([[dist.distance(l, r) for r in block] for l in chunk], dtype=np.float64)
                         have = _merge_nearest(distances, indices, have, values.reshape(rows, stop - start), start, m)
                     block = None
-            finally:
-                if lset is not None:
-                    lset.release()
             yield chunk, indices, distances
             chunk = lset = None
-    finally:
-        if whole_set is not None:
-            whole_set.release()
 
 
 def nearest_profiles(left_profiles, right_profiles, dist, n, max_bytes=None):
@@ -574,12 +562,8 @@ def _write_matrix(output, count, values, precision):
 
 def _device_pair(left, right):
     """(context, device address of left, of right) when both profiles' tables are still in HBM on one context, else None."""
-    a = getattr(left, '_device_counts', None)
-    b = getattr(right, '_device_counts', None)
-    if a is None or b is None or left.length != right.length:
-        return None
-    a, b = a(), b()
-    if not a or not b or a[0] is not b[0]:
+    a, b = _device_table(left), _device_table(right)
+    if not a or not b or a[0] is not b[0] or left.length != right.length:
         return None
     return a[0], a[1], b[1]
 
@@ -588,31 +572,17 @@ def _device_matrix(profiles, dist, metric):
     """The matrix values of profiles whose tables are ALL still in HBM (one context, one k) without a transfer: consecutive
     tables of one batch are used where they lie, anything else is gathered by device-to-device copies first.  None when a
     profile has host counts, or when a user-supplied callable keeps the distance in Python."""
-    devs = []
-    for p in profiles:
-        d = getattr(p, '_device_counts', None)
-        d = d() if d is not None else None
-        if not d or (devs and d[0] is not devs[0][0]):
-            return None
-        devs.append(d)
+    devs = list(map(_device_table, profiles))
+    if not devs[0] or not all(d and d[0] is devs[0][0] for d in devs):
+        return None
     plain = dist._is_plain() and metric is not None and metric != _native.COSINE
     options = None if plain else dist._native_options()
     if not plain and options is None:
         return None
     ctx, k, P = devs[0][0], profiles[0].length, len(profiles)
-    table_bytes = 8 * 4 ** k
-    base, gathered = devs[0][1], None
-    try:
-        if any(devs[i][1] != base + i * table_bytes for i in range(P)):
-            gathered = base = ctx.alloc(P * table_bytes)
-            for i in range(P):
-                ctx.d2d(base + i * table_bytes, devs[i][1], table_bytes)
+    with _DeviceSet(ctx, profiles) as pset:
         if not plain and options.do_smooth:    # one call: a pyramid per profile, the pairs' live elements inside the triangle kernels
-            return ctx.smooth_distance_matrix_device(P, k, base, options)
+            return ctx.smooth_distance_matrix_device(P, k, pset.ptr, options)
         if not plain:    # one call: profiles balanced once, the partner-dependent steps inside the triangle kernels
-            return ctx.profile_distance_matrix_device(P, k, base, options)
-        return ctx.distance_matrix_device(P, k, base, metric, do_balance=dist._do_balance)
-    finally:
-        if gathered is not None:
-            ctx.sync()
-            ctx.free(gathered)
+            return ctx.profile_distance_matrix_device(P, k, pset.ptr, options)
+        return ctx.distance_matrix_device(P, k, pset.ptr, metric, do_balance=dist._do_balance)

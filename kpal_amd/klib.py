@@ -1,5 +1,5 @@
-"""Drop-in for ``kpal.klib``: the :class:`Profile` container with k-mer counting, balance and
-split running as HIP kernels on an MI355X.
+"""Drop-in for ``kpal.klib``: the :class:`Profile` container with k-mer counting, balance, split, merge, shrink and the
+statistics running as HIP kernels on an MI355X.
 
 Same constructor, classmethods, methods, properties and error behaviour as the reference class
 (kpal/klib.py:26-487).  Differences are internal only:
@@ -12,13 +12,21 @@ Same constructor, classmethods, methods, properties and error behaviour as the r
   lines starting with ``>`` open a record whose name is the first whitespace-delimited token;
   the record's remaining lines are concatenated with surrounding whitespace removed; text before
   the first ``>`` is ignored.
-* ``balance`` / ``split`` call ``kpal_balance`` / ``kpal_split``.
+* ``balance`` / ``split`` / ``merge`` / ``shrink`` and the statistics of integer counts call ``kpal_balance`` / ``kpal_split`` /
+  ``kpal_merge`` / ``kpal_shrink`` / ``kpal_stats``.
+* A freshly counted table stays in HBM (``_DeviceBatch``) until something asks for ``counts``, within a budget of live bytes.
+* Beyond the reference: one profile per record, per read and per sliding window (``from_fasta_by_record`` ...), and the
+  operations over whole SETS of profiles -- ``summaries``, ``strand_balances``, ``distributions``, ``balance_profiles``,
+  ``shrink_profiles``, ``merge_profiles``, ``smooth_profiles``, ``pooled`` -- in launches that do not grow with the set.  They
+  share one core: ``_may_stay`` (the residency budget), ``_groups`` (places by k-mer length in groups of bounded bytes) and
+  ``kdistlib._DeviceSet`` (profiles as consecutive device tables, where they lie or gathered).
 
-There is no CPU fallback for those paths: without libkpal_hip.so or without a GPU they raise.
-Container-only helpers (``merge``, ``shrink``, ``shuffle``, statistics, printers, HDF5 I/O) are
-not part of the hot path and use NumPy like the reference.
+There is no CPU fallback for those paths: without libkpal_hip.so or without a GPU they raise.  Only what cannot enter a
+kernel -- non-integer counts (scaled profiles), user callables, ``shuffle``, the printers, HDF5 I/O -- uses NumPy like the
+reference.
 """
 import codecs
+import contextlib
 import io
 import itertools
 import math
@@ -42,7 +50,7 @@ _GATHER_THREADS = max(1, min(64, int(os.environ.get('KPAL_GATHER_THREADS', '16')
 _JOIN_BLOCK = 4096       # sequences joined per C-level call
 _RECORD_BATCH_BYTES = 1 << 30   # tables counted per from_fasta_by_record batch
 # from_fasta_by_record leaves its tables in HBM (Profile.counts downloads on first access) while no more than this many bytes of
-# them are alive; past it a batch is downloaded at once, as before round 6 (KPAL_DEVICE_PROFILE_BYTES; 0: always download)
+# them are alive; past it a batch is downloaded at once into one host array (KPAL_DEVICE_PROFILE_BYTES; 0: always download)
 _DEVICE_PROFILE_BYTES = int(os.environ.get('KPAL_DEVICE_PROFILE_BYTES', str(64 << 30)))
 
 
@@ -71,7 +79,7 @@ class _DeviceBatch(object):
     def table(self, index):
         """Table ``index`` on the host.  The first request brings the WHOLE batch over in one copy (a profile at a time cost
         140 us per 512 KiB table: `kpal count --by-record` asks for every one of them); the rows are views of that array, as
-        the tables of a batch were before round 6."""
+        the tables of a batch that is downloaded at once are."""
         if self.host is None:
             host = np.empty((self.n_tables, self.nbytes // (8 * self.n_tables)), dtype=np.int64)
             self.ctx.d2h(host, self.ptr)
@@ -103,6 +111,37 @@ class _DeviceBatch(object):
         except Exception:       # pragma: no cover  (interpreter shutdown)
             pass
 
+
+def _may_stay(nbytes):
+    """Whether ``nbytes`` more of tables may stay in HBM: the budget of live device tables (0: none ever does)."""
+    return bool(_DEVICE_PROFILE_BYTES) and _DeviceBatch.live_bytes + nbytes <= _DEVICE_PROFILE_BYTES
+
+
+def _tables_per_group(k, sides=1):
+    """Places of ``sides`` tables of 4^k counts each that make ``_RECORD_BATCH_BYTES``, never fewer than one."""
+    return max(1, _RECORD_BATCH_BYTES // (sides * 8 * 4 ** k))
+
+
+def _groups(places, length_of, sides=1):
+    """``places`` by k-mer length (``length_of(place)``), ascending k, in groups of at most ``_RECORD_BATCH_BYTES`` over
+    ``sides`` tables per place, never fewer than one place: yields ``(k, group)``."""
+    by_length = {}
+    for i in places:
+        by_length.setdefault(length_of(i), []).append(i)
+    for k, same in sorted(by_length.items()):
+        per = _tables_per_group(k, sides)
+        for at in range(0, len(same), per):
+            yield k, same[at:at + per]
+
+
+def _kmer_length(length):
+    """``length`` as an integer; ValueError unless it is a k-mer length the library counts."""
+    length = int(length)
+    if length < 1 or length > _native.KPAL_MAX_K:
+        raise ValueError('k-mer length must be in 1..%d (got %d)' % (_native.KPAL_MAX_K, length))
+    return length
+
+
 _FASTA_CHUNK = 64 << 20  # FASTA text read per device feed (cut back to a record boundary)
 _DROPPED = {ord(' '): None, ord('\r'): None}   # removed from the joined record (Biopython's SimpleFastaParser)
 
@@ -129,6 +168,14 @@ def _fasta_records(handle):
         yield name, ''.join(parts).translate(_DROPPED)
 
 
+def _ascii_compatible(handle):
+    """Whether the bytes under the text handle ``handle`` are its ASCII text: an ASCII-compatible encoding."""
+    try:
+        return codecs.lookup(handle.encoding or '').name in ('utf-8', 'ascii', 'iso8859-1')
+    except LookupError:
+        return False
+
+
 def _plain_file(handle):
     """``(path, byte position)`` when ``handle`` is an ordinary file opened for reading whose raw bytes ARE its text and whose
     position is known -- an ``open(path)`` / ``open(path, 'rb')`` / ``argparse.FileType('r')`` handle on a regular file, in an
@@ -138,10 +185,7 @@ def _plain_file(handle):
     raw = handle
     text_mode = isinstance(handle, io.TextIOWrapper)
     if text_mode:
-        try:
-            if codecs.lookup(handle.encoding or '').name not in ('utf-8', 'ascii', 'iso8859-1'):
-                return None
-        except LookupError:
+        if not _ascii_compatible(handle):
             return None
         raw = handle.buffer
     if isinstance(raw, io.BufferedReader):
@@ -194,9 +238,9 @@ def _byte_reader(handle):
     encoding), else the handle itself."""
     if isinstance(handle, io.TextIOWrapper):
         try:
-            if codecs.lookup(handle.encoding or '').name in ('utf-8', 'ascii', 'iso8859-1') and handle.tell() == 0:
+            if _ascii_compatible(handle) and handle.tell() == 0:
                 return handle.buffer, handle.encoding
-        except (LookupError, OSError, ValueError):
+        except (OSError, ValueError):
             pass
     return handle, 'ascii'
 
@@ -379,8 +423,7 @@ def _window_arguments(length, window, step):
     ``1 <= step <= window`` and ``step`` divides ``window``."""
     length, window = int(length), int(window)
     step = window if step is None else int(step)
-    if length < 1 or length > _native.KPAL_MAX_K:
-        raise ValueError('k-mer length must be in 1..%d (got %d)' % (_native.KPAL_MAX_K, length))
+    _kmer_length(length)
     if window < length:
         raise ValueError('the window (%d) must be at least as long as the k-mers (%d)' % (window, length))
     if step < 1 or step > window or window % step:
@@ -392,9 +435,7 @@ def _window_arguments(length, window, step):
 
 def _read_arguments(length, min_quality, quality_offset):
     """``length`` as an integer; ValueError unless it is a k-mer length and the mask options are those of ``from_fastq``."""
-    length = int(length)
-    if length < 1 or length > _native.KPAL_MAX_K:
-        raise ValueError('k-mer length must be in 1..%d (got %d)' % (_native.KPAL_MAX_K, length))
+    length = _kmer_length(length)
     _native.fastq_options_check(min_quality, quality_offset)
     return length
 
@@ -406,6 +447,14 @@ def _fastq_reads(ctx, handle, prefix, min_quality, quality_offset):
         reads = ctx.fastq_flatten(indexed.text, min_quality, quality_offset).split(b'\n')[1:]
         for pair in zip(names, reads):
             yield pair
+
+
+def _named_sequences(handle, prefix, fastq):
+    """``(name, sequence)`` per record of a FASTA handle -- with ``fastq = (min_quality, quality_offset)``, per read of a FASTQ
+    handle -- for a k whose table alone exceeds the batch budget: ``from_sequences`` then counts them one by one."""
+    if fastq is not None:
+        return _fastq_reads(_native.context(), handle, prefix, fastq[0], fastq[1])
+    return ((prefix + (record_name or str(i + 1)), seq) for i, (record_name, seq) in enumerate(_fasta_records(handle)))
 
 
 def _join_block(block):
@@ -487,20 +536,11 @@ def _device_sets(profiles, indices):
     """``indices`` -- places in ``profiles`` of integer profiles -- by k-mer length and in groups of at most
     ``_RECORD_BATCH_BYTES`` of tables: yields (places, context, device address of their consecutive tables, k).  Tables that
     are consecutive in one batch are used where they lie, others are gathered (``kdistlib._DeviceSet``)."""
-    by_length = {}
-    for i in indices:
-        by_length.setdefault(profiles[i].length, []).append(i)
-    for k, places in sorted(by_length.items()):
-        per = max(1, _RECORD_BATCH_BYTES // (8 * 4 ** k))
-        for at in range(0, len(places), per):
-            group = places[at:at + per]
-            members = [profiles[i] for i in group]
-            ctx = kdistlib._cross_context(members)
-            dset = kdistlib._DeviceSet(ctx, members)
-            try:
-                yield group, ctx, dset.ptr, k
-            finally:
-                dset.release()
+    for k, group in _groups(indices, lambda i: profiles[i].length):
+        members = [profiles[i] for i in group]
+        ctx = kdistlib._cross_context(members)
+        with kdistlib._DeviceSet(ctx, members) as dset:
+            yield group, ctx, dset.ptr, k
 
 
 def summaries(profiles):
@@ -586,18 +626,60 @@ def _fresh_batch(ctx, n_tables, bins):
     """A new batch of ``n_tables`` tables of ``bins`` entries on ``ctx``, or None when the budget of live device tables or the
     allocation itself says no: the caller then takes the per-profile route."""
     nbytes = 8 * bins * n_tables
-    if not _DEVICE_PROFILE_BYTES or _DeviceBatch.live_bytes + nbytes > _DEVICE_PROFILE_BYTES:
-        return None
     try:
-        return _DeviceBatch(ctx, nbytes, n_tables)
+        return _DeviceBatch(ctx, nbytes, n_tables) if _may_stay(nbytes) else None
     except MemoryError:
         return None
 
 
-def _repoint(profiles, group, batch, length):
-    for j, i in enumerate(group):
-        p = profiles[i]
-        p._counts, p._device, p.length = None, (batch, j, False), length
+def _batch_or_methods(ctx, n_tables, bins, method, *sides):
+    """``_fresh_batch`` for a group -- or, when there is none, None after the per-profile route has been taken for every
+    member: ``method(p)`` for the profiles of one side, ``method(p, o)`` for the pairs of two, with the counts of ``p``
+    downloaded first (a method whose profile is still in HBM would come back to the set functions)."""
+    batch = _fresh_batch(ctx, n_tables, bins)
+    if batch is None:
+        for each in zip(*sides):
+            each[0].counts
+            method(*each)
+    return batch
+
+
+def _repoint(targets, batch, length):
+    """Row j of ``batch`` becomes the table of ``targets[j]``, a profile of k-mer length ``length`` (None: that row is nobody's)."""
+    for j, p in enumerate(targets):
+        if p is not None:
+            p._counts, p._device, p.length = None, (batch, j, False), length
+
+
+def _hand_out(ctx, ptr, bins, targets, in_place):
+    """Downloads ``len(targets)`` tables of ``bins`` counts from ``ptr`` and hands row j to ``targets[j]`` (None: to nobody):
+    written into the array the profile holds (``in_place``), or as its new counts -- rows of one array, as the tables of a
+    downloaded batch are."""
+    tables = np.empty((len(targets), bins), dtype=np.int64)
+    ctx.d2h(tables, ptr)
+    for j, p in enumerate(targets):
+        if p is None:
+            continue
+        if in_place:
+            p.counts[...] = tables[j]
+        else:
+            p.counts = tables[j]
+
+
+@contextlib.contextmanager
+def _result_tables(ctx, batch, nbytes, sync=False):
+    """Where a set call writes ``nbytes`` of results: the rows of ``batch``, or without one an allocation that lives as long
+    as the ``with`` (``sync``: work queued on it is waited for before it goes)."""
+    if batch is not None:
+        yield batch.ptr
+        return
+    out = ctx.alloc(nbytes)
+    try:
+        yield out
+    finally:
+        if sync:
+            ctx.sync()
+        ctx.free(out)
 
 
 def _by_placement(profiles, usable=_set_counts):
@@ -619,20 +701,14 @@ def balance_profiles(profiles):
     for i in other:
         profiles[i].balance()
     for group, ctx, ptr, k in _device_sets(profiles, resident):
-        batch = _fresh_batch(ctx, len(group), 4 ** k)
-        if batch is None:
-            for i in group:
-                profiles[i].counts        # (downloaded: balance() takes the host route from here)
-                profiles[i].balance()
-            continue
-        ctx.balance_set_device(k, len(group), ptr, batch.ptr)
-        _repoint(profiles, group, batch, k)
+        members = [profiles[i] for i in group]
+        batch = _batch_or_methods(ctx, len(group), 4 ** k, lambda p: p.balance(), members)
+        if batch is not None:
+            ctx.balance_set_device(k, len(group), ptr, batch.ptr)
+            _repoint(members, batch, k)
     for group, ctx, ptr, k in _device_sets(profiles, host):
         ctx.balance_set_device(k, len(group), ptr, ptr)      # (host counts are gathered into an allocation of the group's own)
-        tables = np.empty((len(group), 4 ** k), dtype=np.int64)
-        ctx.d2h(tables, ptr)
-        for j, i in enumerate(group):
-            profiles[i].counts[...] = tables[j]
+        _hand_out(ctx, ptr, 4 ** k, [profiles[i] for i in group], in_place=True)
 
 
 def _shrink_arguments(length, factor):
@@ -659,25 +735,18 @@ def shrink_profiles(profiles, factor=1):
     for i in other:
         profiles[i].shrink(factor)
     for group, ctx, ptr, k in _device_sets(profiles, resident):
-        batch = _fresh_batch(ctx, len(group), 4 ** (k - factor))
-        if batch is None:
-            for i in group:
-                profiles[i].counts
-                profiles[i].shrink(factor)
-            continue
-        ctx.shrink_set_device(k, factor, len(group), ptr, batch.ptr)
-        _repoint(profiles, group, batch, k - factor)
+        members = [profiles[i] for i in group]
+        batch = _batch_or_methods(ctx, len(group), 4 ** (k - factor), lambda p: p.shrink(factor), members)
+        if batch is not None:
+            ctx.shrink_set_device(k, factor, len(group), ptr, batch.ptr)
+            _repoint(members, batch, k - factor)
     for group, ctx, ptr, k in _device_sets(profiles, host):
-        tables = np.empty((len(group), 4 ** (k - factor)), dtype=np.int64)
-        out = ctx.alloc(tables.nbytes)
-        try:
+        members = [profiles[i] for i in group]
+        with _result_tables(ctx, None, len(group) * 8 * 4 ** (k - factor)) as out:
             ctx.shrink_set_device(k, factor, len(group), ptr, out)
-            ctx.d2h(tables, out)
-        finally:
-            ctx.free(out)
-        for j, i in enumerate(group):
-            profiles[i].counts = tables[j]       # (rows of one array, as the tables of a downloaded batch are)
-            profiles[i].length = k - factor
+            _hand_out(ctx, out, 4 ** (k - factor), members, in_place=False)
+        for p in members:
+            p.length = k - factor
 
 
 def merge_profiles(profiles, others, merger=metrics.mergers['sum']):
@@ -695,47 +764,30 @@ def merge_profiles(profiles, others, merger=metrics.mergers['sum']):
         for p, o in zip(profiles, others):
             p.merge(o, merger)
         return
-    resident, host = {}, {}
+    resident, host = [], []
     for i, (p, o) in enumerate(zip(profiles, others)):
         if not (_set_counts(p) and _set_counts(o) and p.length == o.length):
             p.merge(o, merger)
-        elif p._device_counts() and o._device_counts():
-            resident.setdefault(p.length, []).append(i)
         else:
-            host.setdefault(p.length, []).append(i)
-    for in_hbm, by_length in ((True, resident), (False, host)):
-        for k, places in sorted(by_length.items()):
-            bins, per = 4 ** k, max(1, _RECORD_BATCH_BYTES // (8 * 4 ** k))
-            for at in range(0, len(places), per):
-                group = places[at:at + per]
-                left, right = [profiles[i] for i in group], [others[i] for i in group]
-                ctx = kdistlib._cross_context(left + right)
-                batch = _fresh_batch(ctx, len(group), bins) if in_hbm else None
-                if in_hbm and batch is None:
-                    for p, o in zip(left, right):
-                        p.counts
-                        p.merge(o, merger)
-                    continue
-                lset = kdistlib._DeviceSet(ctx, left)
-                try:
-                    rset = kdistlib._DeviceSet(ctx, right)
-                    try:
-                        if in_hbm:
-                            ctx.merge_device(len(group) * bins, lset.ptr, rset.ptr, code, batch.ptr)
-                            _repoint(profiles, group, batch, k)
-                        else:
-                            # one side at least was gathered into an allocation of the group's own: the result goes there
-                            out = lset.ptr if lset.owned is not None else rset.ptr
-                            assert lset.owned is not None or rset.owned is not None
-                            ctx.merge_device(len(group) * bins, lset.ptr, rset.ptr, code, out)
-                            tables = np.empty((len(group), bins), dtype=np.int64)
-                            ctx.d2h(tables, out)
-                            for j, i in enumerate(group):
-                                profiles[i].counts = tables[j]
-                    finally:
-                        rset.release()
-                finally:
-                    lset.release()
+            (resident if p._device_counts() and o._device_counts() else host).append(i)
+    for in_hbm, places in ((True, resident), (False, host)):
+        for k, group in _groups(places, lambda i: profiles[i].length):
+            bins = 4 ** k
+            left, right = [profiles[i] for i in group], [others[i] for i in group]
+            ctx = kdistlib._cross_context(left + right)
+            batch = _batch_or_methods(ctx, len(group), bins, lambda p, o: p.merge(o, merger), left, right) if in_hbm else None
+            if in_hbm and batch is None:
+                continue
+            with kdistlib._DeviceSet(ctx, left) as lset, kdistlib._DeviceSet(ctx, right) as rset:
+                if in_hbm:
+                    ctx.merge_device(len(group) * bins, lset.ptr, rset.ptr, code, batch.ptr)
+                    _repoint(left, batch, k)
+                else:
+                    # one side at least was gathered into an allocation of the group's own: the result goes there
+                    out = lset.ptr if lset.owned is not None else rset.ptr
+                    assert lset.owned is not None or rset.owned is not None
+                    ctx.merge_device(len(group) * bins, lset.ptr, rset.ptr, code, out)
+                    _hand_out(ctx, out, bins, left, in_place=False)
 
 
 def _smooth_counts(profile):
@@ -756,48 +808,30 @@ def smooth_profiles(profiles, others, dist):
         raise ValueError('smooth_profiles: %d profiles, %d partners' % (len(profiles), len(others)))
     _no_repeats(profiles + others, 'smooth_profiles')
     code = metrics.summary_code(dist._function)
-    by_length = {}
+    places = []
     for i, (p, o) in enumerate(zip(profiles, others)):
         if code is None or not kdistlib._is_number(dist._threshold) or not (_smooth_counts(p) and _smooth_counts(o) and p.length == o.length):
             dist.dynamic_smooth(p, o)
         else:
-            by_length.setdefault(p.length, []).append(i)
-    for k, places in sorted(by_length.items()):
-        bins, per = 4 ** k, max(1, _RECORD_BATCH_BYTES // (2 * 8 * 4 ** k))
-        for at in range(0, len(places), per):
-            group = places[at:at + per]
-            n = len(group)
-            both = [profiles[i] for i in group] + [others[i] for i in group]
-            resident = [j for j, p in enumerate(both) if p._device_counts()]
-            ctx = kdistlib._cross_context(both)
-            # the two smoothed sets, left first: rows of a new batch when a profile stays in HBM, else an allocation of the group's
-            batch = _fresh_batch(ctx, 2 * n, bins) if resident else None
-            if resident and batch is None:
-                for p, o in zip(both[:n], both[n:]):
-                    dist.dynamic_smooth(p, o)
-                continue
-            out = batch.ptr if batch is not None else ctx.alloc(2 * n * 8 * bins)
-            try:
-                lset = kdistlib._DeviceSet(ctx, both[:n])
-                try:
-                    rset = kdistlib._DeviceSet(ctx, both[n:])
-                    try:
-                        ctx.paired_smooth_device(k, n, lset.ptr, rset.ptr, code, dist._threshold, out, out + n * 8 * bins)
-                        if len(resident) < 2 * n:
-                            tables = np.empty((2 * n, bins), dtype=np.int64)
-                            ctx.d2h(tables, out)
-                            for j in sorted(set(range(2 * n)) - set(resident)):
-                                both[j]._counts[...] = tables[j]
-                    finally:
-                        rset.release()
-                finally:
-                    lset.release()
-            finally:
-                if batch is None:
-                    ctx.sync()
-                    ctx.free(out)
-            for j in resident:      # (_repoint's assignment; row j of the batch, whatever the profile's place among the resident ones)
-                both[j]._counts, both[j]._device = None, (batch, j, False)
+            places.append(i)
+    for k, group in _groups(places, lambda i: profiles[i].length, sides=2):
+        n, bins = len(group), 4 ** k
+        both = [profiles[i] for i in group] + [others[i] for i in group]
+        in_hbm = [p if p._device_counts() else None for p in both]
+        resident = 2 * n - in_hbm.count(None)
+        ctx = kdistlib._cross_context(both)
+        # the two smoothed sets, left first: rows of a new batch when a profile stays in HBM, else an allocation of the group's
+        batch = _fresh_batch(ctx, 2 * n, bins) if resident else None
+        if resident and batch is None:
+            for p, o in zip(both[:n], both[n:]):      # (dynamic_smooth downloads what it needs: no set function behind it)
+                dist.dynamic_smooth(p, o)
+            continue
+        with _result_tables(ctx, batch, 2 * n * 8 * bins, sync=True) as out, \
+                kdistlib._DeviceSet(ctx, both[:n]) as lset, kdistlib._DeviceSet(ctx, both[n:]) as rset:
+            ctx.paired_smooth_device(k, n, lset.ptr, rset.ptr, code, dist._threshold, out, out + n * 8 * bins)
+            if resident < 2 * n:
+                _hand_out(ctx, out, bins, [p if stays is None else None for p, stays in zip(both, in_hbm)], in_place=True)
+        _repoint(in_hbm, batch, k)      # (row j of the batch, whatever the profile's place among the resident ones)
 
 
 def pooled(profiles, name=None):
@@ -819,24 +853,17 @@ def pooled(profiles, name=None):
     bins = 4 ** k
     ctx = kdistlib._cross_context(profiles)
     batch = _fresh_batch(ctx, 1, bins) if all(p._device_counts() for p in profiles) else None
-    out = batch.ptr if batch is not None else ctx.alloc(8 * bins)
-    try:
-        per = max(1, _RECORD_BATCH_BYTES // (8 * bins))
+    with _result_tables(ctx, batch, 8 * bins) as out:
+        per = _tables_per_group(k)
         for at in range(0, len(profiles), per):
             members = profiles[at:at + per]
-            dset = kdistlib._DeviceSet(ctx, members)
-            try:
+            with kdistlib._DeviceSet(ctx, members) as dset:
                 ctx.pool_set_device(len(members), bins, dset.ptr, out, accumulate=at > 0)
-            finally:
-                dset.release()
         if batch is not None:
             return Profile._from_device(batch, 0, k, name)
         total = np.empty(bins, dtype=np.int64)
         ctx.d2h(total, out)
         return Profile(total, name=name)
-    finally:
-        if batch is None:
-            ctx.free(out)
 
 
 class Profile(object):
@@ -924,9 +951,7 @@ class Profile(object):
         The text is handed to the GPU in chunks of whole records; header removal, line joining
         and record separation happen on the device (``kpal_count_feed_fasta``), so there is no
         per-character or per-line Python work."""
-        length = int(length)
-        if length < 1 or length > _native.KPAL_MAX_K:
-            raise ValueError('k-mer length must be in 1..%d (got %d)' % (_native.KPAL_MAX_K, length))
+        length = _kmer_length(length)
         ctx = _native.context()
         ctx.count_begin(length)
         plain = _plain_file(handle)
@@ -936,13 +961,7 @@ class Profile(object):
             ctx.count_feed_fasta_file(plain[0], plain[1], 0)
             handle.seek(0, os.SEEK_END)      # the handle has been consumed, as by the reference's SeqIO.parse loop
             return cls._finish_count(ctx, length, name)
-        reader = handle
-        if isinstance(handle, io.TextIOWrapper):
-            try:                              # a pipe or a decompressing wrapper in an ASCII-compatible text encoding: its bytes, undecoded
-                if codecs.lookup(handle.encoding or '').name in ('utf-8', 'ascii', 'iso8859-1') and handle.tell() == 0:
-                    reader = handle.buffer
-            except (LookupError, OSError, ValueError):
-                reader = handle
+        reader, _ = _byte_reader(handle)      # (a pipe or a decompressing wrapper under a text handle: its bytes, undecoded)
         carry = b''   # the unfinished last record of the previous chunk (small)
         while True:
             text = reader.read(_FASTA_CHUNK)
@@ -981,10 +1000,7 @@ class Profile(object):
         64) is below it is masked: it breaks k-mer windows like any byte outside ``ACGT``.  Tokenising, validation and masking
         run on the device (``kpal_count_feed_fastq``); Python does not look for record boundaries.  A malformed record raises
         ``ValueError`` naming its 1-based number, and no profile is returned."""
-        length = int(length)
-        if length < 1 or length > _native.KPAL_MAX_K:
-            raise ValueError('k-mer length must be in 1..%d (got %d)' % (_native.KPAL_MAX_K, length))
-        _native.fastq_options_check(min_quality, quality_offset)
+        length = _read_arguments(length, min_quality, quality_offset)
         ctx = _native.context()
         ctx.count_begin(length)
         plain = _plain_file(handle)
@@ -1013,23 +1029,7 @@ class Profile(object):
         ``_RECORD_BATCH_BYTES`` of tables).  The host reads the HEADER lines only, for the names; there is no per-line or
         per-character Python work.  A k whose table alone exceeds that budget falls back to ``from_sequences`` per
         record."""
-        length = int(length)
-        if length < 1 or length > _native.KPAL_MAX_K:
-            raise ValueError('k-mer length must be in 1..%d (got %d)' % (_native.KPAL_MAX_K, length))
-        prefix = prefix + '_' if prefix else ''
-        table_bytes = 8 * 4 ** length
-        per_batch = _RECORD_BATCH_BYTES // table_bytes
-        if per_batch < 2:
-            for i, (record_name, seq) in enumerate(_fasta_records(handle)):
-                yield cls.from_sequences([seq], length, name=prefix + (record_name or str(i + 1)))
-            return
-        ctx = _native.context()
-        for names, _, indexed in _indexed_pieces(ctx, handle, prefix, 'from_fasta_by_record'):
-            for first in range(0, len(names), per_batch):
-                indexed()
-                n = min(per_batch, len(names) - first)
-                for profile in cls._record_batch(ctx, length, first, n, names):
-                    yield profile
+        yield from cls._by_record(handle, _kmer_length(length), prefix, 'from_fasta_by_record')
 
     @classmethod
     def from_fasta_by_window(cls, handle, length, window, step=None, prefix=None):
@@ -1047,17 +1047,7 @@ class Profile(object):
         tokenised and counted once, whatever ``window / step`` is, and the tables stay in HBM under the same budgets.  A k
         whose table alone exceeds the batch budget falls back to ``from_sequences`` per window."""
         length, window, step = _window_arguments(length, window, step)
-        prefix = prefix + '_' if prefix else ''
-        table_bytes = 8 * 4 ** length
-        per_batch = _RECORD_BATCH_BYTES // table_bytes
-        if per_batch < 2:
-            for i, (record_name, seq) in enumerate(_fasta_records(handle)):
-                for profile in cls._windows_one_by_one(seq, prefix + (record_name or str(i + 1)), length, window, step):
-                    yield profile
-            return
-        ctx = _native.context()
-        for profile in cls._indexed_windows(ctx, handle, length, window, step, prefix, per_batch, 'from_fasta_by_window'):
-            yield profile
+        yield from cls._by_window(handle, length, window, step, prefix, 'from_fasta_by_window')
 
     @classmethod
     def from_fastq_by_record(cls, handle, length, prefix=None, min_quality=None, quality_offset=33):
@@ -1075,20 +1065,7 @@ class Profile(object):
         own, which the end of the handle ends).  A k whose table alone exceeds the batch budget falls back to
         ``from_sequences`` per read, on the reads as the device masks them."""
         length = _read_arguments(length, min_quality, quality_offset)
-        prefix = prefix + '_' if prefix else ''
-        table_bytes = 8 * 4 ** length
-        per_batch = _RECORD_BATCH_BYTES // table_bytes
-        ctx = _native.context()
-        if per_batch < 2:
-            for read_name, read in _fastq_reads(ctx, handle, prefix, min_quality, quality_offset):
-                yield cls.from_sequences([read], length, name=read_name)
-            return
-        for names, _, indexed in _indexed_pieces(ctx, handle, prefix, 'from_fastq_by_record', (min_quality, quality_offset)):
-            for first in range(0, len(names), per_batch):
-                indexed()
-                n = min(per_batch, len(names) - first)
-                for profile in cls._record_batch(ctx, length, first, n, names):
-                    yield profile
+        yield from cls._by_record(handle, length, prefix, 'from_fastq_by_record', (min_quality, quality_offset))
 
     @classmethod
     def from_fastq_by_window(cls, handle, length, window, step=None, prefix=None, min_quality=None, quality_offset=33):
@@ -1098,29 +1075,42 @@ class Profile(object):
         k-mers.  Indexing, batching, residency and errors are those of ``from_fastq_by_record``."""
         length, window, step = _window_arguments(length, window, step)
         _read_arguments(length, min_quality, quality_offset)
+        yield from cls._by_window(handle, length, window, step, prefix, 'from_fastq_by_window', (min_quality, quality_offset))
+
+    @classmethod
+    def _by_record(cls, handle, length, prefix, who, fastq=None):
+        """One profile per record of a FASTA handle -- with ``fastq = (min_quality, quality_offset)``, per read of a FASTQ
+        handle: the records indexed on the device (``_indexed_pieces``) and counted in batches of ``_tables_per_group``
+        tables, or, when fewer than two tables make a batch, one by one."""
         prefix = prefix + '_' if prefix else ''
-        table_bytes = 8 * 4 ** length
-        per_batch = _RECORD_BATCH_BYTES // table_bytes
-        ctx = _native.context()
+        per_batch = _tables_per_group(length)
         if per_batch < 2:
-            for read_name, read in _fastq_reads(ctx, handle, prefix, min_quality, quality_offset):
-                for profile in cls._windows_one_by_one(read, read_name, length, window, step):
-                    yield profile
+            for name, seq in _named_sequences(handle, prefix, fastq):
+                yield cls.from_sequences([seq], length, name=name)
             return
-        for profile in cls._indexed_windows(ctx, handle, length, window, step, prefix, per_batch, 'from_fastq_by_window',
-                                            (min_quality, quality_offset)):
-            yield profile
+        ctx = _native.context()
+        for names, _, indexed in _indexed_pieces(ctx, handle, prefix, who, fastq):
+            for first in range(0, len(names), per_batch):
+                indexed()
+                n = min(per_batch, len(names) - first)
+                for profile in cls._counted_batch(ctx, length, n, names[first:first + n],
+                                                  lambda ptr: ctx.fasta_records_count_device(length, first, n, ptr),
+                                                  lambda: ctx.fasta_records_count(length, first, n)):
+                    yield profile
 
     @classmethod
-    def _windows_one_by_one(cls, seq, record_name, length, window, step):
-        """The window profiles of one record by ``from_sequences`` (a k whose table alone exceeds the batch budget)."""
-        for start in range(0, _window_count(len(seq), window, step) * step, step):
-            end = min(start + window, len(seq))
-            yield cls.from_sequences([seq[start:end]], length, name='%s:%d-%d' % (record_name, start + 1, end))
-
-    @classmethod
-    def _indexed_windows(cls, ctx, handle, length, window, step, prefix, per_batch, who, fastq=None):
-        """The window profiles of every record of a handle, its records indexed on the device (``_indexed_pieces``)."""
+    def _by_window(cls, handle, length, window, step, prefix, who, fastq=None):
+        """One profile per sliding window of every record (``fastq``: of every read) of a handle, batched or one by one as
+        ``_by_record`` does."""
+        prefix = prefix + '_' if prefix else ''
+        per_batch = _tables_per_group(length)
+        if per_batch < 2:
+            for name, seq in _named_sequences(handle, prefix, fastq):
+                for start in range(0, _window_count(len(seq), window, step) * step, step):
+                    end = min(start + window, len(seq))
+                    yield cls.from_sequences([seq[start:end]], length, name='%s:%d-%d' % (name, start + 1, end))
+            return
+        ctx = _native.context()
         for names, bases, indexed in _indexed_pieces(ctx, handle, prefix, who, fastq):
             n_windows, first_window = ctx.fasta_windows_layout(window, step)
             for first in range(0, n_windows, per_batch):
@@ -1132,7 +1122,9 @@ class Profile(object):
                 starts = (numbers - first_window[records]) * np.uint64(step)
                 ends = np.minimum(starts + np.uint64(window), bases[records])
                 window_names = ['%s:%d-%d' % (names[r], a + 1, b) for r, a, b in zip(records.tolist(), starts.tolist(), ends.tolist())]
-                for profile in cls._window_batch(ctx, length, window, step, first, n, window_names):
+                for profile in cls._counted_batch(ctx, length, n, window_names,
+                                                  lambda ptr: ctx.fasta_windows_count_device(length, window, step, first, n, ptr),
+                                                  lambda: ctx.fasta_windows_count(length, window, step, first, n)):
                     yield profile
 
     @classmethod
@@ -1142,7 +1134,7 @@ class Profile(object):
         (`kpal count` saving it: the one download it always was; a distance between two freshly counted profiles: none at all);
         past the budget of live device tables it is downloaded at once."""
         nbytes = 8 * 4 ** length
-        if _DEVICE_PROFILE_BYTES and _DeviceBatch.live_bytes + nbytes <= _DEVICE_PROFILE_BYTES:
+        if _may_stay(nbytes):
             ctx.count_finish(to_host=False)
             table, _ = ctx.count_table()
             batch = _DeviceBatch(ctx, nbytes, 1)
@@ -1152,27 +1144,16 @@ class Profile(object):
         return cls(ctx.count_finish(), name=name)
 
     @classmethod
-    def _record_batch(cls, ctx, length, first, n, names):
-        """The profiles of records [first, first + n) of the text the context has indexed.  Their tables stay in HBM (one
-        allocation per batch) while the budget of live device tables allows; else they are downloaded at once."""
+    def _counted_batch(cls, ctx, length, n, names, count_device, count_host):
+        """The ``n`` profiles ``names`` of one batch of records or windows of the text the context has indexed.  Their tables
+        stay in HBM (one allocation per batch, filled by ``count_device(address)``) while the budget of live device tables
+        allows; else they are downloaded at once (``count_host()``: the n tables)."""
         nbytes = n * 8 * 4 ** length
-        if _DEVICE_PROFILE_BYTES and _DeviceBatch.live_bytes + nbytes <= _DEVICE_PROFILE_BYTES:
+        if _may_stay(nbytes):
             batch = _DeviceBatch(ctx, nbytes, n)
-            ctx.fasta_records_count_device(length, first, n, batch.ptr)
-            return [cls._from_device(batch, j, length, names[first + j]) for j in range(n)]
-        tables = ctx.fasta_records_count(length, first, n)
-        return [cls(tables[j], name=names[first + j]) for j in range(n)]
-
-    @classmethod
-    def _window_batch(cls, ctx, length, window, step, first, n, names):
-        """The profiles of windows [first, first + n) of the records the context has indexed (``names``: theirs), kept in
-        HBM or downloaded at once as ``_record_batch`` does."""
-        nbytes = n * 8 * 4 ** length
-        if _DEVICE_PROFILE_BYTES and _DeviceBatch.live_bytes + nbytes <= _DEVICE_PROFILE_BYTES:
-            batch = _DeviceBatch(ctx, nbytes, n)
-            ctx.fasta_windows_count_device(length, window, step, first, n, batch.ptr)
+            count_device(batch.ptr)
             return [cls._from_device(batch, j, length, names[j]) for j in range(n)]
-        tables = ctx.fasta_windows_count(length, window, step, first, n)
+        tables = count_host()
         return [cls(tables[j], name=names[j]) for j in range(n)]
 
     @classmethod
@@ -1181,9 +1162,7 @@ class Profile(object):
 
         Windows never span two sequences or a character outside ``AaCcGgTt``.
         """
-        length = int(length)
-        if length < 1 or length > _native.KPAL_MAX_K:
-            raise ValueError('k-mer length must be in 1..%d (got %d)' % (_native.KPAL_MAX_K, length))
+        length = _kmer_length(length)
         ctx = _native.context()
         ctx.count_begin(length)
         if _kpal_gather is not None:

@@ -241,18 +241,55 @@ def get_count(input_handle, output_handle, word, names=None):
         print(name, str(profile.counts[offset]), file=output_handle)
 
 
+class _LengthMismatch(ValueError):
+    """LENGTH_ERROR for a linked pair: the one error of ``_paired`` behind which the earlier pairs are still written."""
+
+
 def _paired(input_handle_left, input_handle_right, names_left, names_right):
-    """The (left, right) profile pairs of the two-file commands, linked by position in the name lists."""
+    """The (left, right) profile pairs of the two-file commands, linked by position in the name lists.  Unequal numbers of
+    names raise here, at the call -- before a caller evaluates a custom function, like the reference; the pairs are read as
+    the generator that is returned goes."""
     names_left = _profile_names(input_handle_left, names_left)
     names_right = _profile_names(input_handle_right, names_right)
     if len(names_left) != len(names_right):
         raise ValueError(PAIRED_NAMES_COUNT_ERROR)
-    for name_left, name_right in zip(names_left, names_right):
-        left = klib.Profile.from_file(input_handle_left, name=name_left)
-        right = klib.Profile.from_file(input_handle_right, name=name_right)
-        if left.length != right.length:
-            raise ValueError(LENGTH_ERROR)
-        yield left, right
+
+    def pairs():
+        for name_left, name_right in zip(names_left, names_right):
+            left = klib.Profile.from_file(input_handle_left, name=name_left)
+            right = klib.Profile.from_file(input_handle_right, name=name_right)
+            if left.length != right.length:
+                raise _LengthMismatch(LENGTH_ERROR)
+            yield left, right
+
+    return pairs()
+
+
+def _paired_groups(input_handle_left, input_handle_right, names_left, names_right):
+    """The pairs of ``_paired`` as ``(lefts, rights)`` lists of at most ``klib._RECORD_BATCH_BYTES`` of counts over both sides
+    (never less than one pair), sized as ``_profile_groups`` sizes its groups: what the set functions of linked pairs take at
+    a time.  A pair of two k-mer lengths ends the groups with LENGTH_ERROR AFTER the pairs before it have been handed out, so
+    that they are written as the pair-by-pair loop wrote them; any other error is raised at once."""
+    pairs = _paired(input_handle_left, input_handle_right, names_left, names_right)
+
+    def groups():
+        lefts, rights, size, mismatch = [], [], 0, None
+        try:
+            for left, right in pairs:
+                lefts.append(left)
+                rights.append(right)
+                size += np.asanyarray(left.counts).nbytes + np.asanyarray(right.counts).nbytes
+                if size >= klib._RECORD_BATCH_BYTES:
+                    yield lefts, rights
+                    lefts, rights, size = [], [], 0
+        except _LengthMismatch as error:
+            mismatch = error
+        if lefts:
+            yield lefts, rights
+        if mismatch is not None:
+            raise mismatch
+
+    return groups()
 
 
 def positive(input_handle_left, input_handle_right, output_handle_left, output_handle_right, names_left=None,
@@ -311,34 +348,14 @@ def smooth(input_handle_left, input_handle_right, output_handle_left, output_han
 
     (kpal/kmer.py:486-538.)  Both files are read in groups of at most ``klib._RECORD_BATCH_BYTES`` of counts over both sides; a
     group is smoothed by one set call on the device (``klib.smooth_profiles``)."""
-    names_left = _profile_names(input_handle_left, names_left)
-    names_right = _profile_names(input_handle_right, names_right)
-    if len(names_left) != len(names_right):      # before the custom function is evaluated, like the reference
-        raise ValueError(PAIRED_NAMES_COUNT_ERROR)
+    groups = _paired_groups(input_handle_left, input_handle_right, names_left, names_right)
     function = _custom_function(custom_summary, 'values') if custom_summary else metrics.summary[summary]
     dist = kdistlib.ProfileDistance(summary=function, threshold=threshold)
-    lefts, rights, size = [], [], 0
-
-    def flush():
+    for lefts, rights in groups:
         klib.smooth_profiles(lefts, rights, dist)
         for left, right in zip(lefts, rights):
             left.save(output_handle_left)
             right.save(output_handle_right)
-        del lefts[:], rights[:]
-
-    for name_left, name_right in zip(names_left, names_right):
-        left = klib.Profile.from_file(input_handle_left, name=name_left)
-        right = klib.Profile.from_file(input_handle_right, name=name_right)
-        if left.length != right.length:
-            flush()      # the earlier pairs are written before the error, as the pair-by-pair loop wrote them
-            raise ValueError(LENGTH_ERROR)
-        lefts.append(left)
-        rights.append(right)
-        size += np.asanyarray(left.counts).nbytes + np.asanyarray(right.counts).nbytes
-        if size >= klib._RECORD_BATCH_BYTES:
-            flush()
-            size = 0
-    flush()
 
 
 def _profile_distance(distance_function, pairwise, custom_pairwise, do_smooth, summary, custom_summary, threshold,
@@ -359,34 +376,13 @@ def distance(input_handle_left, input_handle_right, output_handle, names_left=No
     """``left right distance`` lines for the profiles of two files, linked pairwise
     (kpal/kmer.py:541-620).  Both files are read in groups of at most ``klib._RECORD_BATCH_BYTES`` of counts over both sides;
     a group's distances come from one set call on the device."""
-    names_left = _profile_names(input_handle_left, names_left)
-    names_right = _profile_names(input_handle_right, names_right)
-    if len(names_left) != len(names_right):
-        raise ValueError(PAIRED_NAMES_COUNT_ERROR)
+    groups = _paired_groups(input_handle_left, input_handle_right, names_left, names_right)
     dist = _profile_distance(distance_function, pairwise, custom_pairwise, do_smooth, summary, custom_summary,
                              threshold, do_scale, down, do_positive, do_balance)
-    names, lefts, rights, size = [], [], [], 0
-
-    def flush():
+    for lefts, rights in groups:
         # a group of pairs is one set call (kdistlib.paired_distances); the lines are those of the loop over dist.distance
-        for pair, value in zip(names, kdistlib.paired_distances(lefts, rights, dist)):
-            print(pair[0], pair[1], _fixed(precision, value), file=output_handle)
-        del names[:], lefts[:], rights[:]
-
-    for name_left, name_right in zip(names_left, names_right):
-        left = klib.Profile.from_file(input_handle_left, name=name_left)
-        right = klib.Profile.from_file(input_handle_right, name=name_right)
-        if left.length != right.length:
-            flush()      # the lines of all earlier pairs are written before the error, as the pair-by-pair loop wrote them
-            raise ValueError(LENGTH_ERROR)
-        names.append((name_left, name_right))
-        lefts.append(left)
-        rights.append(right)
-        size += np.asanyarray(left.counts).nbytes + np.asanyarray(right.counts).nbytes
-        if size >= klib._RECORD_BATCH_BYTES:
-            flush()
-            size = 0
-    flush()
+        for left, right, value in zip(lefts, rights, kdistlib.paired_distances(lefts, rights, dist)):
+            print(left.name, right.name, _fixed(precision, value), file=output_handle)
 
 
 def distance_matrix(input_handle, output_handle, names=None, distance_function='default', pairwise='prod',
