@@ -568,6 +568,17 @@ int kpal_shrink_set_device(kpal_ctx *ctx, int k, int factor, size_t n_tables, co
  * has `bins` entries and must not overlap the tables. */
 int kpal_pool_set_device(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *dev_tables /* n_tables x bins */,
                          int accumulate, int64_t *dev_out /* bins */);
+/* The pool BY LABEL: out[g][j] = (accumulate ? out[g][j] : 0) + the sum over the tables t with labels[t] == g of tables[t][j],
+ * int64 wrap.  `labels` is a HOST array: a label in [0, n_groups) names the group of a table, a negative one no group, a label
+ * >= n_groups is KPAL_E_INVALID.  The host inverts the labels into one member list per group and cuts long lists into chunks
+ * (pool_groups_plan.hpp); that index goes up in one copy, which the call waits for.  Then every table is read once, where it
+ * lies: ONE launch ("pool_groups") when no list is cut, exactly TWO otherwise ("pool_groups", whose partial rows go to the
+ * context's scratch, and "pool_groups_final"), whatever n_tables and n_groups are.  A group without a table becomes zeros, or
+ * with accumulate != 0 keeps what it holds.  dev_out has n_groups x bins entries and must not overlap the tables; the other
+ * refusals are those of kpal_pool_set_device, and n_groups == 0. */
+int kpal_pool_groups_device(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *dev_tables /* n_tables x bins */,
+                            const int64_t *labels /* HOST, n_tables */, size_t n_groups, int accumulate,
+                            int64_t *dev_out /* n_groups x bins */);
 
 /* ---- per-kernel timing with HIP events on the ctx stream (bench.py roofline leg) ---- */
 int kpal_prof_enable(kpal_ctx *ctx, int on);

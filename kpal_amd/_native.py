@@ -178,6 +178,7 @@ SIGNATURES = {
     'kpal_balance_set_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_size_t, _vp, _vp]),
     'kpal_shrink_set_device': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, _vp, _vp]),
     'kpal_pool_set_device': (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_int, _vp]),
+    'kpal_pool_groups_device': (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
     'kpal_prof_enable': (ctypes.c_int, [_vp, ctypes.c_int]),
     'kpal_prof_reset': (ctypes.c_int, [_vp]),
     'kpal_prof_count': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
@@ -1008,6 +1009,21 @@ class Context(object):
         """dev_out[j] (+)= the sum of n_tables consecutive int64 vectors of ``bins`` entries at dev_tables (int64 wrap), at most
         two launches; queued."""
         _check(self._L.kpal_pool_set_device(self._h, int(n_tables), int(bins), _vp(dev_tables), int(bool(accumulate)), _vp(dev_out)))
+
+    def pool_groups_device(self, n_tables, bins, dev_tables, labels, n_groups, dev_out, accumulate=False):
+        """dev_out[g][j] (+)= the sum of those of the n_tables consecutive int64 vectors of ``bins`` entries at dev_tables whose
+        label (``labels``: n_tables host integers; negative: no group) is g, for the ``n_groups`` rows of dev_out (int64 wrap):
+        one launch, or two when a long list is cut; queued."""
+        at = None
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.int64)
+            if labels.ndim != 1 or labels.size < int(n_tables):
+                raise ValueError('%d labels for %d tables' % (labels.size, int(n_tables)))
+            if not labels.size:
+                labels = np.zeros(1, dtype=np.int64)     # (no labels: still an address)
+            at = labels.ctypes.data
+        _check(self._L.kpal_pool_groups_device(self._h, int(n_tables), int(bins), _vp(dev_tables), _vp(at), int(n_groups), int(bool(accumulate)),
+                                               _vp(dev_out)))
 
     def profile_distance_matrix(self, profiles, k, options):
         arrs = [_as_i64(p) for p in profiles]

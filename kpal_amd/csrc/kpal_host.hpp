@@ -6,7 +6,8 @@
 // split, summaries, merge, shrink; kpal_sets.hip: the summaries and the strand balance of a whole set of vectors, planned by
 // stat_plan.hpp, and the strand balance of one vector, which is a set of one; kpal_spectrum.hip: the count-of-counts spectrum of
 // every vector of a set, planned by spectrum_plan.hpp; kpal_transform.hip: the balance, the shrink and the pool of a whole set of
-// vectors, planned by transform_plan.hpp; kpal_multi.hip: multi-GPU entry points over RCCL.  The five units that serve distances
+// vectors, planned by transform_plan.hpp; kpal_pool_groups.hip: the pool of a set by label, planned by pool_groups_plan.hpp;
+// kpal_multi.hip: multi-GPU entry points over RCCL.  The five units that serve distances
 // share dist_host.hpp on top of this header -- kpal_pair.hip: the distance of one pair, plain and with options; kpal_cross.hip:
 // the distances of sets of profiles, triangle and rectangle, plain, with options and with dynamic smoothing, planned by
 // matrix_plan.hpp and smooth_plan.hpp; kpal_paired.hip: the distances of the linked pairs of two sets, planned by

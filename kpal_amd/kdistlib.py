@@ -18,7 +18,8 @@ every left profile without that rectangle on the host (``kpal_cross_nearest_devi
 selected on the device), the left side streamed.  :func:`paired_distances` / :func:`successive_distances` -- the distances of the
 LINKED pairs of two sets, ``left[i]`` against ``right[i]``, or of one set against itself ``lag`` profiles on
 (``kpal_paired_distance_device``, with dynamic smoothing ``kpal_paired_smooth_distance_device``: a number of launches that
-does not grow with the number of pairs).
+does not grow with the number of pairs).  :func:`pooled_nearest` -- every left profile assigned to its nearest right profile and
+the left profiles pooled bin by bin (``kpal_pool_groups_device`` on the tables the selection ran on), the left side streamed.
 """
 import contextlib
 
@@ -479,7 +480,9 @@ def nearest_chunks(left_profiles, right_profiles, dist, n, max_bytes=None):
     return _nearest_chunks(left_profiles, right_profiles, dist, n, CROSS_MAX_BYTES if max_bytes is None else max_bytes)
 
 
-def _nearest_chunks(left_profiles, right, dist, n, max_bytes):
+def _nearest_chunks(left_profiles, right, dist, n, max_bytes, hand_on=False):
+    """``hand_on``: yields ``(chunk, indices, distances, left set)`` instead, while the chunk's ``_DeviceSet`` is still
+    resident (None where the chunk took no fast route): :func:`pooled_nearest` pools the tables it was made for."""
     R = len(right)
     m = min(n, R)
     options = dist._native_options() if n <= _native.NEAREST_MAX else None
@@ -512,7 +515,10 @@ def _nearest_chunks(left_profiles, right, dist, n, max_bytes):
                         values = np.array([[dist.distance(l, r) for r in block] for l in chunk], dtype=np.float64)
                         have = _merge_nearest(distances, indices, have, values.reshape(rows, stop - start), start, m)
                     block = None
-            yield chunk, indices, distances
+                if hand_on:
+                    yield chunk, indices, distances, lset
+            if not hand_on:
+                yield chunk, indices, distances
             chunk = lset = None
 
 
@@ -527,6 +533,79 @@ def nearest_profiles(left_profiles, right_profiles, dist, n, max_bytes=None):
         indices.append(i)
         distances.append(d)
     return np.concatenate(indices, axis=0), np.concatenate(distances, axis=0)
+
+
+def pooled_nearest(left_profiles, right_profiles, dist, max_bytes=None):
+    """Assigns every left profile to its nearest right profile and pools the left profiles bin by bin: ``(indices, distances,
+    pools)`` -- column 0 of :func:`nearest_profiles` ``(..., 1)`` as an int64 and a float64 array of shape ``(Q,)``, and a list
+    of R entries: ``pools[r]`` is the pooled profile (``klib.pooled``) of the left profiles whose nearest is
+    ``right_profiles[r]``, named after it, or None where none fell.  A left profile whose nearest distance is NaN is in no bin.
+
+    ``left_profiles`` is read a chunk at a time exactly as in :func:`nearest_chunks`, and a chunk's tables are made resident
+    ONCE for both steps: the set the selection ran on is pooled by label where it lies (``kpal_pool_groups_device``, one call
+    per chunk, accumulated into R rows on the device).  The chunk is not referenced once the next one is asked for: over
+    ``Profile.from_fastq_by_record`` the batches of reads are freed as the scan goes and R tables are kept.  When every chunk
+    was in HBM, so are the pools, as rows of one new batch.  Where the fast route of :func:`nearest_chunks` does not apply --
+    a user callable, non-integer counts -- the assignment follows its fallbacks and the pooling ``klib.pooled_by``; left
+    profiles of different k-mer lengths are a ``ValueError``."""
+    from . import klib
+    if not (hasattr(right_profiles, '__len__') and hasattr(right_profiles, '__getitem__')):
+        right_profiles = list(right_profiles)
+    R = len(right_profiles)
+    if R < 1:
+        raise ValueError('pooled_nearest needs at least one right profile')
+    max_bytes = CROSS_MAX_BYTES if max_bytes is None else max_bytes
+    indices, distances = [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.float64)]
+    k = ctx = batch = rows = None      # rows: the R pooled tables on the device (those of `batch`, or an allocation of the call's)
+    on_device, started = np.zeros(R, dtype=bool), False
+    on_host = {}
+    try:
+        for chunk, index, value, lset in _nearest_chunks(left_profiles, right_profiles, dist, 1, max_bytes, hand_on=True):
+            index, value = index[:, 0], value[:, 0]
+            indices.append(index)
+            distances.append(value)
+            if k is None:
+                k = chunk[0].length
+            if any(p.length != k for p in chunk):
+                raise ValueError('pooled_nearest: profiles of different k-mer lengths')
+            labels = np.where(np.isnan(value), -1, index).astype(np.int64)
+            if lset is None:
+                keys, sums = klib.pooled_by(chunk, [None if r < 0 else r for r in labels.tolist()])
+                for r, p in zip(keys, sums):
+                    on_host[r] = p.counts if r not in on_host else metrics.mergers['sum'](on_host[r], p.counts)
+                continue
+            bins = 4 ** k
+            if rows is None:
+                ctx = lset.ctx
+                if all(_device_table(p) is not None for p in chunk):
+                    batch = klib._fresh_batch(ctx, R, bins)
+                rows = batch.ptr if batch is not None else ctx.alloc(R * 8 * bins)
+            ctx.pool_groups_device(len(chunk), bins, lset.ptr, labels, R, rows, accumulate=started)    # (the first call zeroes every row)
+            started = True
+            on_device |= np.bincount(labels[labels >= 0], minlength=R) > 0
+            chunk = lset = None
+        pools = [None] * R
+        names = {}
+        for r in set(np.flatnonzero(on_device).tolist()) | set(on_host):
+            names[r] = right_profiles[r].name
+        if rows is not None and batch is not None and not on_host:
+            for r in names:
+                pools[r] = klib.Profile._from_device(batch, r, k, names[r])
+        else:
+            tables = None
+            if rows is not None:
+                tables = np.empty((R, 4 ** k), dtype=np.int64)
+                ctx.d2h(tables, rows)
+            for r in names:
+                total = tables[r] if on_device[r] else None
+                if r in on_host:
+                    total = on_host[r] if total is None else metrics.mergers['sum'](total, on_host[r])
+                pools[r] = klib.Profile(total, name=names[r])
+    finally:
+        if rows is not None and batch is None:
+            ctx.sync()
+            ctx.free(rows)
+    return np.concatenate(indices), np.concatenate(distances), pools
 
 
 def cross_distance_matrix(left_profiles, right_profiles, output, precision, dist, max_bytes=None):

@@ -17,7 +17,7 @@ Same constructor, classmethods, methods, properties and error behaviour as the r
 * A freshly counted table stays in HBM (``_DeviceBatch``) until something asks for ``counts``, within a budget of live bytes.
 * Beyond the reference: one profile per record, per read and per sliding window (``from_fasta_by_record`` ...), and the
   operations over whole SETS of profiles -- ``summaries``, ``strand_balances``, ``distributions``, ``balance_profiles``,
-  ``shrink_profiles``, ``merge_profiles``, ``smooth_profiles``, ``pooled`` -- in launches that do not grow with the set.  They
+  ``shrink_profiles``, ``merge_profiles``, ``smooth_profiles``, ``pooled``, ``pooled_by`` -- in launches that do not grow with the set.  They
   share one core: ``_may_stay`` (the residency budget), ``_groups`` (places by k-mer length in groups of bounded bytes) and
   ``kdistlib._DeviceSet`` (profiles as consecutive device tables, where they lie or gathered).
 
@@ -864,6 +864,64 @@ def pooled(profiles, name=None):
         total = np.empty(bins, dtype=np.int64)
         ctx.d2h(total, out)
         return Profile(total, name=name)
+
+
+def _label_codes(labels):
+    """The distinct ``labels`` in order of first appearance (None: no label) and, per place, the position of its label among
+    them as an int64 array (-1: none)."""
+    keys, where = [], {}
+    codes = np.full(len(labels), -1, dtype=np.int64)
+    for i, label in enumerate(labels):
+        if label is None:
+            continue
+        if label not in where:
+            where[label] = len(keys)
+            keys.append(label)
+        codes[i] = where[label]
+    return keys, codes
+
+
+def pooled_by(profiles, labels):
+    """``(keys, pooled)``: the distinct ``labels`` (any hashables; None: the profile is in no group) in order of first
+    appearance, and for ``keys[i]`` a new profile named ``str(keys[i])`` whose counts are those of ``pooled([p for p, l in
+    zip(profiles, labels) if l == keys[i]])``, bit for bit -- the reads that fell to each member of a panel, the contigs of a
+    bin, the windows of a record.  Integer profiles are summed as SETS by label (``kpal_pool_groups_device``: every table read
+    once where it lies, one or two launches per group of at most ``_RECORD_BATCH_BYTES`` of tables, whatever the number of
+    labels).  When every profile is still in HBM, so are the results, as the rows of one new batch.  When any profile is not
+    integer counts the sums are those of the sum merger, label by label.  Lists of unequal length, an empty list and mixed
+    k-mer lengths are a ``ValueError``; when every label is None the result is ``([], [])``."""
+    profiles, labels = list(profiles), list(labels)
+    if len(profiles) != len(labels):
+        raise ValueError('pooled_by: %d profiles, %d labels' % (len(profiles), len(labels)))
+    if not profiles:
+        raise ValueError('pooled_by: no profiles')
+    k = profiles[0].length
+    if any(p.length != k for p in profiles):
+        raise ValueError('pooled_by: profiles of different k-mer lengths')
+    keys, codes = _label_codes(labels)
+    if not keys:
+        return [], []
+    names = [str(key) for key in keys]
+    if not all(_set_counts(p) for p in profiles):
+        totals = [None] * len(keys)
+        for p, g in zip(profiles, codes.tolist()):
+            if g >= 0:
+                totals[g] = np.array(p.counts) if totals[g] is None else metrics.mergers['sum'](totals[g], p.counts)
+        return keys, [Profile(total, name=name) for total, name in zip(totals, names)]
+    bins, n_groups = 4 ** k, len(keys)
+    ctx = kdistlib._cross_context(profiles)
+    batch = _fresh_batch(ctx, n_groups, bins) if all(p._device_counts() for p in profiles) else None
+    with _result_tables(ctx, batch, n_groups * 8 * bins) as out:
+        per = _tables_per_group(k)
+        for at in range(0, len(profiles), per):
+            members = profiles[at:at + per]
+            with kdistlib._DeviceSet(ctx, members) as dset:
+                ctx.pool_groups_device(len(members), bins, dset.ptr, codes[at:at + per], n_groups, out, accumulate=at > 0)
+        if batch is not None:
+            return keys, [Profile._from_device(batch, i, k, name) for i, name in enumerate(names)]
+        totals = np.empty((n_groups, bins), dtype=np.int64)
+        ctx.d2h(totals, out)
+        return keys, [Profile(totals[i], name=name) for i, name in enumerate(names)]
 
 
 class Profile(object):

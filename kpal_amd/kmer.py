@@ -25,6 +25,7 @@ LENGTH_ERROR = 'k-mer lengths of the files differ'
 NAMES_COUNT_ERROR = 'number of profile names does not match number of profiles'
 PAIRED_NAMES_COUNT_ERROR = 'number of left and right profile names do not match'
 PREFIX_COUNT_ERROR = 'number of name prefixes does not match number of profiles'
+POOL_NEEDS_NEAREST = '--pool needs --nearest'
 
 # dotted path of an importable function, e.g. ``package.module.function`` (kpal/kmer.py:36-38)
 _DOTTED_PATH = re.compile(r'[_a-zA-Z][_a-zA-Z0-9]*(\.[_a-zA-Z][_a-zA-Z0-9]*)+$')
@@ -406,10 +407,11 @@ def distance_matrix(input_handle, output_handle, names=None, distance_function='
 def cross(input_handle_left, input_handle_right, output_handle, names_left=None, names_right=None,
           distance_function='default', pairwise='prod', custom_pairwise=None, do_smooth=False, summary='min',
           custom_summary=None, threshold=0, do_scale=False, down=False, do_positive=False, do_balance=False,
-          precision=10, nearest=None):
+          precision=10, nearest=None, pool=None):
     """Distances of every profile of the left file to every profile of the right file: ``Q R``, the left names, the
     right names, then Q lines of R distances; with --nearest N, ``left right distance`` lines of the N closest right
-    profiles per left profile instead.
+    profiles per left profile instead; with --pool FILE next to it, FILE receives for every right profile that is the
+    closest of some left profile the pooled (summed) profile of those left profiles, under the right profile's name.
 
     A fixed number of kernel launches per chunk of the right file for the built-in functions; the right file is read profile by
     profile, so only a chunk of it is resident at a time."""
@@ -419,10 +421,12 @@ def cross(input_handle_left, input_handle_right, output_handle, names_left=None,
         raise ValueError('you must give at least one k-mer profile on each side')
     if nearest is not None and nearest < 1:
         raise ValueError('--nearest needs a positive number')
+    if pool is not None and nearest is None:
+        raise ValueError(POOL_NEEDS_NEAREST)
     dist = _profile_distance(distance_function, pairwise, custom_pairwise, do_smooth, summary, custom_summary,
                              threshold, do_scale, down, do_positive, do_balance)
     if nearest is not None:
-        _cross_nearest(input_handle_left, names_left, input_handle_right, names_right, output_handle, dist, precision, nearest)
+        _cross_nearest(input_handle_left, names_left, input_handle_right, names_right, output_handle, dist, precision, nearest, pool)
         return
     left = [klib.Profile.from_file(input_handle_left, name=name) for name in names_left]
 
@@ -462,10 +466,13 @@ class _FileProfiles(object):
         return self._read(self.names[item])
 
 
-def _cross_nearest(input_handle_left, names_left, input_handle_right, names_right, output_handle, dist, precision, nearest):
+def _cross_nearest(input_handle_left, names_left, input_handle_right, names_right, output_handle, dist, precision, nearest, pool=None):
     """``left right distance`` lines of the ``nearest`` closest right profiles of every left profile.  The left file is read in
     groups (``_profile_groups``) and the right file chunk by chunk when it does not fit the device at once; the distances are
-    selected on the device (``kdistlib.nearest_chunks``), so no Q x R rectangle is built."""
+    selected on the device (``kdistlib.nearest_chunks``), so no Q x R rectangle is built.  ``pool``: an open profile file that
+    receives one profile per right name that is the closest (the first hit; a NaN distance is no hit) of a left profile -- the
+    sum of those left profiles, pooled group of the left file by group of the left file (``klib.pooled_by``) -- in the order
+    of the right names."""
     lengths = []
 
     def left():
@@ -478,10 +485,17 @@ def _cross_nearest(input_handle_left, names_left, input_handle_right, names_righ
                 yield profile
 
     right = _FileProfiles(input_handle_right, names_right, lengths)
+    pools = {}
     for chunk, indices, distances in kdistlib.nearest_chunks(left(), right, dist, nearest):
         for profile, row, values in zip(chunk, indices, distances):
             for r, value in zip(row, values):
                 print(profile.name, names_right[r], _fixed(precision, value), file=output_handle)
+        if pool is not None:
+            hits = [None if np.isnan(d) else int(r) for r, d in zip(indices[:, 0], distances[:, 0])]
+            for r, pooled in zip(*klib.pooled_by(chunk, hits)):
+                pools[r] = pooled if r not in pools else klib.pooled([pools[r], pooled])
+    for r in sorted(pools):
+        pools[r].save(pool, name=names_right[r])
 
 
 def _parsers():
@@ -626,6 +640,18 @@ def build_parser():
     sub.add_argument('--nearest', dest='nearest', metavar='N', type=int, default=None,
                      help='write "left right distance" lines for the N closest right profiles of every left profile '
                      'instead of the matrix')
+    sub.add_argument('--pool', dest='pool', metavar='FILE', type=ProfileFileType('w'), default=None,
+                     help='with --nearest: write to the k-mer profile file FILE, for every right profile that is the closest '
+                     'of some left profile, the pooled (summed) profile of those left profiles under the right profile\'s name')
+    parse_cross = sub.parse_known_args
+
+    def parse_cross_checked(args=None, namespace=None, sub=sub):
+        namespace, rest = parse_cross(args, namespace)
+        if namespace.pool is not None and namespace.nearest is None:
+            sub.error(POOL_NEEDS_NEAREST)
+        return namespace, rest
+
+    sub.parse_known_args = parse_cross_checked     # (the two options are checked against each other where they are parsed)
     return parser
 
 

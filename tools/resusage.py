@@ -1,6 +1,6 @@
 """Per-kernel register / spill / LDS summary from hipcc's -Rpass-analysis=kernel-resource-usage remarks.
 Usage: python tools/resusage.py UNIT [name-substring ...] [-DMACRO ...]
-(compiles kpal_amd/csrc/UNIT.hip -- kpal_quads, kpal_quads2, kpal_count, kpal_text, kpal_records, kpal_vec, kpal_sets, kpal_spectrum, kpal_transform, kpal_pair, kpal_cross, kpal_paired, kpal_paired_smooth, kpal_nearest --, no GPU needed)"""
+(compiles kpal_amd/csrc/UNIT.hip -- kpal_quads, kpal_quads2, kpal_count, kpal_text, kpal_records, kpal_vec, kpal_sets, kpal_spectrum, kpal_transform, kpal_pool_groups, kpal_pair, kpal_cross, kpal_paired, kpal_paired_smooth, kpal_nearest --, no GPU needed)"""
 import re
 import subprocess
 import sys
