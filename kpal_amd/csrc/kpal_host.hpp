@@ -6,7 +6,8 @@
 // split, summaries, merge, shrink; kpal_sets.hip: the summaries and the strand balance of a whole set of vectors, planned by
 // stat_plan.hpp, and the strand balance of one vector, which is a set of one; kpal_spectrum.hip: the count-of-counts spectrum of
 // every vector of a set, planned by spectrum_plan.hpp; kpal_transform.hip: the balance, the shrink and the pool of a whole set of
-// vectors, planned by transform_plan.hpp; kpal_pool_groups.hip: the pool of a set by label, planned by pool_groups_plan.hpp;
+// vectors, planned by transform_plan.hpp; kpal_pool_groups.hip: the pool of a set by label, planned by pool_groups_plan.hpp --
+// these five share table_host.hpp on top of this header: the argument checks, the upload of host tables, the shrink launch;
 // kpal_multi.hip: multi-GPU entry points over RCCL.  The five units that serve distances
 // share dist_host.hpp on top of this header -- kpal_pair.hip: the distance of one pair, plain and with options; kpal_cross.hip:
 // the distances of sets of profiles, triangle and rectangle, plain, with options and with dynamic smoothing, planned by
@@ -212,7 +213,8 @@ struct kpal_ctx {
     hipEvent_t ev_copied[2] = {nullptr, nullptr};
     hipEvent_t ev_done[2] = {nullptr, nullptr};
     bool stage_used[2] = {false, false};
-    // Scratch for vector ops.  kpal_vec, kpal_sets, kpal_records, kpal_spectrum and kpal_multi use scratch[0..3] within one function.
+    // Scratch for vector ops.  kpal_vec, kpal_sets, kpal_records, kpal_spectrum and kpal_multi use scratch[0..3] within one function;
+    // the host entries of the table units fill them through table_host.hpp alone (upload_vector; for_uploaded_chunks: scratch[0]).
     // The distance units (dist_host.hpp) hold a buffer ACROSS calls into functions that take workspace themselves, by these roles.
     // ensure() frees a buffer that must grow: a callee that grew one its caller still points into would leave that pointer
     // dangling, so only the functions of the last column may ensure() a buffer, and nothing called while a pointer is held does.

@@ -3,6 +3,7 @@
 // pool_groups_plan.hpp; the kernel: pool_groups_kernels.hpp).  Every table is read once, where it lies.  The index of the plan
 // goes up in one copy; the launches are queued on the context's stream and nothing is downloaded.
 #include "kpal_host.hpp"
+#include "table_host.hpp"
 
 #include "pool_groups_kernels.hpp"
 
@@ -15,7 +16,7 @@ static int launch_pool_groups(kpal_ctx *ctx, const char *name, const int64_t *ta
     const int shift = pool_groups_lane_shift(bins);
     const uint64_t item_workgroups = pool_groups_item_workgroups(n_items, bins);
     const dim3 grid((unsigned)pool_column_groups(bins), (unsigned)std::min<uint64_t>(item_workgroups, kPoolGroupsMaxGridY)), block(kPoolThreads);
-    const bool vec = bins % 2 == 0 && (uintptr_t)tables % 16 == 0 && (uintptr_t)out % 16 == 0;
+    const bool vec = pool_rows_by_16(bins, tables, out);
     const bool wave = shift >= 6;
     if (vec && wave) LAUNCH(ctx, name, (pool_groups_kernel<true, true, LISTED>), grid, block, tables, bins, members, begin, (uint32_t)n_items, shift, accumulate, out);
     else if (vec) LAUNCH(ctx, name, (pool_groups_kernel<true, false, LISTED>), grid, block, tables, bins, members, begin, (uint32_t)n_items, shift, accumulate, out);
@@ -28,15 +29,13 @@ KPAL_API int kpal_pool_groups_device(kpal_ctx *ctx, size_t n_tables, size_t bins
                                      int accumulate, int64_t *dev_out)
 {
     CTX_ENTER(ctx);
-    if (!dev_tables || !labels || !dev_out) return set_err(KPAL_E_INVALID, "NULL pointer");
-    if (n_tables == 0) return set_err(KPAL_E_INVALID, "empty set");
-    if (bins == 0) return set_err(KPAL_E_INVALID, "empty vector");
+    CHK(check_set(dev_tables && labels && dev_out, n_tables));
+    CHK(check_vector(bins));
     if (n_groups == 0) return set_err(KPAL_E_INVALID, "no groups");
-    if ((uintptr_t)dev_tables % 8 != 0 || (uintptr_t)dev_out % 8 != 0) return set_err(KPAL_E_INVALID, "tables are not 8-byte aligned");
+    CHK(check_aligned(dev_tables, dev_out));
     if (!pool_groups_fit(n_tables, n_groups, bins))
         return set_err(KPAL_E_INVALID, "%zu tables of %zu bins in %zu groups: too many bytes", n_tables, bins, n_groups);
-    if (transform_overlap((uint64_t)(uintptr_t)dev_tables, (uint64_t)n_tables * bins * 8, (uint64_t)(uintptr_t)dev_out, (uint64_t)n_groups * bins * 8) !=
-        kTransformDisjoint)
+    if (tables_overlap(dev_tables, (uint64_t)n_tables * bins * 8, dev_out, (uint64_t)n_groups * bins * 8) != kTransformDisjoint)
         return set_err(KPAL_E_INVALID, "pool of groups: the output overlaps the tables");
     PoolGroupsPlan plan;
     const int status = pool_groups_plan(labels, n_tables, n_groups, bins, (uint64_t)ctx->num_cu, plan);

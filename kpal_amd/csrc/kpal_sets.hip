@@ -2,17 +2,9 @@
 // and the strand balance of every profile, in a number of launches that does not grow with the set (planned by stat_plan.hpp,
 // the kernels in stat_set_kernels.hpp).  The strand balance of ONE vector is here too: a set of one table, no other implementation.
 #include "kpal_host.hpp"
+#include "table_host.hpp"
 
 #include "stat_set_kernels.hpp"
-
-// KPAL_STAT_SET_PROFILES: a lower cap on the profiles of one pass (read on every call: tests put a chunk seam into small sets).
-static uint64_t stat_set_cap()
-{
-    const char *e = getenv("KPAL_STAT_SET_PROFILES");
-    if (!e || !*e) return 0;
-    const long long v = atoll(e);
-    return v > 0 ? (uint64_t)v : 0;
-}
 
 // The summaries of `count` consecutive tables: 8 launches and 2 per digit, 2 synchronisations.
 static int stats_set_pass(kpal_ctx *ctx, uint64_t count, uint64_t bins, const int64_t *dev_tables, kpal_profile_stats *host_out)
@@ -58,51 +50,33 @@ static int stats_set_pass(kpal_ctx *ctx, uint64_t count, uint64_t bins, const in
     return KPAL_OK;
 }
 
-static int stats_set_check(size_t n_tables, size_t bins, const int64_t *tables, const kpal_profile_stats *out)
-{
-    if (!tables || !out) return set_err(KPAL_E_INVALID, "NULL pointer");
-    if (n_tables == 0) return set_err(KPAL_E_INVALID, "empty set");
-    if (bins == 0) return set_err(KPAL_E_INVALID, "empty vector");
-    if ((uintptr_t)tables % 8 != 0) return set_err(KPAL_E_INVALID, "tables are not 8-byte aligned");
-    if (bins > (SIZE_MAX / 8) / n_tables) return set_err(KPAL_E_INVALID, "%zu tables of %zu bins: too many bytes", n_tables, bins);
-    return KPAL_OK;
-}
-
 KPAL_API int kpal_stats_set_device(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *dev_tables, kpal_profile_stats *host_out)
 {
     CTX_ENTER(ctx);
-    CHK(stats_set_check(n_tables, bins, dev_tables, host_out));
+    CHK(check_counted_set(n_tables, bins, dev_tables, host_out));
     const uint64_t per = stat_profiles_per_pass(stat_scratch_bytes(bins), kStatSetBudgetBytes, stat_set_cap());
     for (const StatChunk &c : stat_chunks(n_tables, per))
         CHK(stats_set_pass(ctx, c.count, bins, dev_tables + c.first * (uint64_t)bins, host_out + c.first));
     return KPAL_OK;
 }
 
-// Host tables go through the context's scratch, at most kSetUploadBytes of them at a time (never less than one table).
-constexpr uint64_t kSetUploadBytes = 1ULL << 30;
-
 KPAL_API int kpal_stats_set(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *host_tables, kpal_profile_stats *host_out)
 {
     CTX_ENTER(ctx);
-    CHK(stats_set_check(n_tables, bins, host_tables, host_out));
-    const uint64_t per = std::max<uint64_t>(1, kSetUploadBytes / ((uint64_t)bins * 8));
-    for (const StatChunk &c : stat_chunks(n_tables, per)) {
-        CHK(ensure(ctx, ctx->scratch[0], (size_t)(c.count * bins * 8)));
-        HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, host_tables + c.first * (uint64_t)bins, (size_t)(c.count * bins * 8), hipMemcpyHostToDevice, ctx->stream));
-        CHK(kpal_stats_set_device(ctx, (size_t)c.count, bins, (const int64_t *)ctx->scratch[0].p, host_out + c.first));
-    }
-    return KPAL_OK;
+    CHK(check_counted_set(n_tables, bins, host_tables, host_out));
+    return for_uploaded_chunks(ctx, n_tables, bins, host_tables, [&](uint64_t first, uint64_t count, const int64_t *dev) {
+        return kpal_stats_set_device(ctx, (size_t)count, bins, dev, host_out + first);
+    });
 }
 
+// (the pairwise stands between the empty set and the alignment)
 static int balance_set_check(int k, size_t n_tables, const int64_t *tables, int pairwise, const double *out)
 {
-    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
-    if (!tables || !out) return set_err(KPAL_E_INVALID, "NULL pointer");
-    if (n_tables == 0) return set_err(KPAL_E_INVALID, "empty set");
+    CHK(check_k(k));
+    CHK(check_set(tables && out, n_tables));
     if (pairwise != KPAL_PAIRWISE_PROD && pairwise != KPAL_PAIRWISE_SUM) return set_err(KPAL_E_INVALID, "pairwise must be prod or sum");
-    if ((uintptr_t)tables % 8 != 0) return set_err(KPAL_E_INVALID, "tables are not 8-byte aligned");
-    if (n_tables > (SIZE_MAX >> (2 * k + 3))) return set_err(KPAL_E_INVALID, "%zu tables at k=%d: too many bytes", n_tables, k);
-    return KPAL_OK;
+    CHK(check_aligned(tables));
+    return check_bytes_at_k(n_tables, k);
 }
 
 KPAL_API int kpal_strand_balance_set_device(kpal_ctx *ctx, int k, size_t n_tables, const int64_t *dev_tables, int pairwise, double *host_out)
@@ -135,14 +109,9 @@ KPAL_API int kpal_strand_balance_set(kpal_ctx *ctx, int k, size_t n_tables, cons
 {
     CTX_ENTER(ctx);
     CHK(balance_set_check(k, n_tables, host_tables, pairwise, host_out));
-    const uint64_t n = 1ULL << (2 * k);
-    const uint64_t per = std::max<uint64_t>(1, kSetUploadBytes / (n * 8));
-    for (const StatChunk &c : stat_chunks(n_tables, per)) {
-        CHK(ensure(ctx, ctx->scratch[0], (size_t)(c.count * n * 8)));
-        HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, host_tables + c.first * n, (size_t)(c.count * n * 8), hipMemcpyHostToDevice, ctx->stream));
-        CHK(kpal_strand_balance_set_device(ctx, k, (size_t)c.count, (const int64_t *)ctx->scratch[0].p, pairwise, host_out + c.first));
-    }
-    return KPAL_OK;
+    return for_uploaded_chunks(ctx, n_tables, 1ULL << (2 * k), host_tables, [&](uint64_t first, uint64_t count, const int64_t *dev) {
+        return kpal_strand_balance_set_device(ctx, k, (size_t)count, dev, pairwise, host_out + first);
+    });
 }
 
 // One vector is a set of one table: the same checks with the same texts, the same kernels on the same grid, the same bits.

@@ -3,18 +3,10 @@
 // spectrum_plan.hpp, the kernels in spectrum_kernels.hpp).  One table is a set of one: there is no other implementation.  The
 // result is ragged, so the entries are a begin / fetch pair: the pairs stay with the context.
 #include "kpal_host.hpp"
+#include "table_host.hpp"
 
 #include "stat_set_kernels.hpp"
 #include "spectrum_kernels.hpp"
-
-// KPAL_STAT_SET_PROFILES: a lower cap on the tables of one pass (read on every call: tests put a pass seam into small sets).
-static uint64_t spectrum_set_cap()
-{
-    const char *e = getenv("KPAL_STAT_SET_PROFILES");
-    if (!e || !*e) return 0;
-    const long long v = atoll(e);
-    return v > 0 ? (uint64_t)v : 0;
-}
 
 // The spectra of `count` consecutive tables, appended to the context's pairs; offsets[t + 1] = where table t's pairs end.
 // 6 launches (7 if any entry lies past its table's window), 3 synchronisations.
@@ -100,16 +92,6 @@ static int spectrum_pass(kpal_ctx *ctx, uint64_t count, uint64_t bins, const int
     return KPAL_OK;
 }
 
-static int spectrum_check(size_t n_tables, size_t bins, const int64_t *tables, const uint64_t *offsets)
-{
-    if (!tables || !offsets) return set_err(KPAL_E_INVALID, "NULL pointer");
-    if (n_tables == 0) return set_err(KPAL_E_INVALID, "empty set");
-    if (bins == 0) return set_err(KPAL_E_INVALID, "empty vector");
-    if ((uintptr_t)tables % 8 != 0) return set_err(KPAL_E_INVALID, "tables are not 8-byte aligned");
-    if (bins > (SIZE_MAX / 8) / n_tables) return set_err(KPAL_E_INVALID, "%zu tables of %zu bins: too many bytes", n_tables, bins);
-    return KPAL_OK;
-}
-
 static void spectrum_reset(kpal_ctx *ctx)
 {
     ctx->spec_pending = false;
@@ -120,20 +102,22 @@ static void spectrum_reset(kpal_ctx *ctx)
 // The passes of a set whose first table is table `first` of the call: offsets[first] is set already.
 static int spectrum_device(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *dev_tables, uint64_t *offsets)
 {
-    const uint64_t per = spectrum_tables_per_pass(bins, kStatSetBudgetBytes, spectrum_set_cap());
+    const uint64_t per = spectrum_tables_per_pass(bins, kStatSetBudgetBytes, stat_set_cap());
     for (const StatChunk &c : stat_chunks(n_tables, per))
         CHK(spectrum_pass(ctx, c.count, bins, dev_tables + c.first * (uint64_t)bins, offsets + c.first));
     return KPAL_OK;
 }
 
-KPAL_API int kpal_distribution_set_device(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *dev_tables, uint64_t *host_offsets)
+// What the two entries do around their passes: the pairs of the call before are dropped first, even by a call that is refused.
+template <class Passes>
+static int spectrum_entry(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *tables, uint64_t *host_offsets, Passes passes)
 {
     CTX_ENTER(ctx);
     spectrum_reset(ctx);
-    CHK(spectrum_check(n_tables, bins, dev_tables, host_offsets));
+    CHK(check_counted_set(n_tables, bins, tables, host_offsets));
     host_offsets[0] = 0;
     try {
-        CHK(spectrum_device(ctx, n_tables, bins, dev_tables, host_offsets));
+        CHK(passes());
     } catch (const std::bad_alloc &) {
         spectrum_reset(ctx);
         return set_err(KPAL_E_NOMEM, "distribution of a set: out of host memory");
@@ -142,28 +126,18 @@ KPAL_API int kpal_distribution_set_device(kpal_ctx *ctx, size_t n_tables, size_t
     return KPAL_OK;
 }
 
-// Host tables go through the context's scratch, at most kSpectrumUploadBytes of them at a time (never less than one table).
-constexpr uint64_t kSpectrumUploadBytes = 1ULL << 30;
+KPAL_API int kpal_distribution_set_device(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *dev_tables, uint64_t *host_offsets)
+{
+    return spectrum_entry(ctx, n_tables, bins, dev_tables, host_offsets, [&] { return spectrum_device(ctx, n_tables, bins, dev_tables, host_offsets); });
+}
 
 KPAL_API int kpal_distribution_set(kpal_ctx *ctx, size_t n_tables, size_t bins, const int64_t *host_tables, uint64_t *host_offsets)
 {
-    CTX_ENTER(ctx);
-    spectrum_reset(ctx);
-    CHK(spectrum_check(n_tables, bins, host_tables, host_offsets));
-    host_offsets[0] = 0;
-    const uint64_t per = std::max<uint64_t>(1, kSpectrumUploadBytes / ((uint64_t)bins * 8));
-    try {
-        for (const StatChunk &c : stat_chunks(n_tables, per)) {
-            CHK(ensure(ctx, ctx->scratch[0], (size_t)(c.count * bins * 8)));
-            HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, host_tables + c.first * (uint64_t)bins, (size_t)(c.count * bins * 8), hipMemcpyHostToDevice, ctx->stream));
-            CHK(spectrum_device(ctx, (size_t)c.count, bins, (const int64_t *)ctx->scratch[0].p, host_offsets + c.first));
-        }
-    } catch (const std::bad_alloc &) {
-        spectrum_reset(ctx);
-        return set_err(KPAL_E_NOMEM, "distribution of a set: out of host memory");
-    }
-    ctx->spec_pending = true;
-    return KPAL_OK;
+    return spectrum_entry(ctx, n_tables, bins, host_tables, host_offsets, [&] {
+        return for_uploaded_chunks(ctx, n_tables, bins, host_tables, [&](uint64_t first, uint64_t count, const int64_t *dev) {
+            return spectrum_device(ctx, (size_t)count, bins, dev, host_offsets + first);
+        });
+    });
 }
 
 KPAL_API int kpal_distribution_fetch(kpal_ctx *ctx, uint64_t first_pair, uint64_t n_pairs, int64_t *host_values, uint64_t *host_numbers)

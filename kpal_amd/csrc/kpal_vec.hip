@@ -1,10 +1,10 @@
 // kpal_vec.hip -- everything of the C-ABI that works on ONE count vector: balance, split, the reduction of (sum, count)
-// partials every distance ends with, profile summaries, merge and shrink.  (The strand balance of one vector: kpal_sets.hip.)
+// partials every distance ends with, profile summaries, merge and shrink (shrink_launch serves the shrink of a set too).  (The strand balance of one vector: kpal_sets.hip.)
 #include "kpal_host.hpp"
+#include "table_host.hpp"
 
 #include "vec_kernels.hpp"
 #include "stat_kernels.hpp"
-#include "stat_plan.hpp"
 
 KPAL_API uint64_t kpal_reverse_complement(uint64_t number, int k)
 {
@@ -74,7 +74,7 @@ int launch_balance(kpal_ctx *ctx, int k, const int64_t *in, int64_t *out)
 KPAL_API int kpal_balance_device(kpal_ctx *ctx, int k, int64_t *dev_inout)
 {
     CTX_ENTER(ctx);
-    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
+    CHK(check_k(k));
     if (!dev_inout) return set_err(KPAL_E_INVALID, "dev_inout is NULL");
     if (ctx->counting && dev_inout == (int64_t *)ctx->table.p && k == ctx->k) return kpal_count_balance(ctx);   // (fuses with a pending finalisation)
     return launch_balance(ctx, k, dev_inout, dev_inout);
@@ -83,35 +83,32 @@ KPAL_API int kpal_balance_device(kpal_ctx *ctx, int k, int64_t *dev_inout)
 KPAL_API int kpal_balance(kpal_ctx *ctx, int k, int64_t *host_inout)
 {
     CTX_ENTER(ctx);
-    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
+    CHK(check_k(k));
     if (!host_inout) return set_err(KPAL_E_INVALID, "host_inout is NULL");
     const uint64_t n = 1ULL << (2 * k);
-    CHK(ensure(ctx, ctx->scratch[0], n * 8));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, host_inout, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    CHK(kpal_balance_device(ctx, k, (int64_t *)ctx->scratch[0].p));
-    HIPCHK(hipMemcpyAsync(host_inout, ctx->scratch[0].p, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return KPAL_OK;
+    int64_t *d = nullptr;
+    CHK(upload_vector(ctx, 0, host_inout, n, &d));
+    CHK(kpal_balance_device(ctx, k, d));
+    return download_wait(ctx, host_inout, d, n);
 }
 
 KPAL_API int kpal_split(kpal_ctx *ctx, int k, const int64_t *host_counts, int64_t *host_forward,
                         int64_t *host_reverse, uint64_t *n_out)
 {
     CTX_ENTER(ctx);
-    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
-    if (!host_counts || !host_forward || !host_reverse) return set_err(KPAL_E_INVALID, "NULL pointer");
+    CHK(check_k(k));
+    CHK(check_pointers(host_counts && host_forward && host_reverse));
     const uint64_t n = 1ULL << (2 * k);
     const uint64_t pal = (k % 2 == 0) ? (1ULL << k) : 0ULL;   // 4^(k/2) palindromes for even k
     const uint64_t m = (n + pal) / 2;
     const uint32_t nseg = (uint32_t)((n + kSplitSeg - 1) / kSplitSeg);
-    CHK(ensure(ctx, ctx->scratch[0], n * 8));
+    int64_t *dc = nullptr;
+    CHK(upload_vector(ctx, 0, host_counts, n, &dc));
     CHK(ensure(ctx, ctx->scratch[1], m * 8));
     CHK(ensure(ctx, ctx->scratch[2], m * 8));
     CHK(ensure(ctx, ctx->scratch[3], (size_t)nseg * 16));
-    int64_t *dc = (int64_t *)ctx->scratch[0].p;
     uint32_t *dcount = (uint32_t *)ctx->scratch[3].p;
     uint64_t *doffs = (uint64_t *)((uint8_t *)ctx->scratch[3].p + (size_t)nseg * 4 + ((size_t)nseg * 4) % 8);
-    HIPCHK(hipMemcpyAsync(dc, host_counts, n * 8, hipMemcpyHostToDevice, ctx->stream));
     LAUNCH(ctx, "split_count", split_count_kernel, dim3(nseg), dim3(256), k, n, dcount);
     std::vector<uint32_t> hc(nseg);
     HIPCHK(hipMemcpyAsync(hc.data(), dcount, (size_t)nseg * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -127,8 +124,7 @@ KPAL_API int kpal_split(kpal_ctx *ctx, int k, const int64_t *host_counts, int64_
     LAUNCH(ctx, "split_write", split_write_kernel, dim3(nseg), dim3(256), (const int64_t *)dc, k, n,
            (const uint64_t *)doffs, (int64_t *)ctx->scratch[1].p, (int64_t *)ctx->scratch[2].p);
     HIPCHK(hipMemcpyAsync(host_forward, ctx->scratch[1].p, m * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(host_reverse, ctx->scratch[2].p, m * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    CHK(download_wait(ctx, host_reverse, (const int64_t *)ctx->scratch[2].p, m));
     if (n_out) *n_out = m;
     return KPAL_OK;
 }
@@ -164,8 +160,8 @@ double finish_value(int metric, const Partial &p, int64_t *aux)
 KPAL_API int kpal_stats_device(kpal_ctx *ctx, size_t n, const int64_t *dev_counts, kpal_profile_stats *out)
 {
     CTX_ENTER(ctx);
-    if (!dev_counts || !out) return set_err(KPAL_E_INVALID, "NULL pointer");
-    if (n == 0) return set_err(KPAL_E_INVALID, "empty vector");
+    CHK(check_pointers(dev_counts && out));
+    CHK(check_vector(n));
     const unsigned grid = stream_grid(ctx, n, kStatThreads);
     CHK(ensure(ctx, ctx->partials, (size_t)grid * sizeof(StatPartial) + 256 * 8));
     StatPartial *dp = (StatPartial *)ctx->partials.p;
@@ -246,19 +242,24 @@ KPAL_API int kpal_stats_device(kpal_ctx *ctx, size_t n, const int64_t *dev_count
 KPAL_API int kpal_stats(kpal_ctx *ctx, size_t n, const int64_t *host_counts, kpal_profile_stats *out)
 {
     CTX_ENTER(ctx);
-    if (!host_counts || !out) return set_err(KPAL_E_INVALID, "NULL pointer");
-    if (n == 0) return set_err(KPAL_E_INVALID, "empty vector");
-    CHK(ensure(ctx, ctx->scratch[0], n * 8));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, host_counts, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    return kpal_stats_device(ctx, n, (const int64_t *)ctx->scratch[0].p, out);
+    CHK(check_pointers(host_counts && out));
+    CHK(check_vector(n));
+    int64_t *d = nullptr;
+    CHK(upload_vector(ctx, 0, host_counts, n, &d));
+    return kpal_stats_device(ctx, n, d, out);
+}
+
+static int merge_check(bool pointers_given, int merger)   // the pointers, then the merger; n == 0 is taken, after both
+{
+    CHK(check_pointers(pointers_given));
+    return merger < KPAL_MERGE_SUM || merger > KPAL_MERGE_NINT ? set_err(KPAL_E_INVALID, "unknown merger %d", merger) : KPAL_OK;
 }
 
 KPAL_API int kpal_merge_device(kpal_ctx *ctx, size_t n, const int64_t *dev_left, const int64_t *dev_right, int merger,
                                int64_t *dev_out)
 {
     CTX_ENTER(ctx);
-    if (!dev_left || !dev_right || !dev_out) return set_err(KPAL_E_INVALID, "NULL pointer");
-    if (merger < KPAL_MERGE_SUM || merger > KPAL_MERGE_NINT) return set_err(KPAL_E_INVALID, "unknown merger %d", merger);
+    CHK(merge_check(dev_left && dev_right && dev_out, merger));
     if (n == 0) return KPAL_OK;
     const unsigned grid = stream_grid(ctx, n);
     switch (merger) {
@@ -274,47 +275,39 @@ KPAL_API int kpal_merge(kpal_ctx *ctx, size_t n, const int64_t *host_left, const
                         int64_t *host_out)
 {
     CTX_ENTER(ctx);
-    if (!host_left || !host_right || !host_out) return set_err(KPAL_E_INVALID, "NULL pointer");
-    if (merger < KPAL_MERGE_SUM || merger > KPAL_MERGE_NINT) return set_err(KPAL_E_INVALID, "unknown merger %d", merger);
+    CHK(merge_check(host_left && host_right && host_out, merger));
     if (n == 0) return KPAL_OK;
-    CHK(ensure(ctx, ctx->scratch[0], n * 8));
-    CHK(ensure(ctx, ctx->scratch[1], n * 8));
-    int64_t *dl = (int64_t *)ctx->scratch[0].p, *dr = (int64_t *)ctx->scratch[1].p;
-    HIPCHK(hipMemcpyAsync(dl, host_left, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(dr, host_right, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    int64_t *dl = nullptr, *dr = nullptr;
+    CHK(upload_vector(ctx, 0, host_left, n, &dl));
+    CHK(upload_vector(ctx, 1, host_right, n, &dr));
     CHK(kpal_merge_device(ctx, n, dl, dr, merger, dl));
-    HIPCHK(hipMemcpyAsync(host_out, dl, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return download_wait(ctx, host_out, dl, n);
+}
+
+int shrink_launch(kpal_ctx *ctx, const char *name, const int64_t *in, uint64_t n, uint64_t m, int64_t *out, bool in_aligned_16)
+{
+    if (m <= 64 && in_aligned_16) LAUNCH(ctx, name, shrink_small_kernel, dim3(stream_grid(ctx, n / 2)), dim3(256), in, n / 2, (int)(m / 2), out);
+    else LAUNCH(ctx, name, shrink_large_kernel, dim3(stream_grid(ctx, n / m * 64)), dim3(256), in, n / m, m, out);
     return KPAL_OK;
 }
 
 KPAL_API int kpal_shrink_device(kpal_ctx *ctx, int k, int factor, const int64_t *dev_counts, int64_t *dev_out)
 {
     CTX_ENTER(ctx);
-    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
-    if (factor < 1 || factor >= k) return set_err(KPAL_E_INVALID, "Reduction factor should be smaller than k-mer size.");
-    if (!dev_counts || !dev_out) return set_err(KPAL_E_INVALID, "NULL pointer");
-    const uint64_t n = 1ULL << (2 * k), m = 1ULL << (2 * factor), n_out = n / m;
-    if (m <= 64) {
-        LAUNCH(ctx, "shrink", shrink_small_kernel, dim3(stream_grid(ctx, n / 2)), dim3(256), dev_counts, n / 2, (int)(m / 2), dev_out);
-    } else {
-        LAUNCH(ctx, "shrink", shrink_large_kernel, dim3(stream_grid(ctx, n_out * 64)), dim3(256), dev_counts, n_out, m, dev_out);
-    }
-    return KPAL_OK;
+    CHK(check_shrink(k, factor));
+    CHK(check_pointers(dev_counts && dev_out));
+    return shrink_launch(ctx, "shrink", dev_counts, 1ULL << (2 * k), 1ULL << (2 * factor), dev_out);
 }
 
 KPAL_API int kpal_shrink(kpal_ctx *ctx, int k, int factor, const int64_t *host_counts, int64_t *host_out)
 {
     CTX_ENTER(ctx);
-    if (k < 1 || k > KPAL_MAX_K) return set_err(KPAL_E_INVALID, "k=%d out of range", k);
-    if (factor < 1 || factor >= k) return set_err(KPAL_E_INVALID, "Reduction factor should be smaller than k-mer size.");
-    if (!host_counts || !host_out) return set_err(KPAL_E_INVALID, "NULL pointer");
+    CHK(check_shrink(k, factor));
+    CHK(check_pointers(host_counts && host_out));
     const uint64_t n = 1ULL << (2 * k), n_out = n >> (2 * factor);
-    CHK(ensure(ctx, ctx->scratch[0], n * 8));
+    int64_t *d = nullptr;
+    CHK(upload_vector(ctx, 0, host_counts, n, &d));
     CHK(ensure(ctx, ctx->scratch[1], n_out * 8));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, host_counts, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    CHK(kpal_shrink_device(ctx, k, factor, (const int64_t *)ctx->scratch[0].p, (int64_t *)ctx->scratch[1].p));
-    HIPCHK(hipMemcpyAsync(host_out, ctx->scratch[1].p, n_out * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return KPAL_OK;
+    CHK(kpal_shrink_device(ctx, k, factor, d, (int64_t *)ctx->scratch[1].p));
+    return download_wait(ctx, host_out, (const int64_t *)ctx->scratch[1].p, n_out);
 }

@@ -1,7 +1,7 @@
 // stat_plan.hpp -- what the host decides about the summaries and the strand balance of whole SETS of profiles before it launches
 // anything (kpal_stats_set_device, kpal_strand_balance_set_device; the kernels: stat_set_kernels.hpp).  No GPU in it:
-// kpal_sets.hip, kpal_vec.hip (the mean of a 128-bit sum), the kernels (the slice bounds, the select state) and a CPU program
-// (tests/test_stat_plan_host.py) read the same definitions.
+// kpal_sets.hip, kpal_vec.hip (the mean of a 128-bit sum), table_host.hpp (the tables of one upload of a host set), the kernels
+// (the slice bounds, the select state) and a CPU program (tests/test_stat_plan_host.py) read the same definitions.
 //
 // A table of `bins` entries is cut into SLICES of kStatSliceBins entries, one workgroup each; the grid of a pass is
 // slices x profiles.  The number of slices depends on `bins` alone, and a profile's slices are combined in slice order: what a
@@ -78,6 +78,11 @@ inline std::vector<StatChunk> stat_chunks(uint64_t n, uint64_t per_pass)
     for (uint64_t at = 0; at < n; at += per_pass) out.push_back(StatChunk{at, std::min(per_pass, n - at)});
     return out;
 }
+
+// Host tables go up through the context's scratch, at most kSetUploadBytes of them at a time -- and never less than one table
+// (table_host.hpp: for_uploaded_chunks; the chunks are stat_chunks of this).
+constexpr uint64_t kSetUploadBytes = 1ULL << 30;
+inline uint64_t stat_upload_tables(uint64_t bins) { return std::max<uint64_t>(1, kSetUploadBytes / (std::max<uint64_t>(1, bins) * 8)); }
 
 // The 128-bit two's complement sum (hi, lo) as a double: magnitude first, so that a small negative sum does not cancel.
 KPAL_MATRIX_HD double stat_sum128_to_double(uint64_t lo, int64_t hi)

@@ -9,6 +9,7 @@
 //   limits                         -> kStatSetBudgetBytes kStatSetMaxProfiles
 //   per      SCRATCH BUDGET CAP    -> stat_profiles_per_pass
 //   chunks   N PER                 -> first count first count ...
+//   upload   BINS                  -> stat_upload_tables kSetUploadBytes
 //   bgrid    K                     -> balance_set_grid balance_set_scratch_bytes
 //   sum128   LO HI                 -> stat_sum128_to_double (HI: the two's complement word)
 //   mean     LO HI BINS            -> stat_mean
@@ -52,7 +53,8 @@ int main()
             const std::vector<StatChunk> chunks = stat_chunks(a[0], a[1]);
             for (size_t i = 0; i < chunks.size(); ++i) printf("%s%" PRIu64 " %" PRIu64, i ? " " : "", chunks[i].first, chunks[i].count);
             printf("\n");
-        } else if (!strcmp(what, "bgrid") && got == 1) printf("%" PRIu64 " %" PRIu64 "\n", balance_set_grid((int)a[0]), balance_set_scratch_bytes((int)a[0]));
+        } else if (!strcmp(what, "upload") && got == 1) printf("%" PRIu64 " %" PRIu64 "\n", stat_upload_tables(a[0]), kSetUploadBytes);
+        else if (!strcmp(what, "bgrid") && got == 1) printf("%" PRIu64 " %" PRIu64 "\n", balance_set_grid((int)a[0]), balance_set_scratch_bytes((int)a[0]));
         else if (!strcmp(what, "sum128") && got == 2) printf("%" PRIu64 "\n", bits(stat_sum128_to_double(a[0], (int64_t)a[1])));
         else if (!strcmp(what, "mean") && got == 3) printf("%" PRIu64 "\n", bits(stat_mean(a[0], (int64_t)a[1], a[2])));
         else if (!strcmp(what, "top") && got == 2) printf("%d\n", stat_top_byte(a[0], a[1]));

@@ -48,7 +48,9 @@ def test_header_knows_no_gpu_and_the_unit_has_two_launch_names():
                                                   'transform_bytes_fit(')),
                         ('pool_groups_kernels.hpp', ('pool_groups_plan.hpp', 'kPoolThreads', 'kPoolUnroll', 'kPoolGroupsFinalUnroll', 'pool_column_pairs(')),
                         ('kpal_pool_groups.hip', ('pool_groups_plan(', 'pool_groups_fit(', 'pool_groups_lane_shift(', 'pool_groups_item_workgroups(',
-                                                  'pool_column_groups(', 'transform_overlap(', 'kTransformDisjoint', 'kPoolGroupsMaxGridY'))):
+                                                  'pool_column_groups(', 'tables_overlap(', 'kTransformDisjoint', 'kPoolGroupsMaxGridY',
+                                                  '#include "table_host.hpp"')),
+                        ('table_host.hpp', ('transform_overlap(',))):
         text = re.sub(r'//.*', '', open(os.path.join(CSRC, user)).read())
         assert all(n in text for n in names), user
     unit = open(os.path.join(CSRC, 'kpal_pool_groups.hip')).read()

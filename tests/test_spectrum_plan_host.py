@@ -52,7 +52,9 @@ def test_header_knows_no_gpu():
                                                   'kSpectrumScanThreads', 'SpectrumRange', 'SpectrumOverflow', 'stat_slice_begin(', 'stat_slice_end(')),
                         ('kpal_spectrum.hip', ('spectrum_window(', 'spectrum_window_slices(', 'spectrum_scratch_bytes(', 'spectrum_tables_per_pass(',
                                                'spectrum_value(', 'stat_slices(', 'stat_chunks(', 'kStatSetBudgetBytes', 'kSpectrumOverflowBytes',
-                                               'getenv("KPAL_STAT_SET_PROFILES")'))):
+                                               'stat_set_cap()', 'for_uploaded_chunks(', '#include "table_host.hpp"')),
+                        # the cap of a pass is read by the host front end of the table units, there alone
+                        ('table_host.hpp', ('getenv("KPAL_STAT_SET_PROFILES")',))):
         text = re.sub(r'//.*', '', open(os.path.join(CSRC, user)).read())
         assert all(n in text for n in names), user
     # no size of the plan restated, one key mapping

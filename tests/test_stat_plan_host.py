@@ -53,13 +53,19 @@ def test_header_knows_no_gpu():
     for user, names in (('stat_set_kernels.hpp', ('stat_slice_begin(', 'stat_slice_end(', 'stat_mean(', 'stat_top_byte(', 'stat_mask_above(',
                                                   'StatSetState', 'kStatSetThreads', 'kStatHistBins', 'kStatPartialBytes')),
                         ('kpal_sets.hip', ('stat_slices(', 'stat_scratch_bytes(', 'stat_profiles_per_pass(', 'stat_chunks(', 'balance_set_grid(',
-                                           'balance_set_scratch_bytes(', 'kStatSetBudgetBytes', 'getenv("KPAL_STAT_SET_PROFILES")')),
+                                           'balance_set_scratch_bytes(', 'kStatSetBudgetBytes', 'stat_set_cap()', 'for_uploaded_chunks(',
+                                           '#include "table_host.hpp"')),
+                        # the host front end of the table units: the cap of a pass and the tables of an upload
+                        ('table_host.hpp', ('getenv("KPAL_STAT_SET_PROFILES")', 'stat_chunks(', 'stat_upload_tables(')),
                         ('kpal_vec.hip', ('stat_mean(',))):
         text = re.sub(r'//.*', '', open(os.path.join(CSRC, user)).read())
         assert all(n in text for n in names), user
     # one conversion of the 128-bit sum for the single-profile and the set entry, and no slice size restated
     sources = {f: re.sub(r'//.*', '', open(os.path.join(CSRC, f)).read()) for f in os.listdir(CSRC)}
     assert [f for f, t in sources.items() if '18446744073709551616.0' in t or 'ldexp' in t] == ['stat_plan.hpp']
+    # one reader of the cap's environment variable, one upload budget
+    assert [(f, t.count('"KPAL_STAT_SET_PROFILES"')) for f, t in sources.items() if 'KPAL_STAT_SET_PROFILES' in t] == [('table_host.hpp', 1)]
+    assert [(f, len(re.findall(r'=\s*1ULL << 30', t))) for f, t in sources.items() if 'UploadBytes' in t] == [('stat_plan.hpp', 1)]
     assert not any('8192' in sources[f] for f in ('stat_set_kernels.hpp', 'kpal_sets.hip'))
     # the set kernels stay quiet
     assert 'printf' not in sources['stat_set_kernels.hpp'] and not re.search(r'(?<!static_)assert\(', sources['stat_set_kernels.hpp'])
@@ -103,6 +109,13 @@ def test_chunks(plan):
     plan([(('chunks', 1, 7), (0, 1)), (('chunks', 7, 7), (0, 7)), (('chunks', 8, 7), (0, 7, 7, 1)), (('chunks', 20, 7), (0, 7, 7, 7, 14, 6)),
           (('chunks', 65535, 65535), (0, 65535)), (('chunks', 65536, 65535), (0, 65535, 65535, 1)),
           (('chunks', 3, 1), (0, 1, 1, 1, 2, 1)), (('chunks', 3, 0), (0, 1, 1, 1, 2, 1)), (('chunks', 0, 7), ())])
+
+
+def test_upload_tables(plan):
+    """Host tables go up max(1, 1 GiB / (bins * 8)) at a time: a table larger than the budget still goes alone."""
+    gib = 1 << 30
+    plan([(('upload', 256), (524288, gib)), (('upload', 4 ** 12), (8, gib)), (('upload', 4 ** 13), (2, gib)), (('upload', 4 ** 14), (1, gib)),
+          (('upload', 4 ** 16), (1, gib)), (('upload', 1), (134217728, gib)), (('upload', 3), (44739242, gib)), (('upload', 4 ** 13 + 1), (1, gib))])
 
 
 def test_balance_grid(plan):

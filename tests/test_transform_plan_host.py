@@ -50,8 +50,10 @@ def test_header_knows_no_gpu():
                                                        'pool_slice_end(')),
                         ('kpal_transform.hip', ('balance_set_items(', 'balance_set_slots(', 'balance_set_workgroups(', 'kBalanceSetSmallMaxK',
                                                 'kBalanceSetSlotsPerCu', 'kBalanceSetThreads', 'pool_column_groups(', 'pool_slices(',
-                                                'pool_scratch_bytes(', 'shrink_set_launches(', 'transform_overlap(', 'transform_bytes_fit(', 'kTransformPartial',
-                                                'kTransformDisjoint'))):
+                                                'pool_scratch_bytes(', 'shrink_set_launches(', 'tables_overlap(', 'transform_bytes_fit(', 'kTransformPartial',
+                                                'kTransformDisjoint', 'check_bytes_at_k(', '#include "table_host.hpp"')),
+                        # the host front end of the table units: the overlap test and the bytes of a set behind the rungs the entries share
+                        ('table_host.hpp', ('transform_overlap(', 'transform_bytes_fit('))):
         text = re.sub(r'//.*', '', open(os.path.join(CSRC, user)).read())
         assert all(n in text for n in names), user
     # the launch names are the set's own: existing tests count the single-table ones
