@@ -541,7 +541,8 @@ int kpal_merge_device(kpal_ctx *ctx, size_t n, const int64_t *dev_left, const in
 
 /* Profile.shrink(factor), kpal/klib.py:329-352: out[j] = sum of the 4^factor counts that share the
  * (k - factor)-mer prefix j; 1 <= factor < k (else KPAL_E_INVALID, the reference's ValueError);
- * out has 4^(k - factor) entries and must not overlap the input. */
+ * out has 4^(k - factor) entries and must not overlap the input.  8-byte alignment of both is enough: the
+ * device entry reads 16 bytes at a time only where dev_counts is 16-byte aligned. */
 int kpal_shrink(kpal_ctx *ctx, int k, int factor, const int64_t *host_counts, int64_t *host_out);
 int kpal_shrink_device(kpal_ctx *ctx, int k, int factor, const int64_t *dev_counts, int64_t *dev_out);
 

@@ -296,7 +296,7 @@ KPAL_API int kpal_shrink_device(kpal_ctx *ctx, int k, int factor, const int64_t 
     CTX_ENTER(ctx);
     CHK(check_shrink(k, factor));
     CHK(check_pointers(dev_counts && dev_out));
-    return shrink_launch(ctx, "shrink", dev_counts, 1ULL << (2 * k), 1ULL << (2 * factor), dev_out);
+    return shrink_launch(ctx, "shrink", dev_counts, 1ULL << (2 * k), 1ULL << (2 * factor), dev_out, (uintptr_t)dev_counts % 16 == 0);
 }
 
 KPAL_API int kpal_shrink(kpal_ctx *ctx, int k, int factor, const int64_t *host_counts, int64_t *host_out)

@@ -74,5 +74,5 @@ inline int download_wait(kpal_ctx *ctx, int64_t *host, const int64_t *dev, uint6
 // Whether a pool kernel may take the rows of `bins` entries 16 bytes at a time.
 inline bool pool_rows_by_16(uint64_t bins, const void *tables, const void *out) { return bins % 2 == 0 && (uintptr_t)tables % 16 == 0 && (uintptr_t)out % 16 == 0; }
 // kpal_vec.hip: the shrink of n entries by m = 4^factor.  Up to m = 64 the shuffle form runs, which reads 16 bytes at a time --
-// unless the caller says the input is not aligned for that: kpal_shrink_set_device looks, kpal_shrink_device never has.
-int shrink_launch(kpal_ctx *ctx, const char *name, const int64_t *in, uint64_t n, uint64_t m, int64_t *out, bool in_aligned_16 = true);
+// unless the caller says the input is not aligned for that, and then the form that reads 8 bytes at a time: both entries look.
+int shrink_launch(kpal_ctx *ctx, const char *name, const int64_t *in, uint64_t n, uint64_t m, int64_t *out, bool in_aligned_16);

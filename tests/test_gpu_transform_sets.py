@@ -1,7 +1,12 @@
 """The balance, the shrink and the pool of whole SETS of tables on the GPU at the C-ABI (kpal_balance_set_device,
 kpal_shrink_set_device, kpal_pool_set_device; kpal/klib.py:285-298, 329-352, 269-283) against the oracle per table.  Counts
 are integers: every comparison is exact.  A table's result does not depend on the set it is in, the launches do not grow with
-the set, and a bad argument launches nothing.  Run on the GPU box: pytest -m gpu."""
+the set, and a bad argument launches nothing.  The shrink of ONE table on the device (kpal_shrink_device) is here too, where
+its input lies at an odd multiple of 8 bytes: it shares the launch of the set entry (shrink_launch).
+
+Measured on an MI355X: the whole file (76 tests) in 5.1 s, 3.4 s of it the tables of one balance test; the slowest shrink
+case is (8, 7) at 70 tables, 0.14 s.
+Run on the GPU box: pytest -m gpu."""
 import numpy as np
 import pytest
 
@@ -140,9 +145,11 @@ def test_balance_workgroups_take_several_items_across_tables(ctx, num_cu):
 
 # ---- shrink ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('n', (1, 3, 70))
-@pytest.mark.parametrize('k,factor', ((2, 1), (6, 3), (6, 4), (8, 7), (5, 2)))
+@pytest.mark.parametrize('k,factor', ((2, 1), (6, 3), (6, 4), (8, 7), (5, 2), (8, 1), (8, 2), (8, 3), (8, 4)))
 def test_shrink_sets_vs_oracle(ctx, k, factor, n):
-    """(6, 3): 64 inputs an output, the last case of the shuffle kernel; (6, 4): the wave-per-output kernel."""
+    """(6, 3): 64 inputs an output, the last case of the shuffle kernel; (6, 4): the wave-per-output kernel.  70 tables of
+    k = 8 are 2.29 M input pairs, more than the 8 x CUs x 256 threads of the shuffle kernel's grid: it goes around its rounds
+    more than once, the last time with part of the grid, for 4, 16 and 64 inputs an output; (8, 4) is the first factor past it."""
     tables = make_set(100 * k + 10 * factor + n, 4 ** k, n, shift=factor + n)
     want = np.stack([oracle.shrink(t, k, factor) for t in tables])
     with device_buffers(ctx, tables.nbytes, want.nbytes) as (src, dst):
@@ -175,6 +182,41 @@ def test_shrink_of_tables_at_an_odd_multiple_of_eight_bytes(ctx):
         ctx.h2d(src + 8, tables)
         ctx.shrink_set_device(4, 1, 5, src + 8, dst)
         assert np.array_equal(fetch(ctx, dst, want.shape), want)
+
+
+def test_shrink_of_a_set_at_an_odd_multiple_of_eight_bytes_by_64(ctx):
+    """(6, 3): the largest factor of the shuffle kernel, which reads 16 bytes at a time -- not from here."""
+    k, factor, n = 6, 3, 5
+    tables = make_set(63, 4 ** k, n, shift=1)
+    want = np.stack([oracle.shrink(t, k, factor) for t in tables])
+    with device_buffers(ctx, tables.nbytes + 16, want.nbytes) as (src, dst):
+        ctx.h2d(src + 8, tables)
+        ctx.h2d(dst, np.full(want.shape, -1, dtype=np.int64))
+        _, seen = launches(ctx, lambda: ctx.shrink_set_device(k, factor, n, src + 8, dst))
+        assert seen == {'shrink_set': 1}, seen
+        assert np.array_equal(fetch(ctx, dst, want.shape), want)
+        assert np.array_equal(fetch(ctx, src + 8, tables.shape), tables)
+
+
+@pytest.mark.parametrize('k,factor', ((4, 1), (4, 3), (6, 2), (6, 3), (8, 1)))
+def test_shrink_of_one_table_at_an_odd_multiple_of_eight_bytes(ctx, k, factor):
+    """kpal_shrink_device asks for 8-byte alignment only: up to 64 inputs an output it takes the kernel that reads 16 bytes at
+    a time where the input allows it, and the 8-byte one here."""
+    table = make_set(100 * k + factor, 4 ** k, 3, shift=5)[2]       # values of 2^60 to 2^62: the sums wrap
+    want = oracle.shrink(table, k, factor)
+    with device_buffers(ctx, table.nbytes + 16, want.nbytes) as (src, dst):
+        assert src % 16 == 0
+        ctx.h2d(src + 8, table)
+        ctx.h2d(dst, np.full(want.shape, -1, dtype=np.int64))
+        _, seen = launches(ctx, lambda: ctx.shrink_device(k, factor, src + 8, dst))
+        assert seen == {'shrink': 1}, seen
+        assert np.array_equal(fetch(ctx, dst, want.shape), want)
+        assert np.array_equal(fetch(ctx, src + 8, table.shape), table), 'the input was written'
+        # and from a 16-byte aligned address: the same sums
+        ctx.h2d(src, table)
+        ctx.h2d(dst, np.full(want.shape, -1, dtype=np.int64))
+        _, seen = launches(ctx, lambda: ctx.shrink_device(k, factor, src, dst))
+        assert seen == {'shrink': 1} and np.array_equal(fetch(ctx, dst, want.shape), want)
 
 
 # ---- pool ------------------------------------------------------------------------------------------------------------------

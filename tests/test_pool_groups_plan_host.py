@@ -89,6 +89,14 @@ def test_small_tables_share_a_workgroup(plan):
           (('iwg', 3000, 64), 375), (('iwg', 3001, 64), 376), (('iwg', 200, 256), 100), (('iwg', 7, 4096), 7), (('iwg', 0, 64), 0)])
 
 
+def test_every_lane_shift_below_a_wave_and_the_first_two_of_whole_waves(plan):
+    """The bins tests/test_gpu_pool_groups.py launches to reach the shifts 0 to 4, 6 and 7 (PACKED_BINS)."""
+    plan([(('lanes', 1), (0, 256)), (('lanes', 2), (0, 256)), (('lanes', 3), (1, 128)), (('lanes', 4), (1, 128)), (('lanes', 5), (2, 64)),
+          (('lanes', 16), (3, 32)), (('lanes', 17), (4, 16)), (('lanes', 32), (4, 16)), (('lanes', 100), (6, 4)), (('lanes', 128), (6, 4)),
+          (('lanes', 129), (7, 2)), (('lanes', 512), (8, 1)),
+          (('iwg', 3000, 1), 12), (('iwg', 3000, 17), 188), (('iwg', 3000, 100), 750), (('iwg', 291, 100), 73), (('iwg', 65605, 512), 65605)])
+
+
 def test_member_lists_keep_table_order(plan):
     #                bins CUs groups labels ...           status bad cut items members ct scratch | members | begin
     plan([(('labels', 64, 256, 3, 1, 0, 1, -1, 2, 0, 1), (0, -1, 0, 3, 6, 16, 0, 1, 5, 0, 2, 6, 4, 0, 2, 5, 6)),

@@ -114,6 +114,7 @@ def test_scratch_bytes(plan):
           (('scratch', 4096, 4096), 32848),                 # 40 + 16 + 32768 + 2 x 8 + 8
           (('scratch', 8193, 8193), 65688),                 # two slices, five window slices: 80 + 16 + 65544 + 40 + 8
           (('scratch', 4 ** 8, 4 ** 8), 524888),            # 320 + 16 + 524288 + 256 + 8
+          (('scratch', 1 << 20, 1 << 20), 8397848),         # 128 slices: 5120 + 16 + 8388608 + 4096 + 8
           (('scratch', 4 ** 12, 1048576), 8474648),         # 81920 + 16 + 8388608 + 4096 + 8
           (('scratch', 4 ** 16, 1048576), 29364248)])       # 20971520 + 16 + 8388608 + 4096 + 8
 
@@ -122,6 +123,8 @@ def test_tables_per_pass(plan):
     plan([(('per', 1, BUDGET, 0), 65535),                   # 80 bytes a table: the grid's limit
           (('per', 4096, BUDGET, 0), 8172),                 # 268435456 / 32848 = 8172.05
           (('per', 4 ** 8, BUDGET, 0), 511),                # / 524888 = 511.4
+          (('per', 1 << 20, 256 << 20, 0), 31),             # / 8397848 = 31.96: the seam tests/test_gpu_table_set_seams.py crosses
+          (('per', (1 << 20) + 1, BUDGET, 0), 31),
           (('per', 4 ** 12, BUDGET, 0), 31),                # / 8474648 = 31.7
           (('per', 4 ** 16, BUDGET, 0), 9),                 # / 29364248 = 9.1
           (('per', 4096, BUDGET, 2), 2), (('per', 4096, BUDGET, 100000), 8172), (('per', 4 ** 16, 1000, 0), 1), (('per', 4 ** 16, 1000, 5), 1)])

@@ -65,6 +65,23 @@ def test_header_knows_no_gpu():
     assert 'printf' not in kernels and not re.search(r'(?<!static_)assert\(', kernels) and 'asm' not in kernels
 
 
+def test_both_shrink_entries_look_at_the_alignment_of_their_input():
+    """The shuffle form of the shrink reads 16 bytes at a time, and the hardware may serve such a load from an address aligned
+    to 8 bytes only: a result cannot tell which form ran (tests/test_gpu_transform_sets.py compares the results).  So the text
+    is looked at: shrink_launch has no default for `in_aligned_16`, and each of its two callers passes what its input has."""
+    header = re.sub(r'//.*', '', open(os.path.join(CSRC, 'table_host.hpp')).read())
+    declaration = re.search(r'int shrink_launch\(([^;]*)\);', header).group(1)
+    assert declaration.rstrip().endswith('bool in_aligned_16') and '=' not in declaration, declaration
+    for unit, entry, pointer in (('kpal_vec.hip', 'kpal_shrink_device', 'dev_counts'), ('kpal_transform.hip', 'kpal_shrink_set_device', 'dev_in')):
+        text = re.sub(r'//.*', '', open(os.path.join(CSRC, unit)).read())
+        body = text[text.index('KPAL_API int %s(' % entry):]
+        body = body[:body.index('\n}\n')]
+        calls = [line for line in body.split('\n') if 'shrink_launch(' in line]
+        assert len(calls) == 1 and re.search(r', \(uintptr_t\)%s %% 16 == 0\)\)?;$' % pointer, calls[0]), (entry, calls)
+    launch = re.sub(r'//.*', '', open(os.path.join(CSRC, 'kpal_vec.hip')).read())
+    assert 'if (m <= 64 && in_aligned_16) LAUNCH(ctx, name, shrink_small_kernel,' in launch
+
+
 def test_sizes(plan):
     plan([(('sizes',), (2, 1024, 5, 256, 4, 8, 16, 1048576))])
 
