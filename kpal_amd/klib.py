@@ -155,7 +155,7 @@ def _fasta_records(handle):
     parts = []
     for line in handle:
         if isinstance(line, bytes):
-            line = line.decode('ascii', 'replace')
+            line = line.decode('latin-1')      # (one character per byte, as the device reads them: 0x85 and 0xa0 are blanks)
         if line.startswith('>'):
             if name is not None:
                 yield name, ''.join(parts).translate(_DROPPED)

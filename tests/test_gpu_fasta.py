@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle
+from alphabet_cases import expected_flat, seqio_records
 
 pytestmark = pytest.mark.gpu
 
@@ -18,33 +19,6 @@ pytestmark = pytest.mark.gpu
 def ctx():
     from kpal_amd import _native
     return _native.context()
-
-
-def seqio_records(text):
-    """(name, sequence) per record by Biopython's rules, written independently of kpal_amd.klib:
-    universal newlines, lines before the first '>' skipped, name = first word of the title, every
-    sequence line rstrip()-ed, ' ' and '\\r' removed from the joined record -- so a tab inside a
-    line stays (and splits k-mer windows), a tab at the end of a line goes."""
-    import re
-    records, title, lines = [], None, []
-    for line in re.split('\r\n|\r|\n', text):
-        if line[:1] == '>':
-            if title is not None:
-                records.append((title, lines))
-            title, lines = line[1:].rstrip(), []
-        elif title is not None:
-            lines.append(line.rstrip())
-    if title is not None:
-        records.append((title, lines))
-    out = []
-    for title, lines in records:
-        words = title.split(None, 1)
-        out.append((words[0] if words else '', ''.join(lines).replace(' ', '').replace('\r', '')))
-    return out
-
-
-def expected_flat(text):
-    return b''.join(b'\n' + seq.encode('latin-1') for _, seq in seqio_records(text))
 
 
 def random_fasta(rnd, n_records, max_len, eol='\n'):
